@@ -9,10 +9,14 @@ HBM before the timed region.  One process per GPU; groups shard across ranks
 with no data-path collective (weak scaling: G groups PER GPU).
 
 Prints ONE JSON line (rank 0).  `value` counts leader-side Accepting->Committed
-transitions (multipaxos/messages.rs:412-433) per second, whole job.
-Also reports, in the same line: the HBM roofline of the quorum kernel (R3), the
-CPU oracle timed on this host on a bounded sample (`cpu_baseline`), and the
-RS(3,2) encode rate of BASELINE config 4 (`rs_encode`).
+transitions (multipaxos/messages.rs:412-433) per second, whole job; `ms_per_step`
+is one timed tick, and exactly --steps ticks are timed.  The line also carries
+the HBM roofline of the quorum kernel (R3), from the timed ticks' own events.
+With --full it also reports the CPU oracle timed on this host on a bounded
+sample (`cpu_baseline`), the RS(3,2) encode rate of BASELINE config 4
+(`rs_encode`), the other protocols' legs and the `l2` pass, and times several
+regions of --steps ticks (the median is reported).  --dump-outputs DIR writes
+what the last timed tick left as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -194,7 +198,14 @@ TIMEOUT_HORIZON = 72     # ticks of the default run (60 timed + 12 warm-up): --t
 
 
 def n_regions(args):
+    """timed regions of --steps ticks the workload's leader changes are drawn for (timeout_span)"""
     return args.repeats if args.repeats > 0 else (9 if args.steps <= 30 else 3)
+
+
+def timed_regions(args):
+    """timed regions the run takes: a plain run times exactly --steps ticks (the first of the n_regions(args) regions of the same
+    workload); --full or an explicit --repeats take all of them and report the median"""
+    return n_regions(args) if (args.full or args.repeats > 0) else 1
 
 
 def timeout_span(args):
@@ -236,11 +247,19 @@ def parse():
     ap.add_argument("--layout", choices=("colocated", "spread", "spread-epaxos", "colocated-epaxos", "spread-rspaxos"), default="colocated",
                     help="spread* = SURVEY 8e L2: replica r of block b on rank (b + r) mod N")
     ap.add_argument("--spread-ranks", type=int, default=4, help="spread layouts on ONE GPU: virtual ranks inside the process")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions of --steps ticks (median reported); 0 = 9 if steps <= 30 else 3")
-    ap.add_argument("--no-l2", action="store_true", help="skip the `l2` object (the workload a few ticks in the spread layout)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle baseline")
-    ap.add_argument("--no-rs", action="store_true", help="skip the RS(3,2) encode leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other protocols' legs")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed regions of --steps ticks (median reported); 0 = one region, or with --full 9 if steps <= 30 else 3")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: repeated timed regions (median), the `l2` pass, the CPU "
+                         "baselines, the RS(3,2) encode and the other protocols' legs, the --fused per-round pass; off: set up, warm "
+                         "up, time --steps ticks, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left (counters, a seeded sample of the replicas' state) "
+                         "as DIR/<name>.npy, float32 / float64, < 64 MB (the co-located MultiPaxos layout)")
+    ap.add_argument("--no-l2", action="store_true", help="--full: skip the `l2` object (the workload a few ticks in the spread layout)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-rs", action="store_true", help="--full: skip the RS(3,2) encode leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the other protocols' legs")
     ap.add_argument("--late-legs", action="store_true", help="also run the replica-engine / CRaft / quorum-read legs (child processes)")
     ap.add_argument("--role-rotation", type=int, default=0, help="1: rows of the bulk round launches by role (row 0 = every leader)")
     ap.add_argument("--leg", default=None, help="internal: run one secondary leg in this process and print its JSON")
@@ -1745,6 +1764,66 @@ def launch_check(rank, local, world):
         print(json.dumps({"launch_check": True, "n_gpus": world, "ranks": ranks, "backend": ("nccl" if gpu else "gloo") if world > 1 else None}))
 
 
+def resident_events(torch, st, n_ticks, dev):
+    """the events of ticks [0, n_ticks) of the headline stream in HBM before the clock starts: (fired, events), events[t] holding
+    what st.tick_events(t) holds, array for array.  A tick without a timer passes no timeout arrays (fired[t] is False), and the
+    clients' targets change only on the tick after a timer fired: the device holds one array per fired tick and per distinct
+    target, built there, so that the host's work grows with the leader changes and not with the ticks."""
+    from summerset_amd.stream import NO_REPLICA
+    tt = st.timeout_tick
+    at = np.unique(tt[(tt >= 0) & (tt < n_ticks)])              # the ticks a timer fires on
+    fired = [False] * n_ticks
+    for t in at.tolist():
+        fired[t] = True
+    tt_dev = torch.from_numpy(tt).to(dev)
+    had = tt_dev >= 0
+
+    def fill(mask, val, other):
+        return torch.full(tt.shape, other, dtype=torch.uint8, device=dev).masked_fill_(mask, val)
+    # target k: the clients' replica after the first k fired ticks, from tick at[k - 1] + 1 on (tick_events: moved = t > timeout_tick)
+    firsts = [0] + [t + 1 for t in at.tolist() if t + 1 < n_ticks]
+    targets = [fill(had & (tt_dev < t), st.timeout_rep, 0) for t in firsts]
+    timers = {t: (fill(tt_dev == t, st.timeout_rep, NO_REPLICA), fill(tt_dev == t, 0, NO_REPLICA)) for t in at.tolist()}
+    k_of = np.searchsorted(at, np.arange(n_ticks), side="left")  # fired ticks before t
+    events = []
+    for t in range(n_ticks):
+        rep, src = timers.get(t, (None, None))
+        events.append({"timeout_rep": rep, "timeout_src": src, "req_target": targets[k_of[t]]})
+    return fired, events
+
+
+DUMP_BYTES = 48 << 20            # --dump-outputs: what the sample of the replicas' state may take
+
+
+def dump_outputs(eng, path, group_base=0, seed=0x5EED5EED):
+    """--dump-outputs: what a caller of the timed path reads after its last step -- every replica's counters (commits, redirects,
+    rejects: `counters.npy`, [R][3]) and its canonical state (MultiPaxosCluster.dump, one `<field>.npy` per field with the replicas
+    on the first axis) of a fixed, seeded sample of 64-group blocks (`sample_groups.npy`: their global ids).  float32 for the
+    byte-wide fields, float64 for the rest; as many blocks as DUMP_BYTES holds."""
+    os.makedirs(path, exist_ok=True)
+    G, R = eng.G, eng.R
+    starts = list(range(0, G, 64))
+
+    def block(rep, g0):
+        return {k: v.astype(np.float32 if v.dtype.itemsize == 1 else np.float64) for k, v in eng.dump(rep, g0, min(64, G - g0)).items()}
+    per_block = R * sum(v.nbytes for v in block(0, 0).values())
+    if per_block > 64 << 20:
+        raise SystemExit("bench.py --dump-outputs: one block of 64 groups is %d bytes of state (limit 64 MB)" % per_block)
+    n = max(1, min(len(starts), DUMP_BYTES // per_block))
+    pick = sorted(np.random.default_rng(seed).choice(len(starts), n, replace=False).tolist())
+    out = {}
+    for rep in range(R):
+        parts = [block(rep, starts[b]) for b in pick]
+        for k in parts[0]:
+            out.setdefault(k, []).append(np.concatenate([p[k] for p in parts], axis=-1))
+    arrays = {k: np.stack(v) for k, v in out.items()}
+    arrays["counters"] = np.array([[eng.counters(r)[k] for k in ("commits", "redirects", "rejects")] for r in range(R)], np.float64)
+    arrays["sample_groups"] = np.concatenate([np.arange(starts[b], min(starts[b] + 64, G)) for b in pick]).astype(np.float64) + group_base
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return arrays
+
+
 def main():
     args = parse()
     from summerset_amd import shard
@@ -1754,6 +1833,10 @@ def main():
     _, rank, local, world = plan
     if args.launch_check:
         return launch_check(rank, local, world)
+    if args.dump_outputs and args.layout != "colocated":
+        raise SystemExit("bench.py: --dump-outputs is for the co-located MultiPaxos layout (the headline line)")
+    if not args.full:                              # a plain run: the headline figure and nothing else
+        args.no_l2 = args.no_cpu = args.no_rs = args.no_extra = True
     import torch
     import torch.distributed as dist
     if args.leg == "l2":                           # child of the headline run at N = 1: the spread layout on virtual ranks
@@ -1797,9 +1880,10 @@ def main():
 
     G, R, S, W, H = args.groups, 5, args.slots, args.window, args.hb_every
     cap = W + 4
-    reps = n_regions(args)
+    reps = timed_regions(args)
     n_timed = args.warmup + reps * args.steps     # warm-up, then `reps` timed regions of exactly --steps ticks each
-    n_ticks = n_timed + args.round_ticks          # the per-round pass goes on where the timed region stopped
+    round_pass = bool(args.full and args.fused and args.round_ticks)
+    n_ticks = n_timed + (args.round_ticks if round_pass else 0)   # the per-round pass goes on where the timed region stopped
     if args.fused:
         args.straggler_ticks = 0                  # the fused tick kernel and the side stream exclude each other
     # cluster, stream and launch mode come from summerset_amd/workloads.py: the SAME helpers the BASELINE-size parity tests
@@ -1813,12 +1897,7 @@ def main():
     for t in range(args.pool):
         x = st.tick(t)
         pool.append({k: torch.from_numpy(x[k]).to(dev) for k in ("req_cnt", "req_val", "ackctl")})
-    events = []
-    for t in range(n_ticks):
-        e = st.tick_events(t)
-        events.append({k: torch.from_numpy(v).to(dev) for k, v in e.items() if isinstance(v, np.ndarray)})
-
-    fired = [bool((st.timeout_tick == t).any()) for t in range(n_ticks)]   # host-side fact: did any timer fire
+    fired, events = resident_events(torch, st, n_ticks, dev)   # fired: host-side fact, did any timer fire
 
     def tick_args(t):
         p, e = pool[t % args.pool], events[t]
@@ -1871,10 +1950,12 @@ def main():
         c1 = sum(eng.counters(r)["commits"] for r in range(R))
         regions.append(shard.reduce_metric(el, c1 - c0, device=dev))
     elapsed, commits = sorted(regions)[len(regions) // 2]        # the median region (by time)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs, group_base=shard.group_range(G * world, world, rank)[0])
     rej = sum(eng.counters(r)["rejects"] for r in range(R))
     overflow = int(eng.dump(0)["overflow"].sum()) if G <= 4096 else None
     # untimed: the same workload a few ticks further through the per-round kernels, an event pair around each
-    if args.fused and args.round_ticks:
+    if round_pass:
         eng.profile_enable(True)
         for t in range(n_timed, n_ticks):
             eng.tick(**tick_args(t))
@@ -1954,7 +2035,7 @@ def main():
                               "side-stream launch per batch for the straggler list" % min(args.batch, 16)) if args.batch else
                              "five per-round launches per tick + one side-stream launch per tick for the straggler list"},
         "roofline": roof,
-        "kernels": prof, "kernels_pass": "untimed per-round pass" if args.fused else "timed region",
+        "kernels": prof, "kernels_pass": ("untimed per-round pass" if round_pass else None) if args.fused else "timed region",
         "rejected_batches": rej, "overflow_groups": overflow,
         "generic_path_batches": [eng.debug_generic_units(r) for r in range(R)],
         "straggler_list": dict(zip(("capacity", "wanted_by_last_mark_pass"), eng.straggler_stats())) if args.straggler_ticks else None,

@@ -8,6 +8,7 @@
 #   rocprofv3 --kernel-trace --stats over the EXACT driver command, summarised over the headline process
 TAG=${1:-t3z}
 mkdir -p gpurun_out
+REC=$PWD/$_          # the directory just made: the bench lines below write the record there too
 R=$PWD
 # 0. is this box's GPU sane?  (round 5's third take met one that faulted in every process; every step below then ran into its own
 # timeout and the call used up the round's device minutes.)  One small launch of the hot path against the oracle, or nothing.
@@ -31,9 +32,10 @@ done
 # 2. the suite, the bench lines
 timeout 900 python -m pytest tests -m gpu -q -rxX -p no:cacheprovider --durations=8 2>&1 | tail -40 > gpurun_out/${TAG}_gputests.log
 tail -3 gpurun_out/${TAG}_gputests.log
-timeout 900 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; cp bench_detail.json gpurun_out/${TAG}_bench_detail.json; tail -c 300 gpurun_out/${TAG}_bench.json; echo
+# (--full: the default line with every leg, the CPU baselines, the l2 pass and the median of its timed regions)
+timeout 900 python bench.py --full > $REC/${TAG}_bench.json 2> $REC/${TAG}_bench.err; cp bench_detail.json $REC/${TAG}_bench_detail.json; tail -c 300 $REC/${TAG}_bench.json; echo
 timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_driver_command.json 2>> gpurun_out/${TAG}_bench.err; cp bench_detail.json gpurun_out/${TAG}_bench_driver_command_detail.json
-timeout 300 python bench.py --timeouts 0 --no-cpu --no-rs --no-extra --no-l2 > gpurun_out/${TAG}_bench_steady.json 2>> gpurun_out/${TAG}_bench.err
+timeout 300 python bench.py --full --timeouts 0 --no-cpu --no-rs --no-extra --no-l2 > $REC/${TAG}_bench_steady.json 2>> $REC/${TAG}_bench.err
 # 3. per-kernel times of the driver's exact command
 ( cd /tmp && export TMPDIR=/tmp
   timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${TAG}_prof_bench -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 > $R/gpurun_out/${TAG}_bench_under_rocprof.json 2> /dev/null )
