@@ -1738,13 +1738,13 @@ template <int NR> constexpr int epc_sets() { return NR <= 5 ? EPC_SETS : 1; }   
 //   sh_pa  [set][leader s][10][64]: what leader s broadcasts -- word 0 flags (bit 0 proposed, bits 8-15 the decision, bit 16
 //          committed), 1 col, 2 key, 3-4 seq, 5-9 deps: the PreAccept's (seq0, deps0) until s's own PreAcceptReply step
 //          overwrites them with the decision's (every acceptor has taken the PreAccept by then: barrier behind step R)
-//   sh_rep [set][leader s][acceptor q != s][7][64]: q's PreAcceptReply -- seq lo, seq hi | flag << 31, deps[5]
+//   sh_rep [set][leader s][acceptor q != s][7][64]: q's PreAcceptReply -- seq lo, seq hi, deps[5] (seq 0: no reply)
 //   sh_sc  [wavefront][4][NR][64]: the lanes' per-row scalars (EpLaneT::bind_cache)
 //   sh_af  [set][leader s][acceptor q][64] bytes: q's AcceptReply flag
 // The out[] arrays are still WRITTEN (they are the call's outputs); nothing of the tick reads them back.  The leader's step takes
 // a reply out of LDS when its turn comes instead of holding all four in registers (50 VGPRs of the old step).
 template <int NR> constexpr bool epc_lds() { return NR <= 5; }
-constexpr int EPC_PA_WORDS = 10, EPC_REP_WORDS = 7;       // a reply: seq lo, seq hi | flag << 31 (a sequence number stays below 2^63), deps[5]
+constexpr int EPC_PA_WORDS = 10, EPC_REP_WORDS = 7;       // a reply: seq lo, seq hi, deps[5]; no reply: seq 0 (a reply's seq is 1 + a max, >= 1)
 template <int NR>
 struct EpRepliesInLds {
     const uint32_t *rep;                                                     // sh_rep + the set's and the leader's offset
@@ -1752,9 +1752,8 @@ struct EpRepliesInLds {
     __device__ __forceinline__ void get(uint32_t p, uint32_t &f, uint64_t &rb, uint64_t &rs, uint32_t (&rd)[NR]) const {
         const uint32_t qi = p - (p > s ? 1u : 0u);                           // (p != s: the caller skips the leader itself)
         const uint32_t *w = rep + (size_t)qi * EPC_REP_WORDS * 64 + lane;
-        const uint32_t hi = w[64];
-        f = hi >> 31;
-        rs = (uint64_t)w[0] | ((uint64_t)(hi & 0x7FFFFFFFu) << 32);
+        rs = (uint64_t)w[0] | ((uint64_t)w[64] << 32);
+        f = rs != 0ull;
         rb = (f & 1u) ? (uint64_t)(s + 1u) : 0ull;                           // an acceptor replies with the message's ballot
 #pragma unroll
         for (int k = 0; k < NR; k++) rd[k] = k < 5 ? w[(2 + k) * 64] : EP_NONE;
@@ -1838,7 +1837,8 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), (NR <= 5 ? EPC_WAVES_PER_
                     for (int i = 0; i < NR; i++) in[i] = (i < 5 && (uint32_t)i < R) ? PA(s, 5 + i) : EP_NONE;
                     ep_acceptor_lane_in<0, NR, RECOVERY>(L, on, s, s, PA(s, 1), (uint64_t)(s + 1u), (uint64_t)PA(s, 3) | ((uint64_t)PA(s, 4) << 32), in,
                                                          PA(s, 2), of, ob, os, d);
-                    RP(s, q, 0) = (uint32_t)os; RP(s, q, 1) = ((uint32_t)(os >> 32) & 0x7FFFFFFFu) | ((uint32_t)(of & 1u) << 31);
+                    const uint64_t rs = (of & 1u) ? os : 0ull;
+                    RP(s, q, 0) = (uint32_t)rs; RP(s, q, 1) = (uint32_t)(rs >> 32);
 #pragma unroll
                     for (int i = 0; i < NR; i++) if (i < 5) RP(s, q, 2 + i) = d[i];
                     EPC_SUB(L, 6);
@@ -2069,7 +2069,7 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), EPC_WAVES_PER_EU) void ep
         EpInst<NR> I;
         I.make_null();
         I.bal = (uint64_t)(s + 1u);
-        I.seq = (uint64_t)RP(s, q, 0) | ((uint64_t)(RP(s, q, 1) & 0x7FFFFFFFu) << 32);
+        I.seq = (uint64_t)RP(s, q, 0) | ((uint64_t)RP(s, q, 1) << 32);
 #pragma unroll
         for (int r = 0; r < NR; r++) I.d[r] = RP(s, q, 2 + r);
         I.set_status(EST_PREACCEPTING); I.set_key(k); I.set_bk(2u | (s << 2));
@@ -2226,7 +2226,7 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), EPC_WAVES_PER_EU) void ep
                 I.set_status(EST_PREACCEPTING); I.set_key(k); I.set_bk(2u | ((uint32_t)s << 2));
                 defm |= 1u << s;                                             // (the record and the key's entry: see materialize)
                 if (my[s][s] == EP_NONE || c > my[s][s]) hcm |= 1u << s;
-                RP(s, q, 0) = (uint32_t)sn; RP(s, q, 1) = ((uint32_t)(sn >> 32) & 0x7FFFFFFFu) | (1u << 31);
+                RP(s, q, 0) = (uint32_t)sn; RP(s, q, 1) = (uint32_t)(sn >> 32);      // (sn >= 1: the reply is there)
 #pragma unroll
                 for (int i = 0; i < NR; i++) RP(s, q, 2 + i) = I.d[i];
             }
@@ -2243,7 +2243,8 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), EPC_WAVES_PER_EU) void ep
                 for (int i = 0; i < NR; i++) in[i] = (uint32_t)i < R ? PA(s, 5 + i) : EP_NONE;
                 ep_acceptor_lane_in<0, NR, false>(L, on, s, s, PA(s, 1), (uint64_t)(s + 1u), (uint64_t)PA(s, 3) | ((uint64_t)PA(s, 4) << 32), in,
                                                   PA(s, 2), of, ob, os, d);
-                RP(s, q, 0) = (uint32_t)os; RP(s, q, 1) = ((uint32_t)(os >> 32) & 0x7FFFFFFFu) | ((uint32_t)(of & 1u) << 31);
+                const uint64_t rs = (of & 1u) ? os : 0ull;
+                RP(s, q, 0) = (uint32_t)rs; RP(s, q, 1) = (uint32_t)(rs >> 32);
 #pragma unroll
                 for (int i = 0; i < NR; i++) RP(s, q, 2 + i) = d[i];
             }
@@ -2350,7 +2351,7 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), EPC_WAVES_PER_EU) void ep
             const uint32_t i = L.ix(m ? s : 0u, col[s]);
             w0[s] = (u32x4){0u, 0u, 0u, 0u}; w2[s] = (u32x4){0u, 0u, 0u, 0u};
             if ((defm >> s) & 1u) {                                          // what materialize(s) would have stored: known, not loaded
-                w0[s] = (u32x4){(uint32_t)(s + 1u), 0u, RP(s, q, 0), RP(s, q, 1) & 0x7FFFFFFFu};
+                w0[s] = (u32x4){(uint32_t)(s + 1u), 0u, RP(s, q, 0), RP(s, q, 1)};
                 w2[s] = (u32x4){RP(s, q, 6), (uint32_t)EST_PREACCEPTING | (PA(s, 2) << 8) | ((2u | ((uint32_t)s << 2)) << 16), 0u, EP_NONE};
             } else if (m) {
                 if ((uint32_t)s != q) w0[s] = EA(v.p0, i);
@@ -2485,7 +2486,7 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), EPC_WAVES_PER_EU) void ep
                     }
                     // deps[0..3] as my PreAcceptReply of this tick carried them are what the cell holds while it is still PreAccepting:
                     // the word is written only where the decision differs
-                    const bool same_p1 = !fresh && (w2[s].y & 0xFFu) == EST_PREACCEPTING && (RP(s, q, 1) >> 31) && RP(s, q, 2) == PA(s, 5) && RP(s, q, 3) == PA(s, 6) &&
+                    const bool same_p1 = !fresh && (w2[s].y & 0xFFu) == EST_PREACCEPTING && (RP(s, q, 0) | RP(s, q, 1)) != 0u && RP(s, q, 2) == PA(s, 5) && RP(s, q, 3) == PA(s, 6) &&
                                          RP(s, q, 4) == PA(s, 7) && RP(s, q, 5) == PA(s, 8);
                     if (!same_p1)
                         EA(v.p1, i) = (u32x4){PA(s, 5), NR > 1 ? PA(s, 6) : EP_NONE, NR > 2 ? PA(s, 7) : EP_NONE, NR > 3 ? PA(s, 8) : EP_NONE};
@@ -2544,6 +2545,9 @@ __global__ __launch_bounds__(NR * 64 * epc_sets<NR>(), EPC_WAVES_PER_EU) void ep
 // counts for the next tick.
 #ifndef EPC_CL_LANES
 #define EPC_CL_LANES 2u                       // (1: the same; 4: +12 us per tick, 8: +6, profiles/s28)
+#endif
+#ifndef EPC_CL_MAX_BLOCKS                     // the grid's blocks per replica: a longer list walks the loop below in several passes
+#define EPC_CL_MAX_BLOCKS 1024u               // (the emulator builds with a small cap so that its tests take those passes)
 #endif
 #ifdef EPC_CL_NOLDS                                 // (experiments, profiles/s35: the launch without LDS -- per-row scalars and the walk's arrays in place -- so that
 constexpr bool EPC_CL_LDS = false;                  //  its blocks fit on a CU beside a block of the batched kernel)
@@ -3180,7 +3184,7 @@ static int ep_cluster_tick_one_launch(smr_ep_cluster *c, const uint8_t *const *k
             c->parity ^= 1u;
             hipLaunchKernelGGL((ep_cluster_tick_pm_kernel<NR>), dim3((G + 64 * epc_sets<NR>() - 1) / (64 * epc_sets<NR>())), dim3(R * 64 * epc_sets<NR>()), 0,
                                (hipStream_t)stream, a);
-            hipLaunchKernelGGL((ep_cluster_commit_one_by_one_kernel<NR>), dim3(R, std::min<uint32_t>((G + EPC_CL_LANES - 1u) / EPC_CL_LANES, 1024u)), dim3(64), 0, (hipStream_t)stream, a);
+            hipLaunchKernelGGL((ep_cluster_commit_one_by_one_kernel<NR>), dim3(R, std::min<uint32_t>((G + EPC_CL_LANES - 1u) / EPC_CL_LANES, EPC_CL_MAX_BLOCKS)), dim3(64), 0, (hipStream_t)stream, a);
         }
     } else if (a.quiet)
         hipLaunchKernelGGL((ep_cluster_tick_kernel<NR, false>), dim3((G + 64 * epc_sets<NR>() - 1) / (64 * epc_sets<NR>())), dim3(R * 64 * epc_sets<NR>()), 0,

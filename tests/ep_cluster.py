@@ -189,6 +189,60 @@ def zipf_keys(rng, R, G, n_keys, p_propose=0.9):
     return k
 
 
+# ---- schedules that force the rare steps (keys [R][G] of one tick; drop masks in `tick`'s form) ------------------------------
+def same_key(rng, R, G, n_keys):
+    """every replica proposes, all of a group on ONE key (a clique of R instances of one key in the same tick)"""
+    return np.repeat(rng.integers(0, n_keys, G, dtype=np.uint8)[None, :], R, axis=0)
+
+
+def idle_then_hot(rng, R, G, n_keys, t, W, p_propose=0.9):
+    """a group's replicas stay on one key for W + 2 ticks, then move on to the next (key k + 1 mod n_keys): a key comes back
+    after (n_keys - 1) (W + 2) > W idle ticks, when its highest columns have left the ring.  Staggered per group (a seeded
+    offset of the group id), so that the comebacks fall on different ticks"""
+    off = (np.arange(G, dtype=np.int64) * 7919 + 13) % (W + 2)
+    k = np.repeat((((t + off) // (W + 2)) % n_keys).astype(np.uint8)[None, :], R, axis=0)
+    k[rng.random((R, G)) >= p_propose] = NO_KEY
+    return k
+
+
+def silent_rows(keys, t, who, t0, n):
+    """replica `who` proposes nothing (NO_KEY) in ticks t0 .. t0 + n - 1"""
+    if t0 <= t < t0 + n:
+        keys = keys.copy()
+        keys[who] = NO_KEY
+    return keys
+
+
+def isolated_leader(R, G, who, groups):
+    """every PreAccept of leader `who` is lost, in the groups of the bool mask `groups`: it hears no reply"""
+    return {(who, q): groups.copy() for q in range(R) if q != who}
+
+
+def deaf_acceptor(R, G, who, groups):
+    """every PreAccept TO replica `who` is lost in `groups`: every leader loses that acceptor's reply (a quorum of the others
+    still answers)"""
+    return {(s, who): groups.copy() for s in range(R) if s != who}
+
+
+def lost_replies(flags_mask):
+    """a `via` for `tick`: the PreAcceptReplies of the (acceptor, group) pairs set in flags_mask(s) ([R][G] bool, for leader s)
+    are lost on their way back -- the acceptor took the PreAccept and holds the instance, the leader never hears of it"""
+    def via(s, col, ballot, seq, deps, flags):
+        return ballot, seq, deps, np.where(flags_mask(s), np.uint8(0), flags).astype(np.uint8)
+    return via
+
+
+def wide_seq_via(base, off, pick):
+    """a `via` for `tick`: the PreAcceptReplies to leader s with pick(s) ([R][G] bool) set carry seq max(seq, base - off[g]) (uint64,
+    wrapping like the reference's u64) -- the leader commits that instance with a sequence number near `base`, and every later
+    instance of its key climbs from there"""
+    def via(s, col, ballot, seq, deps, flags):
+        big = np.uint64(base) - off.astype(np.uint64)
+        m = pick(s) & (flags == 1)
+        return ballot, np.where(m, np.maximum(seq, big[None, :]), seq).astype(np.uint64), deps, flags
+    return via
+
+
 # ---- explicit prepare: a command leader dies mid-instance, the others recover its row ------------------------------------
 def crash_tick(reps, dead, keys, rng, G):
     """replica `dead` proposes keys[g]; per group the run is cut at a seeded point: (0) PreAccepts reach a random subset of

@@ -29,8 +29,10 @@ _BASE = [CXX, "-O1", "-gline-tables-only", "-fno-optimize-sibling-calls", "-fno-
          "-w", "-I", _HERE]
 # STRAG_BATCH_BLOCKS: the side launch's grid -- 192 blocks of 512 lanes on the device, where a listed group has a block to itself; here a
 # launch costs its lanes whether they have work or not, and 12 blocks x 6 lanes walk a test's list of 100-200 groups in several passes
-# (the multi-pass loop the device's grid hardly ever enters)
-_KERN = ["-DSMR_ARENA_GUARD=4096", "-DSTRAG_BATCH_BLOCKS=12", "-mllvm", "-disable-block-placement", "-fsanitize=thread", "-mllvm",
+# (the multi-pass loop the device's grid hardly ever enters); EPC_CL_MAX_BLOCKS: the same for the EPaxos one-by-one launch -- 1024
+# blocks of 2 listed lanes per replica on the device, here 3 blocks, so that a tick that lists more than 6 lanes at a replica
+# takes a second pass
+_KERN = ["-DSMR_ARENA_GUARD=4096", "-DSTRAG_BATCH_BLOCKS=12", "-DEPC_CL_MAX_BLOCKS=3", "-mllvm", "-disable-block-placement", "-fsanitize=thread", "-mllvm",
          "-tsan-instrument-func-entry-exit=0", "-mllvm", "-tsan-instrument-atomics=0", "-mllvm", "-tsan-instrument-memintrinsics=0"]
 
 

@@ -510,13 +510,16 @@ def run_epaxos_slices(cuda, oracle, G, W, K, T, width, n_slices, execute=True, l
 
 
 def test_config4_epaxos_65536_groups_all_replicas_propose(cuda, oracle):
-    run_epaxos_slices(cuda, oracle, G=65536, W=16, K=64, T=8, width=512, n_slices=6)
+    W, T = 16, 36                                        # T = 2W + 4: every row's ring wraps twice
+    assert T >= 2 * W + 4
+    run_epaxos_slices(cuda, oracle, G=65536, W=W, K=64, T=T, width=512, n_slices=6)
 
 
-def run_epaxos_cluster_slices(cuda, oracle, G, W, K, T, width, n_slices, phase_major, loss=0.1):
+def run_epaxos_cluster_slices(cuda, oracle, G, W, K, T, width, n_slices, phase_major, loss=0.1, keys_fn=None):
     """BASELINE config 5 through `smr_ep_cluster_tick` -- the whole tick ONE launch -- at full size, against five oracles per
     slice wired into tests/ep_cluster.py's loop in the same order: every leader's outputs every tick, every replica's protocol
-    and execution state at the end"""
+    and execution state at the end.  keys_fn(rng, R, G, K): the tick's proposals (default Zipf).  Returns the lanes of every
+    tick that left the batched CommitNotice step (smr_ep_cluster_batch_stats: the one-by-one launch's lists, all replicas)"""
     import torch
     import ep_cluster as ec
     from summerset_amd import EPaxosReplicaGroup, ep_cluster
@@ -528,10 +531,13 @@ def run_epaxos_cluster_slices(cuda, oracle, G, W, K, T, width, n_slices, phase_m
     rng = np.random.default_rng(G + W + 1)
     dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)   # noqa: E731
     fast = slow = 0
+    listed = []
     for t in range(T):
-        keys = ec.zipf_keys(rng, R, G, K)
+        keys = (keys_fn or ec.zipf_keys)(rng, R, G, K)
         drop = {(s, q): rng.random(G) < loss for s in range(R) for q in range(R) if s != q}
+        before = job.batch_stats()["commit_lanes_one_by_one"]
         oe = job.tick([dv(keys[r]) for r in range(R)], {k: dv(v) for k, v in drop.items()})
+        listed.append(job.batch_stats()["commit_lanes_one_by_one"] - before)
         oe = [{k: v.cpu().numpy() for k, v in o.items()} for o in oe]
         for (g0, n), oc in zip(sl, orcs):
             oo = ec.tick(oc, np.ascontiguousarray(keys[:, g0:g0 + n]), {k: v[g0:g0 + n] for k, v in drop.items()}, phase_major=phase_major)
@@ -549,9 +555,13 @@ def run_epaxos_cluster_slices(cuda, oracle, G, W, K, T, width, n_slices, phase_m
                     assert np.array_equal(a[name], b[name]), (g0, r, name)
     job.close()
     assert fast > 0 and slow > 0
+    return listed
 
 
 @pytest.mark.parametrize("phase_major", [False, True])
 def test_config5_epaxos_65536_groups_one_launch(cuda, oracle, phase_major):
-    """the one-launch cluster tick at BASELINE config 5's size, in the loops' order and with the leaders' steps phase by phase"""
-    run_epaxos_cluster_slices(cuda, oracle, G=65536, W=16, K=64, T=8, width=512, n_slices=4, phase_major=phase_major)
+    """the one-launch cluster tick at BASELINE config 5's size, in the loops' order and with the leaders' steps phase by phase;
+    T = 2W + 4 ticks: every row's ring wraps twice"""
+    W, T = 16, 36
+    assert T >= 2 * W + 4
+    run_epaxos_cluster_slices(cuda, oracle, G=65536, W=W, K=64, T=T, width=512, n_slices=4, phase_major=phase_major)

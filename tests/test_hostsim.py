@@ -450,6 +450,41 @@ def test_device_resident_epaxos_cluster_tick_on_the_host(sim, oracle):
         t.run_shared_table_vs_private("cpu", G=150, K=6)             # round 5: one per-key table per cluster vs private tables
 
 
+@pytest.mark.parametrize("base", [2**31 - 3, 2**32 - 3, 2**63 - 3])
+def test_epaxos_cluster_tick_wide_seq_on_the_host(sim, oracle, base):
+    """tests/test_zzz_ep_cluster_edges_gpu.py: sequence numbers across 2^31, 2^32 - 1, 2^32 and 2^63, both orders"""
+    import test_zzz_ep_cluster_edges_gpu as t
+    with sim.patched():
+        for pm in (False, True):
+            t.run_wide_seq("cpu", oracle, base, G=67, W=8, phase_major=pm)
+
+
+def test_epaxos_cluster_tick_edges_on_the_host(sim, oracle):
+    """tests/test_zzz_ep_cluster_edges_gpu.py: the one-by-one launch's later passes (the emulator's grid: EPC_CL_MAX_BLOCKS = 3
+    blocks of 2 lanes per replica), the walk outside LDS (R W = 640) and at its boundary (512), populations 4 and 6, the
+    phase-major order on the step-by-step kernel"""
+    import test_zz_ep_cluster_gpu as tz
+    import test_zzz_ep_cluster_edges_gpu as t
+    with sim.patched():
+        t.run_multi_pass("cpu", oracle, G=131, cap_lanes=3 * 2)
+        t.run_walk_outside_lds("cpu", oracle, G=67, R=5, W=128)
+        t.run_walk_outside_lds("cpu", oracle, G=67, R=4, W=128)
+        for R in (4, 6):
+            assert tz.run_fused_vs_driver("cpu", 70, 6, 0.15, T=5, R=R, W=16, oracle=oracle, phase_major=R == 4) > 0
+            t.run_schedule("cpu", oracle, "same_key", G=67, R=R, T=5, phase_major=R == 6)
+        assert tz.run_fused_vs_driver("cpu", 70, 6, 0.15, T=5, oracle=oracle, phase_major=True, unbatched=True) > 0
+
+
+@pytest.mark.parametrize("name", ["same_key", "idle_then_hot", "silent_rows", "isolated_leader", "deaf_acceptor", "lost_replies"])
+def test_epaxos_cluster_tick_schedules_on_the_host(sim, oracle, name):
+    """tests/test_zzz_ep_cluster_edges_gpu.py's key and loss schedules, execution on and off, both orders"""
+    import test_zzz_ep_cluster_edges_gpu as t
+    with sim.patched():
+        for execute in (True, False):
+            for pm in (False, True):
+                t.run_schedule("cpu", oracle, name, G=67, W=8, T=6 if name != "idle_then_hot" else None, execute=execute, phase_major=pm)
+
+
 def test_spread_epaxos_exchange_on_the_host(sim, oracle):
     """layout L2 of the EPaxos cluster with every rank in this process (tests/test_spread_ep.py): one all-to-all per
     exchange, both schedules -- against the co-located closed loop, every tick and the final state"""

@@ -39,19 +39,35 @@ def test_device_cluster_tick_matches_the_oracle_cluster(cuda, oracle, G, K, loss
     assert fast > 0 and (slow > 0 or loss == 0.0)
 
 
-def run_fused_vs_driver(dev, G, K, loss, T=7, execute=True, seed=5, R=5, W=32, oracle=None, phase_major=False):
+def run_fused_vs_driver(dev, G, K, loss, T=7, execute=True, seed=5, R=5, W=32, oracle=None, phase_major=False, schedule=None,
+                        prelude=None, unbatched=False, info=None):
     """`smr_ep_cluster_tick` -- one C call per tick: as ONE launch (the default) and as the handler kernels back to back -- against
     the handler-by-handler driver on a third set of replicas and, with `oracle`, against five oracles wired into the same
     loop (tests/ep_cluster.py): every leader's outputs every tick, every replica's final state.  phase_major: all four in the
-    phase-by-phase order of the leaders' steps (smr_ep_cluster_set_mode bit 1)."""
+    phase-by-phase order of the leaders' steps (smr_ep_cluster_set_mode bit 1).
+    schedule(rng, t) -> (keys [R][G], drop or None): the tick's proposals and losses (default: Zipf keys, `loss`).
+    prelude(sets, orcs): runs before the clusters exist, on the three sets of replicas [a, a1, b] and the oracles (None without
+    `oracle`) -- e.g. ticks through ep_cluster.tick with a `via` (wide_seq_prelude).
+    unbatched: the one-launch cluster with SMR_EP_PM_UNBATCHED set at its creation (the step-by-step kernel in the phase-major order).
+    info (a dict): filled with "stats" (the one-launch cluster's batch_stats delta of every tick) and "dumps" (its replicas' final
+    dump())."""
+    import os
     import torch
     import ep_cluster as ec
     from summerset_amd import EPaxosReplicaGroup, ep_cluster
     mk = lambda: [EPaxosReplicaGroup(G, R, me=r, window=W, n_keys=K, execute=execute) for r in range(R)]
     a, a1, b = mk(), mk(), mk()
-    fused = ep_cluster.EPaxosCluster(a, phase_major=phase_major)
-    launches = ep_cluster.EPaxosCluster(a1, per_handler_launches=True, phase_major=phase_major)
     orcs = [oracle.EpOracle(G, R, me=r, W=W, n_keys=K, execute=execute) for r in range(R)] if oracle is not None else None
+    if prelude is not None:
+        prelude([a, a1, b], orcs)
+    if unbatched:
+        os.environ["SMR_EP_PM_UNBATCHED"] = "1"
+    try:
+        fused = ep_cluster.EPaxosCluster(a, phase_major=phase_major)
+    finally:
+        if unbatched:
+            del os.environ["SMR_EP_PM_UNBATCHED"]
+    launches = ep_cluster.EPaxosCluster(a1, per_handler_launches=True, phase_major=phase_major)
     from summerset_amd import SummersetError
     for wrong in (a[::-1], a[:2], a[:4] + [b[0]]):               # replica r must sit at index r, all of them, of one population
         with pytest.raises(SummersetError):
@@ -63,12 +79,18 @@ def run_fused_vs_driver(dev, G, K, loss, T=7, execute=True, seed=5, R=5, W=32, o
     dv = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
     slow = 0
     outs = fused.new_outputs(dev)                                # the caller's arrays, reused every tick
+    stats = [fused.batch_stats()] if info is not None else None
     for t in range(T):
-        keys = ec.zipf_keys(rng, R, G, K)
-        drop = {(s, q): rng.random(G) < loss for s in range(R) for q in range(R) if s != q and rng.random() < 0.7} if loss else None
+        if schedule is None:
+            keys = ec.zipf_keys(rng, R, G, K)
+            drop = {(s, q): rng.random(G) < loss for s in range(R) for q in range(R) if s != q and rng.random() < 0.7} if loss else None
+        else:
+            keys, drop = schedule(rng, t)
         kd = [dv(keys[r]) for r in range(R)]
         dd = None if drop is None else {k: dv(v) for k, v in drop.items()}
         oa = fused.tick(kd, dd, out=outs)
+        if info is not None:
+            stats.append(fused.batch_stats())
         oa1 = launches.tick(kd, dd)
         ob = ep_cluster.tick(b, kd, dd, always_accept_round=True, phase_major=phase_major)
         oo = ec.tick(orcs, keys, drop, phase_major=phase_major) if orcs is not None else None
@@ -100,6 +122,9 @@ def run_fused_vs_driver(dev, G, K, loss, T=7, execute=True, seed=5, R=5, W=32, o
                 z, x = orcs[r].exec_dump(), a[r].exec_dump()
                 for n in z:
                     assert np.array_equal(x[n], z[n]), (r, "exec", n, "oracle")
+    if info is not None:
+        info["stats"] = [{k: stats[t + 1][k] - stats[t][k] for k in stats[t]} for t in range(T)]
+        info["dumps"] = [a[r].dump() for r in range(R)]
     fused.close()
     launches.close()
     return slow
