@@ -320,6 +320,18 @@ def test_rspaxos_payload_store_on_the_host(sim, oracle):
         t.test_argument_errors("cpu")
 
 
+def test_rspaxos_payload_one_call_on_the_host(sim, oracle, monkeypatch):
+    """tests/test_zzz_rsp_payload_one_call_gpu.py on the emulator: the reordered schedule against the oracles, then the one-call
+    byte path (put_follow_all, deliver on and off) through leader changes at groups that straddle the put launch's blocks
+    (L = 4113, all three arms) and groups wider than a block (L = 12 300, arms B and C) -- at 8 groups and 21 ticks (the longest
+    log still > 2W), a seed under which every coverage condition holds"""
+    import test_zzz_rsp_payload_one_call_gpu as t
+    with sim.patched():
+        t.run_schedule_matches_oracle("cpu", oracle, 40, 8, 1, 0.1, 27, seed=41)
+        t.run_three_arms("cpu", oracle, monkeypatch, 8, 8, 1, 0.1, 4113, 21, seed=15)
+        t.run_three_arms("cpu", oracle, monkeypatch, 8, 8, 1, 0.1, 12300, 21, seed=15, arms=("B", "C"))
+
+
 def test_accept_reply_records_on_the_host(sim, oracle):
     """the AcceptReply record <-> ack matrix kernels (smr_mp_collect_acks / smr_mp_deliver_acks) under the emulator"""
     import test_mp_gpu as t

@@ -10,13 +10,18 @@ sys.path.insert(0, os.path.dirname(__file__))
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("staging,many", [(False, False), (True, False), (False, True), (False, "one_call")],
-                         ids=["colocated", "messages", "follow_many", "put_follow_all"])
-def test_craft_payload_loop(cuda, oracle, staging, many):
+@pytest.mark.parametrize("staging,many", [(False, False), (True, False), (False, True), (False, "one_call"), (False, "one_call_off")],
+                         ids=["colocated", "messages", "follow_many", "put_follow_all", "put_follow_all_deliver_off"])
+def test_craft_payload_loop(cuda, oracle, monkeypatch, staging, many):
     import craft_payload_loop as cl
-    lp = cl.run(cuda, oracle, G=96, W=32, L=131, staging=staging, many=many)
+    monkeypatch.delenv("SMR_PS_DELIVER", raising=False)
+    if many == "one_call_off":                                     # the followers' shards through the byte kernel
+        monkeypatch.setenv("SMR_PS_DELIVER", "0")
+    lp = cl.run(cuda, oracle, G=96, W=32, L=131, staging=staging, many="one_call" if many == "one_call_off" else many)
     if many == "one_call":
         assert 0 < sum(s.delivered() for s in lp.stores) < sum(s.counters()["copied"] for s in lp.stores)
+    if many == "one_call_off":
+        assert [s.delivered() for s in lp.stores] == [0] * lp.R and sum(s.counters()["copied"] for s in lp.stores) > 0
 
 
 def test_craft_payload_loop_4k_batches(cuda, oracle):
@@ -46,6 +51,7 @@ def test_one_call_byte_path_is_the_three_calls(cuda):
     follow_many in four launches) against the three calls, stores compared byte for byte every tick"""
     import test_craft_payload as t
     t.run_craft_one_call_is_the_three_calls(cuda, G=1000, W=8, L=200, T=14)
+    t.run_craft_one_call_is_the_three_calls(cuda, G=20, W=8, L=12300, T=14)      # a group wider than the put launch's block
     t.run_rspaxos_one_call_is_the_three_calls(cuda, G=1000, W=8, L=333, T=14)
 
 
