@@ -1380,6 +1380,27 @@ int smr_wire_ingest_rsp_accept_replies(const uint8_t *buf_dev, uint64_t buf_len,
 int smr_raft_leader_handle_wire_replies(smr_raft_leader *l, const uint8_t *buf_dev, uint64_t buf_len, const uint64_t *conn_off_dev,
                                         const uint8_t *conn_len_dev, uint32_t n_conn, const uint32_t *order_dev, smr_wire_other *others_dev,
                                         uint64_t other_cap, uint64_t *counts_dev, uint64_t *consumed_dev, int32_t *status_dev, void *stream);
+/* The EPaxos command leader's receive side of a tick in ONE launch -- smr_wire_ingest_ep_pre_accept_replies as the prologue of
+ * smr_ep_handle_pre_accept_replies (safetcp.rs:46,127-132 framing, epaxos/mod.rs:306-377 PreAcceptReply, epaxos/messages.rs:96-270
+ * the handler): no ballot / seq / flags [R][G] and deps [R][R][G] arrays in between, nothing to clear in front (the two calls: two
+ * memsets, two launches, 37 bytes per connection at population 5 written and read back).  The connections come DENSE:
+ * n_conn == n_groups * (population - 1), connection g * (population - 1) + k is group g's k-th peer, ids ascending with my own left
+ * out; their bytes as in smr_wire_ingest_ep_pre_accept_replies (conn_off_dev [n_conn + 1], or starts + conn_len_dev: the layout
+ * smr_wire_emit_ep_pre_accept_replies leaves, stride SMR_WIRE_EMIT_EP_STRIDE).  The reply taken (the first complete one for
+ * (me, col_dev[group]) with `population` dependencies below SMR_EP_NONE), frames located (others_dev, counts_dev), consumed_dev /
+ * status_dev: exactly that call's.  What the leader then does with the replies (order_dev: delivery order per group, NULL = peer
+ * order; exploded_dev; decision_dev / d_seq_dev / d_deps_dev, the replica's counters): exactly smr_ep_handle_pre_accept_replies',
+ * and with smr_ep_cfg.execute the execution pass follows on the same stream as it does there.  Instances of MY row only: the
+ * replies to an instance a replica leads outside its row under explicit prepare (row_dev, smr_ep_handle_pre_accept_replies_at)
+ * stay with the two calls.  counts_dev[4] is WRITTEN by the call's last block (no need to clear it).  The call's counter scratch
+ * is the replica's; its words only ever count up and are never reset, so a call leaves nothing behind that the next one would
+ * have to find cleared (an error return zeroes it).  One stream at a time per replica: two of these calls on the same replica
+ * must not overlap -- they would get each other's counts (the call after them is exact again). */
+int smr_ep_leader_handle_wire_pre_accept_replies(smr_ep_replica *e, const uint8_t *buf_dev, uint64_t buf_len, const uint64_t *conn_off_dev,
+                                                 const uint8_t *conn_len_dev, uint32_t n_conn, const uint32_t *col_dev, const uint32_t *order_dev,
+                                                 const uint8_t *exploded_dev, uint8_t *decision_dev, uint64_t *d_seq_dev, uint32_t *d_deps_dev,
+                                                 smr_wire_other *others_dev, uint64_t other_cap, uint64_t *counts_dev, uint64_t *consumed_dev,
+                                                 int32_t *status_dev, void *stream);
 
 /* ---- reply frames written on the device (round 3; csrc/wire_emit.hip): the send half.  A follower's handler leaves its
  * replies as device arrays; these calls write, for every reply, the frame TcpTransport would send -- `[u64 BE length]

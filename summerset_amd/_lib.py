@@ -293,6 +293,7 @@ SYMBOLS = [
     ("smr_ep_handle_pre_accept_replies", _i, [_vp] + [_vp] * 11),
     ("smr_ep_handle_accept_replies", _i, [_vp] + [_vp] * 6),
     ("smr_ep_handle_pre_accept_replies_at", _i, [_vp] + [_vp] * 12),
+    ("smr_ep_leader_handle_wire_pre_accept_replies", _i, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("smr_ep_handle_accept_replies_at", _i, [_vp] + [_vp] * 7),
     ("smr_ep_heartbeat_timeout", _i, [_vp] + [_vp] * 6),
     ("smr_ep_handle_exp_prepare", _i, [_vp, C.POINTER(EpExpPrepare), C.POINTER(EpExpPrepareReply), _vp]),

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "smr_common.h"
+#include "wire_rd.h"
 
 namespace smr {
 
@@ -1389,6 +1390,218 @@ __global__ __launch_bounds__(256) void ep_pre_accept_replies_kernel(const EpView
     L.flush();
 }
 
+// ---- the command leader's receive side of a tick in ONE launch ---------------------------------------------------------------------
+// smr_wire_ingest_ep_pre_accept_replies parses the acceptors' connections into ballot / seq / flags [R][G] and deps [R][R][G]
+// (two memsets in front: the flag plane, the counters) and smr_ep_handle_pre_accept_replies reads them back: four stream operations
+// and, at R = 5, 37 bytes per connection out and in again for frames of 25 to 45 bytes.  Here the parse is the prologue of the
+// handler, as raft_wire_replies_kernel's is of the Raft leader's.  The connections come DENSE: connection c = g * (R - 1) + k is
+// group g's k-th peer (ids ascending, my own left out), so a block's EW_BLOCK / (R - 1) groups have all their connections in the
+// block.  Every lane walks its connection out of the block's LDS copy of the buffer span (wire_rd.h; the rules are the WR_EPAXOS arm
+// of wire_ingest_replies_kernel: same reply taken, same frames located, same `consumed` / `status`) and leaves the reply it takes
+// in LDS, [peer slot][group of the block]: ballot, seq, R dependencies, a flag.  A reply that did not come is a flag of zero; no
+// array in between, nothing to zero.  Behind one barrier the block's first lanes run ep_pa_replies_lane_rd on their group
+// (messages.rs:96-270) with an RD that reads those words.
+// Own row only: the instances a replica leads outside its row under explicit prepare (row_dev, the _at entries) stay with the two calls.
+//
+// 512 lanes per block: stage 20 KB + located frames 6 KB + reply words 37 B (NR = 5) / 49 B (NR = 8) per lane = 45.5 / 51.6 KB of
+// LDS, three blocks per CU (raft_wire_replies_kernel's 1024 lanes and 77 KB leave one).
+//
+// The call's four counters: summed per block in LDS, added into a scratch of the replica's (16 shards of the three plain
+// counters; the located frames' places come from one word), handed out by the block whose arrival is the grid's last (arrival
+// tickets in two levels of <= 32 arrivals each, as raft_wire_replies_kernel's: a same-address atomic is ~10-25 ns and there
+// are 512 blocks).  NOTHING in that scratch is ever reset, so no call can leave it dirty for the next one: every word only
+// counts up.  A ticket word receives the same number of arrivals in every call of a replica (the grid is the replica's), so
+// "last" is "the count after mine is a multiple of that number"; the counters are cumulative and the last block hands out the
+// difference to the totals the previous call's last block left in snap[] (written with atomicMax: cumulative totals only grow).
+// A launch that never ran added nothing; two calls that overlapped against the contract (one stream at a time per replica)
+// get each other's counts, and the call after them is exact again.  The entry point zeroes the scratch on its error returns.
+// "My adds before my ticket, the last block reads everyone's adds" is ordered by fences: an agent-scope release (__threadfence)
+// in front of every ticket, an acquire behind every winning one.
+struct EpWire {
+    const uint8_t *buf; uint64_t buf_len;
+    const uint64_t *conn_off; const uint8_t *conn_len; uint32_t n_conn;
+    const uint32_t *col, *order; const uint8_t *exploded;
+    uint8_t *decision; uint64_t *d_seq; uint32_t *d_deps;
+    smr_wire_other *others; uint64_t other_cap;
+    uint64_t *counts, *consumed; int32_t *status;
+    unsigned long long *acc;                     // the replica's, cumulative: [0] top ticket, [1] located frames, [2 .. 5] snap[4]: the four counters'
+};                                               //  totals as the last call left them, [8 ..) the shards, then 64 level-1 tickets
+#ifndef EW_BLOCK_N
+#define EW_BLOCK_N 512           // (lanes per block; 1024 would need 91 KB of LDS at NR = 5: one block per CU, what bounds the Raft kernel)
+#endif
+constexpr uint32_t EW_BLOCK = EW_BLOCK_N, EW_STAGE = EW_BLOCK * 40, EW_LOC = EW_BLOCK / 2;
+constexpr uint32_t EW_SHARDS = 16, EW_TICK1 = 8 + EW_SHARDS * 4, EW_ACC_WORDS = EW_TICK1 + 64;
+__device__ __forceinline__ unsigned long long ew_read(unsigned long long *w) { return atomicAdd(w, 0ull); }   // (at L2, where the atomics are)
+
+// the replies a block parsed, in its LDS: peer p's reply to group `gi` of the block lies at [slot of p][gi]
+template <int NR>
+struct EpRepliesInWireLds {
+    const uint64_t *bal, *seq; const uint32_t (*dep)[EW_BLOCK]; const uint8_t *fl;
+    uint32_t me, R, gpb, gi;
+    __device__ __forceinline__ void get(uint32_t p, uint32_t &f, uint64_t &rb, uint64_t &rs, uint32_t (&rd)[NR]) const {
+        const uint32_t i = (p - (p > me ? 1u : 0u)) * gpb + gi;             // (p != me: the caller skips the leader itself)
+        f = fl[i];
+        rb = f ? bal[i] : 0ull; rs = f ? seq[i] : 0ull;
+#pragma unroll
+        for (int k = 0; k < NR; k++) rd[k] = (f && (uint32_t)k < R) ? dep[k][i] : EP_NONE;
+    }
+};
+
+template <int NR>
+__global__ __launch_bounds__(EW_BLOCK) void ep_wire_pre_accept_replies_kernel(const EpView v, const EpWire A) {
+    __shared__ uint32_t stage[EW_STAGE / 4 + 4];
+    __shared__ smr_wire_other loc[EW_LOC];
+    __shared__ uint32_t blk[4];
+    __shared__ unsigned long long loc_base;
+    __shared__ uint64_t sh_bal[EW_BLOCK], sh_seq[EW_BLOCK];
+    __shared__ uint32_t sh_dep[NR][EW_BLOCK];
+    __shared__ uint8_t sh_fl[EW_BLOCK];
+    if (threadIdx.x < 4) blk[threadIdx.x] = 0;
+    const unsigned long long loc_before = A.acc[3];                           // snap[1]: the located frames of all calls before this one
+    const uint32_t F = v.R - 1u, GPB = EW_BLOCK / F;                          // peers per group, groups per block
+    const uint32_t g0 = blockIdx.x * GPB, c0 = g0 * F;
+    const uint32_t n_here = (A.n_conn - c0) < GPB * F ? (A.n_conn - c0) : GPB * F;
+    const bool live = threadIdx.x < n_here;
+    const uint32_t c = c0 + threadIdx.x;
+    const uint64_t start = live ? A.conn_off[c] : 0, end = !live ? 0 : A.conn_len ? start + A.conn_len[c] : A.conn_off[c + 1];
+    // my block's span of the buffer -> LDS: from its first connection's start (16-byte aligned down) as far as the stage goes
+    const uint32_t c1 = c0 + n_here;
+    const uint64_t s0 = A.conn_off[c0] & ~15ull, s1 = A.conn_len ? A.conn_off[c1 - 1] + A.conn_len[c1 - 1] : A.conn_off[c1];
+    uint64_t slo = 0, shi = 0;
+    if (s0 < s1 && s1 <= A.buf_len) {
+        slo = s0; shi = s1 - s0 <= EW_STAGE ? s1 : s0 + EW_STAGE;
+        const uint32_t n16 = (uint32_t)((shi - slo + 15) / 16);
+        for (uint32_t i = threadIdx.x; i <= n16; i += EW_BLOCK) {                  // (one chunk more: the dwords a read at the last bytes reaches into)
+            const uint64_t off = slo + 16ull * i;
+            uint32_t w[4] = {0, 0, 0, 0};
+            if (off + 16 <= A.buf_len) {
+                const wr_u32x4 x = *(const wr_u32x4 *)(A.buf + off);
+                w[0] = x.x; w[1] = x.y; w[2] = x.z; w[3] = x.w;
+            } else {
+                for (uint32_t b = 0; b < 16 && off + b < A.buf_len; b++) w[b >> 2] |= (uint32_t)A.buf[off + b] << (8 * (b & 3));
+            }
+            if (4 * i + 3 < EW_STAGE / 4 + 4) { stage[4 * i] = w[0]; stage[4 * i + 1] = w[1]; stage[4 * i + 2] = w[2]; stage[4 * i + 3] = w[3]; }
+        }
+    }
+    sh_fl[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t my_gi = threadIdx.x / F, my_k = threadIdx.x - my_gi * F;
+    const uint32_t my_w = my_k * GPB + my_gi;                                   // where my connection's reply goes: [peer slot][group of the block]
+    const uint32_t my_col = live ? A.col[g0 + my_gi] : 0u;
+    uint64_t pos = start;
+    int st = 0;
+    bool have = false, deferred = false;
+    if (live && (end < start || end > A.buf_len)) st = 1;
+    while (live && st == 0) {
+        const uint64_t avail = end - pos;
+        if (avail < 8) break;                                                       // length not complete yet
+        GlRd r{A.buf, pos, pos + 8, A.buf_len, true, stage, slo, shi};
+        const uint64_t plen = __builtin_bswap64(r.peek64());
+        if (plen > 1000000000000ull) { st = 1; break; }                             // safetcp.rs:56-66
+        if (avail - 8 < plen) break;                                                // frame not complete yet
+        r.n = pos + 8; r.end = pos + 8 + plen;
+        uint32_t kind = SMR_WIRE_OTHER;
+        bool mine = false;
+        const uint64_t outer = r.varint();
+        if (outer == 2) kind = SMR_WIRE_LEAVE;                                      // PeerMessage::Leave
+        else if (outer == 0) {                                                      // PeerMessage::Msg { msg }
+            const uint64_t var = r.varint();
+            if (!r.ok) { st = 1; break; }
+            kind = (uint32_t)(var <= SMR_WIRE_EP_COMMIT_NOTICE ? var : SMR_WIRE_OTHER);   // (ExpPrepare & co, Heartbeat: located)
+            if (var == SMR_WIRE_EP_PRE_ACCEPT_REPLY) {
+                uint8_t row; uint64_t col, ballot, seq, n; bool fits;
+                // (the dependencies go straight to my LDS words while no reply is taken yet -- they count only under the flag,
+                //  and a reply that turns out not to be mine leaves the flag as it is; behind a taken reply they go nowhere)
+                const bool keep = !have;
+                if (!wr_ep_pre_accept_reply(r, row, col, ballot, seq, n, fits, [&](uint32_t q, uint32_t x) {
+                        if (keep && q < (uint32_t)NR && q < v.R) sh_dep[q][my_w] = x;
+                    })) { st = 1; break; }
+                mine = row == v.me && col == (uint64_t)my_col && n == v.R && fits;
+                if (mine) {
+                    if (have) { deferred = true; break; }                           // the next call's
+                    sh_bal[my_w] = ballot; sh_seq[my_w] = seq; sh_fl[my_w] = 1;
+                    have = true;
+                }
+            }
+        }
+        if (!r.ok) { st = 1; break; }                                               // (the enum tags did not parse)
+        if (!mine) {                                                                // located, not validated
+            smr_wire_other o; o.conn = c; o.kind = kind; o.off = pos; o.len = 8 + plen;
+            const uint32_t at = atomicAdd(&blk[1], 1u);
+            if (at < EW_LOC) loc[at] = o;
+            else {                                                                  // (more than the block keeps: straight to the call's list)
+                const unsigned long long far = atomicAdd(&A.acc[1], 1ull) - loc_before;
+                if (far < A.other_cap) A.others[far] = o;
+            }
+        }
+        pos += 8 + plen;
+    }
+    if (live) {
+        A.consumed[c] = st ? 0 : pos - start;                                       // (a malformed connection: the host looks at all of it)
+        A.status[c] = st;                                                           // (a reply taken in front of the malformed frame stays
+    }                                                                               //  taken, as its flag stays set after the two calls)
+    const unsigned long long m0 = __ballot(have && st == 0), m2 = __ballot(st != 0), m3 = __ballot(deferred);
+    if (threadIdx.x % 64 == 0) {
+        if (m0) atomicAdd(&blk[0], (uint32_t)__popcll(m0));
+        if (m2) atomicAdd(&blk[2], (uint32_t)__popcll(m2));
+        if (m3) atomicAdd(&blk[3], (uint32_t)__popcll(m3));
+    }
+    __syncthreads();
+    // (the located frames' place in the call's list: asked for NOW, used behind the handler -- the word is one for all blocks)
+    const uint32_t n_kept = blk[1] < EW_LOC ? blk[1] : EW_LOC;
+    unsigned long long my_base = 0;
+    if (threadIdx.x == 0 && n_kept) my_base = atomicAdd(&A.acc[1], (unsigned long long)n_kept) - loc_before;
+    // ---- the handler: one lane per group of the block, its peers' replies out of LDS ----
+    const uint32_t g = g0 + threadIdx.x;
+    const bool leads = threadIdx.x < GPB && g < v.G;
+    EpLaneT<NR> L(v, leads ? g : 0);
+    if (leads) {
+        const EpRepliesInWireLds<NR> rdr{sh_bal, sh_seq, sh_dep, sh_fl, v.me, v.R, GPB, threadIdx.x};
+        uint8_t dec; uint64_t dseq; uint32_t dd[NR];
+        ep_pa_replies_lane_rd<NR, false>(L, v.me, A.col[g], A.order ? A.order[g] : SMR_CTL_IDENTITY, A.exploded ? A.exploded[g] : 0u, rdr, dec, dseq, dd);
+        A.decision[g] = dec; A.d_seq[g] = dec ? dseq : 0ull;
+#pragma unroll
+        for (int k = 0; k < NR; k++) if ((uint32_t)k < v.R) A.d_deps[(size_t)k * v.G + g] = dec ? dd[k] : EP_NONE;
+    }
+    if ((threadIdx.x & ~63u) < GPB) L.flush();                                      // (the wavefronts that hold a handler lane)
+    // ---- the call's counters: this block's share, the located frames' place, and -- the last block -- the totals ----
+    if (threadIdx.x == 0) {
+        unsigned long long *const shard = A.acc + 8 + (blockIdx.x % EW_SHARDS) * 4u;
+        if (blk[0]) atomicAdd(&shard[0], (unsigned long long)blk[0]);
+        if (blk[2]) atomicAdd(&shard[2], (unsigned long long)blk[2]);
+        if (blk[3]) atomicAdd(&shard[3], (unsigned long long)blk[3]);
+        loc_base = my_base;
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < n_kept; j += EW_BLOCK)
+        if (loc_base + j < A.other_cap) A.others[loc_base + j] = loc[j];
+    if (threadIdx.x == 0) {
+        // arrivals: my level-1 ticket (blocks 32 k .. 32 k + 31), its last arrival goes on to the top ticket; the last of all hands the totals out
+        const uint32_t n1 = (gridDim.x + 31u) / 32u, t1 = blockIdx.x / 32u;
+        const uint32_t mine = t1 + 1u < n1 ? 32u : gridDim.x - 32u * (n1 - 1u);
+        bool last = false;
+        __threadfence();                                                            // release: my block's adds are in front of my ticket
+        if (n1 > 64u) last = (atomicAdd(&A.acc[0], 1ull) + 1ull) % gridDim.x == 0ull;   // (more level-1 groups than tickets: one level)
+        else if ((atomicAdd(&A.acc[EW_TICK1 + t1], 1ull) + 1ull) % mine == 0ull) {
+            __threadfence();                                                        // acquire my group's, release towards the top ticket
+            last = (atomicAdd(&A.acc[0], 1ull) + 1ull) % n1 == 0ull;
+        }
+        if (last) {
+            __threadfence();                                                        // acquire: every other block's adds are behind its ticket
+            unsigned long long tot[4] = {0ull, 0ull, 0ull, 0ull};
+            for (uint32_t sh = 0; sh < EW_SHARDS; sh++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) if (q != 1) tot[q] += ew_read(&A.acc[8 + sh * 4 + q]);
+            tot[1] = ew_read(&A.acc[1]);
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                A.counts[q] = tot[q] - ew_read(&A.acc[2 + q]);
+                atomicMax(&A.acc[2 + q], tot[q]);
+            }
+        }
+    }
+}
+
 // the AcceptReplies to the instance (row, c) I lead: flags / ballot rows by peer (stride G), peers in ctl order, one
 // handle_msg_accept_reply each (messages.rs:348-436); true = the instance went from Accepting to Committed here
 template <int NR, bool C>
@@ -1593,6 +1806,7 @@ struct smr_ep_replica {
     Arena arena;
     bool skip_exec = false;      // smr_ep_cluster_tick around the handlers that cannot move a commit bar (see there)
     smr_ep_replica **seat = nullptr;   // my seat in the cluster whose per-key table I use (smr_ep_cluster_create): cleared when I go first
+    unsigned long long *wire_acc = nullptr;   // smr_ep_leader_handle_wire_pre_accept_replies: its counters and arrival tickets, cumulative over the calls
 };
 
 namespace smr {
@@ -2670,7 +2884,10 @@ int smr_ep_replica_create(const smr_ep_cfg *cfg, smr_ep_replica **out) {
         err = hipGetLastError();
         if (err == hipSuccess) err = hipDeviceSynchronize();
     }
+    if (err == hipSuccess) err = hipMalloc((void **)&e->wire_acc, EW_ACC_WORDS * 8);
+    if (err == hipSuccess) err = hipMemset(e->wire_acc, 0, EW_ACC_WORDS * 8);
     if (err != hipSuccess) {
+        if (e->wire_acc) (void)hipFree(e->wire_acc);
         (void)hipFree(e->arena.base); delete e;
         return fail(SMR_ERR_DEVICE, std::string("epaxos: init: ") + hipGetErrorString(err));
     }
@@ -2682,6 +2899,7 @@ void smr_ep_replica_destroy(smr_ep_replica *e) {
     if (!e) return;
     if (e->seat) *e->seat = nullptr;                             // (the cluster then has nothing of mine to hand back)
     if (e->arena.base) (void)hipFree(e->arena.base);
+    if (e->wire_acc) (void)hipFree(e->wire_acc);
     delete e;
 }
 
@@ -2759,6 +2977,34 @@ int smr_ep_handle_pre_accept_replies(smr_ep_replica *e, const uint32_t *col_dev,
                                      uint64_t *d_seq_dev, uint32_t *d_deps_dev, void *stream) {
     return smr_ep_handle_pre_accept_replies_at(e, nullptr, col_dev, ballot_dev, seq_dev, deps_dev, flags_dev, order_dev, exploded_dev,
                                                decision_dev, d_seq_dev, d_deps_dev, stream);
+}
+
+int smr_ep_leader_handle_wire_pre_accept_replies(smr_ep_replica *e, const uint8_t *buf_dev, uint64_t buf_len, const uint64_t *conn_off_dev,
+                                                 const uint8_t *conn_len_dev, uint32_t n_conn, const uint32_t *col_dev, const uint32_t *order_dev,
+                                                 const uint8_t *exploded_dev, uint8_t *decision_dev, uint64_t *d_seq_dev, uint32_t *d_deps_dev,
+                                                 smr_wire_other *others_dev, uint64_t other_cap, uint64_t *counts_dev, uint64_t *consumed_dev,
+                                                 int32_t *status_dev, void *stream) {
+    if (!e || !conn_off_dev || !col_dev || !decision_dev || !d_seq_dev || !d_deps_dev || !counts_dev || !consumed_dev || !status_dev ||
+        (buf_len && !buf_dev) || (other_cap && !others_dev))
+        return fail(SMR_ERR_ARG, "epaxos wire replies: null argument");
+    if ((uintptr_t)buf_dev & 15) return fail(SMR_ERR_ARG, "epaxos wire replies: the byte buffer must be 16-byte aligned");
+    const uint32_t F = e->v.R - 1u;
+    if (n_conn != e->v.G * F)
+        return fail(SMR_ERR_ARG, "epaxos wire replies: the connections come dense -- n_groups * (population - 1) of them, connection g * (population - 1) + k "
+                                 "= group g's k-th peer in ascending id");
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t GPB = EW_BLOCK / F;
+    const EpWire A{buf_dev, buf_len, conn_off_dev, conn_len_dev, n_conn, col_dev, order_dev, exploded_dev, decision_dev, d_seq_dev, d_deps_dev,
+                   others_dev, other_cap, counts_dev, consumed_dev, status_dev, e->wire_acc};
+    const dim3 grid((e->v.G + GPB - 1) / GPB), block(EW_BLOCK);
+    if (e->v.R <= 5) hipLaunchKernelGGL(ep_wire_pre_accept_replies_kernel<5>, grid, block, 0, st, e->v, A);
+    else hipLaunchKernelGGL(ep_wire_pre_accept_replies_kernel<EMAXR>, grid, block, 0, st, e->v, A);
+    int rc = SMR_OK;
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) rc = fail(SMR_ERR_DEVICE, std::string("epaxos wire replies: ") + hipGetErrorString(err));
+    else rc = ep_execute(e, stream);
+    if (rc != SMR_OK) (void)hipMemsetAsync(e->wire_acc, 0, EW_ACC_WORDS * 8, st);   // (all zero is a state every call can start from)
+    return rc;
 }
 
 int smr_ep_handle_accept_replies_at(smr_ep_replica *e, const uint8_t *row_dev, const uint32_t *col_dev, const uint64_t *ballot_dev,

@@ -64,5 +64,25 @@ __device__ __forceinline__ bool wr_raft_append_reply(GlRd &r, uint64_t &term, ui
     return r.ok && r.n == r.end;
 }
 
+// one PreAcceptReply frame's payload behind the PeerMessage / PeerMsg tags (epaxos/mod.rs:306-377, variant 1):
+// { slot: SlotIdx(row u8, col), ballot, seq, deps: DepSet = Vec<Option<usize>> }, read rule for rule as the WR_EPAXOS arm of
+// wire_ingest_replies_kernel reads it; false = malformed (n > 64, an Option tag other than 0 / 1, a reply that does not end
+// where its length says).  put(q, dep) is handed dependency q (None = SMR_EP_NONE) in order; fits = every Some below SMR_EP_NONE.
+template <typename PUT>
+__device__ __forceinline__ bool wr_ep_pre_accept_reply(GlRd &r, uint8_t &row, uint64_t &col, uint64_t &ballot, uint64_t &seq, uint64_t &n, bool &fits,
+                                                       const PUT &put) {
+    row = r.byte();
+    col = r.varint(); ballot = r.varint(); seq = r.varint(); n = r.varint();
+    fits = true;
+    if (!r.ok || n > 64) return false;
+    for (uint64_t q = 0; q < n && r.ok; q++) {
+        const uint8_t some = r.byte();
+        uint64_t x = SMR_EP_NONE;
+        if (some == 1) { x = r.varint(); fits = fits && x < SMR_EP_NONE; } else if (some != 0) r.ok = false;
+        put((uint32_t)q, (uint32_t)x);
+    }
+    return r.ok && r.n == r.end;
+}
+
 }  // namespace smr
 #endif

@@ -555,6 +555,30 @@ class ReplyIngest:
                                                             p(self.counts), p(self.consumed), p(self.status), _lib.stream_ptr(stream)))
         return dict(ballot=self.u64a, seq=self.u64b, deps=self.deps, flags=self.flags)
 
+    def ep_pre_accept_into(self, replica, buf, conn_off, col, order=None, exploded=None, stream=None, conn_len=None):
+        """`ep_pre_accept(...)` + `replica.handle_msg_pre_accept_reply(...)` as ONE launch
+        (`smr_ep_leader_handle_wire_pre_accept_replies`): the parse is the prologue of the command leader's reply handler, no
+        [R, G] / [R, R, G] arrays in between.  The connections come dense -- n_groups * (population - 1) of them, connection
+        g * (population - 1) + k = group g's k-th peer in ascending id, the replica's own left out.  The instances are the
+        replica's own row's (`row=` stays with the two calls).  Returns dict(decision, seq, deps) as
+        `EPaxosReplicaGroup.handle_msg_pre_accept_reply` does; `results()` as after `ep_pre_accept(...)`."""
+        import torch
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        G, R, dev = self.G, self.R, col.device
+        assert replica.G == G and replica.R == R
+        assert self.n_conn == G * (R - 1) and conn_off.numel() >= self.n_conn + (conn_len is None) and conn_off.element_size() == 8
+        assert conn_len is None or (conn_len.numel() == self.n_conn and conn_len.element_size() == 1)
+        assert col.numel() == G and col.element_size() == 4
+        assert order is None or (order.numel() == G and order.element_size() == 4)
+        assert exploded is None or (exploded.numel() == G and exploded.element_size() == 1)
+        r = dict(decision=torch.zeros(G, dtype=torch.uint8, device=dev), seq=torch.zeros(G, dtype=torch.int64, device=dev),
+                 deps=torch.zeros((R, G), dtype=torch.int32, device=dev))
+        check(self._L.smr_ep_leader_handle_wire_pre_accept_replies(replica._h, p(buf) if buf.numel() else None, buf.numel(), p(conn_off), p(conn_len),
+                                                                   self.n_conn, p(col), p(order), p(exploded), p(r["decision"]), p(r["seq"]),
+                                                                   p(r["deps"]), p(self.others), self.other_cap, p(self.counts), p(self.consumed),
+                                                                   p(self.status), _lib.stream_ptr(stream)))
+        return r
+
     def rsp_accept(self, buf, conn_off, conn_group, conn_peer, stream=None, conn_len=None):
         """RSPaxos AcceptReplies -> dict(slot, ballot, flags) [R, G] for `RSPaxosReplicaGroup.accept_replies`"""
         p = lambda t: t.data_ptr()   # noqa: E731
