@@ -79,7 +79,9 @@ __device__ __forceinline__ void raft_append_body(const RaftView &v, uint32_t g, 
     // conflict reply's words and candidate terms a round of loads ahead, with the next tick's inputs, gained nothing --
     // 11.2 us, and 9.4 instead of 9.2 without conflicts, profiles/r5n: what a conflict costs is its divergent code, not
     // its round trips.)
-    bool simple = n > 0 && len + n - 1 - snap < v.W;
+    // (snap <= len: a follower takes last_snap from its leader's messages as it comes, messages.rs:211-213, and may lead later with
+    //  a log that ends below it; the loop's len - snap then wraps and rejects, and so must this)
+    bool simple = n > 0 && snap <= len && len + n - 1 - snap < v.W;
 #pragma unroll
     for (int p = 0; p < NR; p++)
         if ((uint32_t)p < v.R && (uint32_t)p != v.me) simple = simple && tn[p] >= 1 && tn[p] - 1 >= start && tn[p] <= len;

@@ -38,6 +38,12 @@ def append_entries_round(rng, dump, G, K, me, W):
                 leader_commit=leader_commit, last_snap=last_snap)
 
 
+def _shift(t, d):
+    """t + d for a uint64 term and a small signed step, never below 0, in uint64 all the way (terms reach 2^63 and beyond)"""
+    t = t.astype(np.uint64)
+    return np.where(d < 0, t - np.minimum(t, np.abs(d).astype(np.uint64)), t + np.maximum(d, 0).astype(np.uint64)).astype(np.uint64)
+
+
 def timeout_round(rng, dump, G, me):
     src = np.where(rng.random(G) < 0.5, dump["leader"], NO).astype(np.uint8)
     src[rng.random(G) < 0.1] = (me + 2) % 5                                  # a timer about somebody who is not my leader
@@ -50,9 +56,9 @@ def request_vote_round(rng, dump, G, me, W):
     flags = (rng.random(G) < 0.85).astype(np.uint8)
     cand = rng.integers(0, 5, G).astype(np.uint8)
     cand[cand == me] = (me + 1) % 5
-    m_term = (term.astype(np.int64) + rng.integers(-1, 3, G)).clip(0).astype(np.uint64)
+    m_term = _shift(term, rng.integers(-1, 3, G))
     my_last = et[(log_len - 1) % W, g]
-    last_term = (my_last.astype(np.int64) + rng.integers(-1, 2, G)).clip(0).astype(np.uint64)
+    last_term = _shift(my_last, rng.integers(-1, 2, G))
     last_slot = (log_len.astype(np.int64) - 1 + rng.integers(-2, 3, G)).clip(0).astype(np.uint32)
     return dict(flags=flags, candidate=cand, term=m_term, last_slot=last_slot, last_term=last_term)
 

@@ -67,6 +67,57 @@ def test_raft_one_launch_tick_on_the_host(sim, oracle):
         assert t.run_one_launch_tick("cpu", oracle, G=70, W=64, K=8, T=8, R=7) > 100            # ... and with seven replicas (the R > 5 instantiation)
 
 
+# ---- tests/test_zzz_raft_edges_gpu.py, small: the Raft engine at wide terms, past the ring, through outages ----
+@pytest.mark.parametrize("term0", [2**32 - 2, 2**63 - 2])
+def test_raft_wide_terms_on_the_host(sim, oracle, term0):
+    import test_zzz_raft_edges_gpu as t
+    with sim.patched():
+        t.run_wide_terms("cpu", oracle, term0, G=130)                                             # calls == one-launch tick == oracle
+        t.run_wide_terms("cpu", oracle, term0, G=130, arms=("calls", "many"), order="senders")    # ... == smr_raft_cluster_replicate
+        t.run_wide_terms_leader("cpu", oracle, term0, G=200)
+        t.run_wide_terms_follower("cpu", oracle, term0, G=300)
+        assert t.run_wide_terms_wire("cpu", oracle, term0, G=200, T=4) > 0
+
+
+def test_raft_closed_loop_past_the_ring_on_the_host(sim, oracle):
+    import test_zzz_raft_edges_gpu as t
+    with sim.patched():
+        t.run_past_the_ring("cpu", oracle, G=130, W=16)
+        t.run_past_the_ring("cpu", oracle, G=130, W=64, T=10, n_new_max=3, outages=False)
+
+
+def test_raft_closed_loop_outages_on_the_host(sim, oracle):
+    import test_zzz_raft_edges_gpu as t
+    with sim.patched():
+        t.run_outages("cpu", oracle, G=130)
+        t.run_outages("cpu", oracle, G=130, arms=("calls",), loss=0.1)
+        t.run_outages("cpu", oracle, G=130, arms=("calls",), loss=0.1, order="receivers")
+
+
+def test_raft_leader_deep_conflicts_on_the_host(sim, oracle):
+    import test_zzz_raft_edges_gpu as t
+    with sim.patched():
+        t.run_deep_conflicts("cpu", oracle, G=130)
+
+
+def test_raft_message_capacity_on_the_host(sim, oracle):
+    import test_zzz_raft_edges_gpu as t
+    with sim.patched():
+        t.run_small_messages("cpu", oracle, G=130, K=2)
+        t.run_empty_messages("cpu", oracle, G=130)
+        t.run_empty_messages("cpu", oracle, G=130, arms=("calls", "many"), order="senders")
+
+
+def test_raft_one_launch_shapes_on_the_host(sim, oracle):
+    import test_zzz_raft_edges_gpu as t
+    with sim.patched():
+        t.run_populations("cpu", oracle, 3, G=130)
+        t.run_populations("cpu", oracle, 8, G=65)
+        t.run_populations("cpu", oracle, 5, G=1)
+        t.run_one_launch_shapes("cpu", oracle, G=65)
+        assert t.run_cluster_tick_argument_errors("cpu")[0] == 9
+
+
 def test_craft_leader_kernels_on_the_host(sim, oracle):
     """the CRaft leader variant (a15): reply kernel with the fork's rules, heartbeat tick with the reply counters and the
     full-copy fall-back, mode switches, shard assignment + the RS kernels"""

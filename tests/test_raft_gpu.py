@@ -8,9 +8,16 @@ from summerset_amd import stream
 pytestmark = pytest.mark.gpu
 
 
+DEPTHS = (7, 8, 9, 15, 16, 17)          # around the ends of the back-off loop's first and second round of eight candidates
+
+
 def _replies(seed, t, G, R, log_len, curr_term, lag_max=3, drop_p=0.05, stale_p=0.005, conflict_p=0.005,
-             higher_p=0.0):
-    """per (peer, group): end_slot = leader_last - lag, some dropped / stale-term / conflict replies"""
+             higher_p=0.0, stale_prev=False, deep=None):
+    """per (peer, group): end_slot = leader_last - lag, some dropped / stale-term / conflict replies.
+    stale_prev: a stale reply carries curr_term - 1 instead of 0 (a wide term stays wide).
+    deep = (next_slot [R, G], the log's term): a conflict reply names that term and conflict_slot = next_slot - depth, depth
+    0 .. 20 -- the leader's walk down its log (messages.rs:320-330) goes as far as the reply lets it; in every tick six groups
+    of sixteen carry one of DEPTHS at one peer and a seventh conflict_slot = 0 (on a wrapped log: below ring_lo)"""
     p = np.arange(R, dtype=np.uint64)[:, None]
     g = np.arange(G, dtype=np.uint64)[None, :]
     u = lambda tag: (stream._key(seed, tag, t, p, g) >> np.uint64(11)).astype(np.float64) / float(1 << 53)
@@ -20,32 +27,59 @@ def _replies(seed, t, G, R, log_len, curr_term, lag_max=3, drop_p=0.05, stale_p=
     flags = (u(2) >= drop_p).astype(np.uint8)
     term = np.broadcast_to(curr_term[None, :], (R, G)).astype(np.uint64).copy()
     stale = u(3) < stale_p
-    term[stale] = 0                                                    # stale (smaller) term: still processed
+    term[stale] = (term[stale] - np.minimum(term[stale], 1)) if stale_prev else 0   # stale (smaller) term: still processed
     higher = u(6) < higher_p
     term[higher] += 1                                                  # a peer moved on: leader steps down
     conflict = u(4) < conflict_p
     flags = (flags | (conflict.astype(np.uint8) << 1)).astype(np.uint8)
     cterm = np.where(conflict, curr_term[None, :], 0).astype(np.uint64)
     cslot = np.where(conflict, np.maximum(end_slot.astype(np.int64) - 2, 1), 0).astype(np.uint32)
+    if deep is not None:
+        next_slot, log_term = deep
+        depth = (stream._key(seed, 7, t, p, g) % np.uint64(21)).astype(np.int64)
+        gi, pi = np.arange(G)[None, :], np.arange(R)[:, None]
+        at = pi == 1 + (gi // 16 + t) % (R - 1)                        # (the leader is replica 0)
+        forced = at & (gi % 16 < len(DEPTHS))
+        depth = np.where(forced, np.array(DEPTHS)[gi % 16 % len(DEPTHS)], depth)
+        low = at & (gi % 16 == len(DEPTHS))
+        conflict = conflict | forced | low
+        flags = np.where(forced | low, 3, (flags & 1) | (conflict.astype(np.uint8) << 1)).astype(np.uint8)
+        cterm = np.where(conflict, np.uint64(log_term), np.uint64(0)).astype(np.uint64)
+        cslot = np.where(conflict & ~low, np.maximum(next_slot.astype(np.int64) - depth, 0), 0).astype(np.uint32)
     order = stream.random_ackctl(seed, t, 1, G, R, 0.0)[0]
     return term, end_slot, flags, cterm, cslot, np.ascontiguousarray(order)
 
 
-def _run(cuda, oracle, G, R, W, T, commit_extra=0, higher_p=0.0, n_new_max=3, seed=77):
+def _deep_cover(info, before, after, fl, cs, W):
+    """what a round of replies with deep conflicts reached, on the oracle's dumps around it"""
+    lead = (before["role"] == 2) & (after["role"] == 2)
+    conf = ((fl & 3) == 3) & lead[None, :]
+    fall = np.where(conf, before["next_slot"].astype(np.int64) - after["next_slot"], 0)
+    info["fall_max"] = max(info.get("fall_max", 0), int(fall.max()))
+    info["at_one"] = info.get("at_one", 0) + int((conf & (before["next_slot"] == 1)).sum())
+    lo = np.maximum(before["log_len"].astype(np.int64) - W, 0)
+    info["below_ring"] = info.get("below_ring", 0) + int((conf & (lo[None, :] > 0) & (cs < lo[None, :]) & (before["next_slot"] > 1)).sum())
+
+
+def _run(cuda, oracle, G, R, W, T, commit_extra=0, higher_p=0.0, n_new_max=3, seed=77, term=1, wide=False, deep=False, conflict_p=0.005, info=None):
+    """term: the leader's; wide: stale replies carry term - 1; deep: `_replies(deep=...)`, the run's reach left in `info`"""
     import torch
     from summerset_amd import RaftLeaderGroup
-    eng = RaftLeaderGroup(G, R, 0, W, term=1, commit_extra=commit_extra)
-    orc = oracle.RaftOracle(G, R, W, 0, 1, commit_extra)
-    dev = lambda a: torch.from_numpy(a).to(cuda)
+    eng = RaftLeaderGroup(G, R, 0, W, term=term, commit_extra=commit_extra)
+    orc = oracle.RaftOracle(G, R, W, 0, term, commit_extra)
+    dev = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(cuda)
     for t in range(T):
         n_new = (stream._key(seed, 9, t, np.arange(G, dtype=np.uint64)) % np.uint64(n_new_max + 1)).astype(np.uint32)
         orc.append(n_new)
         eng.handle_req_batch(dev(n_new))
         d = orc.dump()
-        term, es, fl, ct, cs, order = _replies(seed, t, G, R, d["log_len"], d["curr_term"], higher_p=higher_p)
-        orc.handle_replies(term, es, fl, ct, cs, order)
-        eng.handle_msg_append_entries_reply(dev(term), dev(es), dev(fl), dev(ct), dev(cs), dev(order))
+        rt, es, fl, ct, cs, order = _replies(seed, t, G, R, d["log_len"], d["curr_term"], higher_p=higher_p, stale_prev=wide,
+                                             conflict_p=conflict_p, deep=(d["next_slot"], term) if deep else None)
+        orc.handle_replies(rt, es, fl, ct, cs, order)
+        eng.handle_msg_append_entries_reply(dev(rt), dev(es), dev(fl), dev(ct), dev(cs), dev(order))
         a, b = eng.dump(), orc.dump()
+        if deep and info is not None:
+            _deep_cover(info, d, b, fl, cs, W)
         for k in b:
             assert np.array_equal(a[k], b[k]), "tick %d field %s" % (t, k)
         assert eng.total_commits() == orc.total_commits()
@@ -53,15 +87,16 @@ def _run(cuda, oracle, G, R, W, T, commit_extra=0, higher_p=0.0, n_new_max=3, se
     return eng, orc
 
 
-def _run_batched(cuda, oracle, G, R, W, T, batches, higher_p=0.0, n_new_max=3, seed=78, quiet=()):
+def _run_batched(cuda, oracle, G, R, W, T, batches, higher_p=0.0, n_new_max=3, seed=78, quiet=(), term=1, wide=False, deep=False, conflict_p=0.005,
+                 info=None):
     """`smr_raft_leader_run_ticks` (one launch per <= 16 ticks, the state in registers from tick to tick) against the oracle's
     tick-by-tick run of the same inputs: state at every batch boundary.  `quiet`: ticks that pass NULL for their appends /
     replies (and give the oracle none)"""
     import torch
     from summerset_amd import RaftLeaderGroup, SummersetError
-    eng = RaftLeaderGroup(G, R, 0, W, term=1)
-    orc = oracle.RaftOracle(G, R, W, 0, 1, 0)
-    dev = lambda a: torch.from_numpy(a).to(cuda)
+    eng = RaftLeaderGroup(G, R, 0, W, term=term)
+    orc = oracle.RaftOracle(G, R, W, 0, term, 0)
+    dev = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(cuda)
     ticks, snaps = [], []
     for t in range(T):
         n_new = (stream._key(seed, 9, t, np.arange(G, dtype=np.uint64)) % np.uint64(n_new_max + 1)).astype(np.uint32)
@@ -70,10 +105,14 @@ def _run_batched(cuda, oracle, G, R, W, T, batches, higher_p=0.0, n_new_max=3, s
             orc.append(n_new)
             x["n_new"] = dev(n_new)
         d = orc.dump()
-        term, es, fl, ct, cs, order = _replies(seed, t, G, R, d["log_len"], d["curr_term"], higher_p=higher_p)
+        rt, es, fl, ct, cs, order = _replies(seed, t, G, R, d["log_len"], d["curr_term"], higher_p=higher_p, stale_prev=wide,
+                                             conflict_p=conflict_p, deep=(d["next_slot"], term) if deep else None)
         if ("replies", t) not in quiet:
-            orc.handle_replies(term, es, fl, ct, cs, order)
-            x.update(reply_term=dev(term), end_slot=dev(es), flags=dev(fl), conflict_term=dev(ct), conflict_slot=dev(cs), order=dev(order))
+            orc.handle_replies(rt, es, fl, ct, cs, order)
+            x.update(reply_term=dev(rt), end_slot=dev(es), flags=dev(fl), conflict_term=dev(ct), conflict_slot=dev(cs), order=dev(order))
+            if deep and info is not None:
+                _deep_cover(info, d, orc.dump(), fl, cs, W)
+                info.setdefault("conflict_ticks", set()).update([t] if ((fl & 3) == 3).any() else [])
         ticks.append(x)
         snaps.append((orc.dump(), orc.total_commits()))
     t0 = 0
@@ -149,20 +188,20 @@ def _same_reply(r_eng, r_orc, step):
 
 
 @pytest.mark.parametrize("G,W", [(777, 64), (4096, 32)])
-def test_follower_and_elections_match_oracle(cuda, oracle, G, W):
+def test_follower_and_elections_match_oracle(cuda, oracle, G, W, term=1):
     from summerset_amd import RaftLeaderGroup
     import raft_scenarios as sc                       # tests/ is on sys.path under pytest
     R, me, K = 5, 2, 6
     rng = np.random.default_rng(G + W)
-    eng = RaftLeaderGroup(G, R, leader_id=me, window=W, term=1)
-    orc = oracle.RaftOracle(G, R, W, leader_id=me, term=1)
+    eng = RaftLeaderGroup(G, R, leader_id=me, window=W, term=term)
+    orc = oracle.RaftOracle(G, R, W, leader_id=me, term=term)
     # a few leader appends give every group a log, then everybody is a follower of replica 0
     for _ in range(3):
         n_new = rng.integers(0, 4, G).astype(np.uint32)
         eng.handle_req_batch(_t(n_new, cuda))
         orc.append(n_new)
-    eng.preset(0, 0, 1)
-    orc.preset(0, 0, 1)
+    eng.preset(0, 0, term)
+    orc.preset(0, 0, term)
     _same_state(eng, orc, "preset")
     from summerset_amd import stream
     for step in range(40):
@@ -204,6 +243,7 @@ def test_follower_and_elections_match_oracle(cuda, oracle, G, W):
     assert hits == orc.ring_guard_hits(), (hits, orc.ring_guard_hits())
     if W >= 64:
         assert hits == 0, "the follower parity run reached the ring guard %d times" % hits
+    return orc
 
 
 def test_closed_loop_cluster_matches_oracle(cuda, oracle):
@@ -299,13 +339,15 @@ def run_one_launch_replication(dev, oracle, G=600, W=64, K=8, T=16):
     return n_msg
 
 
-def run_one_launch_tick(dev, oracle, G=600, W=64, K=8, T=16, R=5):
+def run_one_launch_tick(dev, oracle, G=600, W=64, K=8, T=16, R=5, down=None):
     """`smr_raft_cluster_tick` -- a sender's append, its AppendEntries for its four peers, their handlers and its reply handler in ONE
     launch -- in the closed loop of tests/raft_cluster.py (elections, a second election in a third of the groups, conflicts and
     truncations behind it), every sender's whole tick before the next sender's: a cluster that runs the 2 + 2 n calls, one that runs
-    the one launch and five oracles stay identical -- every message, every reply, every replica's state, tick by tick"""
+    the one launch and five oracles stay identical -- every message, every reply, every replica's state, tick by tick.
+    down[t]: the replicas nobody reaches at tick t (raft_cluster.tick: the one launch then runs with the followers that are left)"""
     import raft_cluster as rc
     from summerset_amd import RaftLeaderGroup
+    down = down or {}
     mk = lambda: [rc.NumpyRaft(RaftLeaderGroup(G, R, leader_id=r, window=W, term=1), dev) for r in range(R)]
     calls, fused = mk(), mk()
     orcs = [oracle.RaftOracle(G, R, W, leader_id=r, term=1) for r in range(R)]
@@ -319,7 +361,7 @@ def run_one_launch_tick(dev, oracle, G=600, W=64, K=8, T=16, R=5):
         nonlocal n_msg
         seen = ([], [], [])
         for reps, one, sn in ((calls, False, seen[0]), (fused, "tick", seen[1]), (orcs, False, seen[2])):
-            rc.tick(reps, to, n_new, K, sender_ticks=True, one_launch=one, seen=sn)
+            rc.tick(reps, to, n_new, K, sender_ticks=True, one_launch=one, seen=sn, down=down.get(where, ()))
         for (s, q, m0, r0), (_, _, m1, r1), (_, _, m2, r2) in zip(*seen):
             on = m2["flags"] != 0
             n_msg += int(on.sum())

@@ -350,18 +350,23 @@ def test_reply_ingest_argument_edges(cuda):
     assert all(int(o["end_slot"][1, g]) % G == g for g in range(G)) and set(int(o["reply_term"][1, g]) - 100 for g in range(G)) <= set(range(n)) and last
 
 
-def run_fused_raft_wire_replies(cuda, oracle, G=300, R=5, W=64, T=6, seed=21, me=2):
+def run_fused_raft_wire_replies(cuda, oracle, G=300, R=5, W=64, T=6, seed=21, me=2, term0=2, deep=False, info=None):
     """`smr_raft_leader_handle_wire_replies` (round 6: the parse as the prologue of the leader's reply handler, ONE launch, dense
     connections) against the two calls it stands for -- `smr_wire_ingest_raft_replies` + `smr_raft_leader_handle_replies` -- on a
     second leader in the same state, and both against the oracle fed the decoded replies directly: T ticks of appends and replies
     with conflicts, higher terms, junk frames around the replies, second replies (deferred), incomplete tails and malformed
-    connections.  Counts, located frames, `consumed`, `status` and the leaders' state every tick."""
+    connections.  Counts, located frames, `consumed`, `status` and the leaders' state every tick.
+    term0: the leaders' term (the replies carry term0 and term0 + 1, conflicts term0 - 1 and term0: wide ones travel as 9- and
+    10-byte varints).  deep: a third of the replies are conflicts in the log's term whose conflict_slot lies 0 .. 20 (in six
+    groups of sixteen: test_raft_gpu.DEPTHS) below the peer's next_slot -- the leader's walk goes into its second and third
+    round; info: the oracle's largest fall of a next_slot in one reply."""
     import torch
     from summerset_amd import RaftLeaderGroup, wire
     rng = np.random.default_rng(seed)
     F = R - 1
-    a, b = RaftLeaderGroup(G, R, leader_id=me, window=W, term=2), RaftLeaderGroup(G, R, leader_id=me, window=W, term=2)
-    orc = oracle.RaftOracle(G, R, W, leader_id=me, term=2) if oracle is not None else None
+    a, b = RaftLeaderGroup(G, R, leader_id=me, window=W, term=term0), RaftLeaderGroup(G, R, leader_id=me, window=W, term=term0)
+    orc = oracle.RaftOracle(G, R, W, leader_id=me, term=term0) if oracle is not None else None
+    from test_raft_gpu import DEPTHS
     ing_a, ing_b = wire.ReplyIngest(G * F, G, R, 4 * G * F, cuda), wire.ReplyIngest(G * F, G, R, 4 * G * F, cuda)
     peers_of = [p for p in range(R) if p != me]
     grp = torch.from_numpy(np.repeat(np.arange(G), F).astype(np.int32)).to(cuda)
@@ -374,7 +379,8 @@ def run_fused_raft_wire_replies(cuda, oracle, G=300, R=5, W=64, T=6, seed=21, me
             x.handle_req_batch(torch.from_numpy(n_new).to(cuda))
         if orc is not None:
             orc.append(n_new.astype(np.uint32))
-        len_now = a.dump()["log_len"].astype(np.int64)
+        d0 = a.dump()
+        len_now = d0["log_len"].astype(np.int64)
         rt, es, fl = np.zeros((R, G), np.uint64), np.zeros((R, G), np.uint32), np.zeros((R, G), np.uint8)
         ct, cs = np.zeros((R, G), np.uint64), np.zeros((R, G), np.uint32)
         streams = []
@@ -385,22 +391,25 @@ def run_fused_raft_wire_replies(cuda, oracle, G=300, R=5, W=64, T=6, seed=21, me
                     s += junk[int(rng.integers(0, len(junk)))]
                 x = rng.random()
                 if x < 0.85:
-                    term = 2 if rng.random() < 0.995 else 3                                        # (a higher term now and then: the leader steps down)
+                    term = term0 if rng.random() < 0.995 else term0 + 1                            # (a higher term now and then: the leader steps down)
                     end = int(rng.integers(0, max(int(len_now[g]), 1)))
-                    conflict = (int(rng.integers(1, 3)), int(rng.integers(0, max(end, 1)))) if rng.random() < 0.1 else None
+                    conflict = (term0 - 2 + int(rng.integers(1, 3)), int(rng.integers(0, max(end, 1)))) if rng.random() < 0.1 else None
+                    if deep and (g + t + p) % 3 == 0:
+                        depth = DEPTHS[g % 16] if g % 16 < len(DEPTHS) else int(rng.integers(0, 21))
+                        conflict = (term0, max(int(d0["next_slot"][p, g]) - depth, 0))
                     s += _raft_reply(term, end, conflict)
                     rt[p, g], es[p, g], fl[p, g] = term, end, 1 | (2 if conflict else 0)
                     if conflict:
                         ct[p, g], cs[p, g] = conflict
                     y = rng.random()
                     if y < 0.05:
-                        s += _raft_reply(2, 1)                                                       # a second reply: the next call's
+                        s += _raft_reply(term0, 1)                                                   # a second reply: the next call's
                     elif y < 0.1:
                         s += _raft_reply(1 << 40, 7)[:int(rng.integers(1, 11))]                      # an incomplete tail
                     elif y < 0.13:
                         s += _frame(_varint(0) + _varint(9))                                         # malformed behind a delivered reply
                 elif x < 0.9:
-                    s += _raft_reply(2, (1 << 32) + 5)                                               # a slot beyond u32: located, not taken
+                    s += _raft_reply(term0, (1 << 32) + 5)                                           # a slot beyond u32: located, not taken
                 streams.append(bytes(s))
         buf, off, _, _, _ = _layout(torch, cuda, streams, [0] * len(streams), [0] * len(streams))
         o = ing_a.raft(buf, off, grp, peer)
@@ -422,6 +431,10 @@ def run_fused_raft_wire_replies(cuda, oracle, G=300, R=5, W=64, T=6, seed=21, me
             do = orc.dump()
             for n in do:
                 assert np.array_equal(db[n], do[n]), (t, n, "oracle")
+            if info is not None:
+                lead = (d0["role"] == 2) & (do["role"] == 2)
+                fall = np.where(((fl & 3) == 3) & lead[None, :], d0["next_slot"].astype(np.int64) - do["next_slot"], 0)
+                info["fall_max"] = max(info.get("fall_max", 0), int(fall.max()))
         n_exec = int(db["last_commit"].sum())
     assert n_exec > 0
     return n_exec
