@@ -366,6 +366,11 @@ int smr_mp_deliver_acks_conn(smr_mp_cluster *c, uint8_t rep, const void *acks12_
 int smr_mp_collect_acks(smr_mp_cluster *c, uint8_t rep, smr_mp_ack *out_dev, uint64_t cap, uint64_t *n_dev, void *stream);
 int smr_mp_clear_acks(smr_mp_cluster *c, uint8_t rep, void *stream);
 
+/* debug / measurement only: the one device allocation that holds every array of the cluster (ring rows dead or alive,
+ * outboxes, ack matrices, scratch), i.e. what a wholesale copy of the engine's state would move -- tools/time_mp_snapshot.py
+ * times that copy beside smr_mp_save_state.  The layout inside is the library's own; nothing else may depend on it. */
+int smr_mp_debug_arena_view(smr_mp_cluster *c, void **base_dev, uint64_t *n_bytes);
+
 /* --- read-back (host buffers; each call synchronizes the device) -------- */
 int smr_mp_read_group_state(smr_mp_cluster *c, uint32_t group, uint8_t rep, smr_mp_group_state *out);
 
@@ -386,6 +391,52 @@ int smr_mp_dump(smr_mp_cluster *c, uint8_t rep, const smr_mp_dump_bufs *host_buf
  * parity check at BASELINE sizes uses: 65 536 groups run on the device, slices of them are compared against an
  * oracle started at that group offset (1.8 GB per replica would cross PCIe for a full dump at W = 512). */
 int smr_mp_dump_range(smr_mp_cluster *c, uint8_t rep, uint32_t g0, uint32_t n, const smr_mp_dump_bufs *host_bufs);
+
+/* ---- save / load of a cluster's state, on the device ---------------------------------------------------------------------
+ * A snapshot is a device-resident object that holds what the cluster's next tick depends on: for every LIVE replica the
+ * scalars of smr_mp_group_state, every slot of [start_slot, log_len) with the fields smr_mp_dump gives, the pending entries
+ * of the next tick's outbox (the Accepts a prepare quorum of R3 leaves, messages.rs:238-286), the overflow flags, the
+ * counters and the committed-slot entries not yet polled.  It is what the reference keeps across a restart in its snapshot
+ * file and WAL (snapshot.rs:121-186 take_new_snapshot, recovery.rs recover_from_wal) plus the volatile replica state
+ * that its crash-restart loop (summerset_server/src/main.rs:124-167) rebuilds from nothing and a checkpoint must not
+ * lose.  Not carried, because results do not depend on them: the straggler list, role rotation, profiling events and the
+ * scratch a tick fills and consumes itself (ack matrix, PrepareReply batch, heartbeat record).
+ *   smr_mp_snapshot_create   room for the worst case of `like` (every ring row live, every outbox full: a fraction of the
+ *                            cluster's own allocation), so a save never finds the snapshot too small and its result needs
+ *                            no confirmation; a cluster with a larger window / outbox_cap / commit_list_cap saved into it
+ *                            later makes it grow in that save call (sizes the host knows: no read-back);
+ *   smr_mp_save_state        one kernel on `stream`, enqueues only.  Between two ticks: SMR_ERR_STATE inside an open
+ *                            smr_mp_spread tick, a side-stream fork or a round-by-round tick with the straggler list on
+ *                            that smr_mp_end_tick has not closed.  (It would first complete a deferred R3 rest; today
+ *                            smr_mp_run_ticks leaves none behind, so that is a defence only);
+ *   smr_mp_load_state        the inverse, one kernel: overwrites the whole logical state of the live replicas (not-live
+ *                            replicas of a spread block are left alone).  Needs the same n_groups, population, commit_extra
+ *                            and live mask, window >= max_live, outbox_cap >= max_outbox, commit_list_cap >= the entries
+ *                            carried per replica -- else SMR_ERR_ARG and the cluster is untouched.  Synchronises once
+ *                            per save to read the image's header;
+ *   smr_mp_snapshot_info_get synchronises;
+ *   smr_mp_snapshot_export / _import   the image as host bytes.  The format is canonical: two clusters that hold the
+ *                            same logical state export the same bytes, whatever their window, outbox_cap, straggler_ticks,
+ *                            role rotation, or the calls their ticks were run by.  One exception: a commit
+ *                            list that OVERFLOWED (entries were lost; smr_mp_poll_commits reports n_out > cap) leaves its
+ *                            length and commit_list_cap entries in the image, as the loaded cluster must report the
+ *                            same loss.  Import checks everything
+ *                            (SMR_ERR_ARG) and never reads past len.  Export returns the bytes written, < 0 on error
+ *                            (SMR_ERR_ARG: cap below info.bytes). */
+typedef struct smr_mp_snapshot smr_mp_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint64_t n_slots, n_outbox;     /* live slots / pending next-tick outbox entries, over all saved replicas and groups */
+    uint32_t n_groups, max_live, max_outbox;   /* max live span (log_len - start_slot) and max pending outbox of one (replica, group) */
+    uint8_t population, commit_extra, live_mask, reserved;
+} smr_mp_snapshot_info;
+int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out);
+void smr_mp_snapshot_destroy(smr_mp_snapshot *s);
+int smr_mp_save_state(smr_mp_cluster *c, smr_mp_snapshot *s, void *stream);
+int smr_mp_load_state(smr_mp_cluster *c, const smr_mp_snapshot *s, void *stream);
+int smr_mp_snapshot_info_get(const smr_mp_snapshot *s, smr_mp_snapshot_info *out);
+int64_t smr_mp_snapshot_export(const smr_mp_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len);
 
 /* counters of replica `rep`: [0] leader-side commits (Accepting->Committed,
  * messages.rs:412-433), [1] redirected batches (request.rs:128-154),

@@ -60,6 +60,12 @@ class MpGroupState(C.Structure):
                 ("peer_exec_bar", C.c_uint32 * SMR_MAX_REPLICAS)]
 
 
+class MpSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_slots", C.c_uint64), ("n_outbox", C.c_uint64), ("n_groups", C.c_uint32),
+                ("max_live", C.c_uint32), ("max_outbox", C.c_uint32), ("population", C.c_uint8), ("commit_extra", C.c_uint8),
+                ("live_mask", C.c_uint8), ("reserved", C.c_uint8)]
+
+
 MP_DUMP_FIELDS = ["leader", "bal_prep_sent", "bal_prepared", "bal_max_seen", "start_slot", "log_len",
                   "accept_bar", "commit_bar", "exec_bar", "snap_bar", "peer_exec_bar", "s_bal", "s_status",
                   "s_reqs", "s_vbal", "s_vreqs", "s_flags", "s_acks", "s_packs", "s_pmax", "s_ltrig",
@@ -254,6 +260,14 @@ SYMBOLS = [
     ("smr_mp_spread_tick", _i, [_vp, _vp, _i, _vp]),
     ("smr_mp_straggler_stats", _i, [_vp, C.POINTER(_u64 * 2)]),
     ("smr_mp_poll_commits", _i, [_vp, _u8, _vp, _vp, _u64, C.POINTER(_u64)]),
+    ("smr_mp_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("smr_mp_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_mp_snapshot_destroy", None, [_vp]),
+    ("smr_mp_save_state", _i, [_vp, _vp, _vp]),
+    ("smr_mp_load_state", _i, [_vp, _vp, _vp]),
+    ("smr_mp_snapshot_info_get", _i, [_vp, C.POINTER(MpSnapshotInfo)]),
+    ("smr_mp_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_mp_snapshot_import", _i, [_vp, _vp, _u64]),
     ("smr_mp_profile_enable", _i, [_vp, _i]),
     ("smr_mp_profile_read", _i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("smr_raft_leader_create", _i, [C.POINTER(RaftCfg), C.POINTER(_vp)]),

@@ -103,8 +103,7 @@ struct Lane {
 
     __device__ __forceinline__ void bal_touch() { BAL_TOUCH(); }   // for callers outside the struct (experiments, see above)
     static __device__ __forceinline__ uint32_t follower_run_meta(uint32_t tok, uint32_t ldr, bool executed) {
-        return (executed ? SMR_ST_EXECUTED : SMR_ST_ACCEPTING) | M_RBK | (ldr << M_SRC_SH) | (VM_SAME << M_VMODE_SH) |
-               (tok ? M_NONEMPTY : 0u);
+        return smr::follower_run_meta(tok, ldr, executed);      // (mp_types.h: shared with the dump and the snapshot kernels)
     }
     // is `slot` inside a follower's run: its meta word is not stored (see above)
     __device__ __forceinline__ bool meta_unstored(uint32_t slot) const { return slot >= brun && leader != me; }

@@ -9,11 +9,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <functional>
 #include <vector>
 
 #include "mp_device.h"
 #include "smr_common.h"
+#include "mp_snapshot.h"
 
 // experiment (profiles/r9h): the bulk round kernels' wavefronts at a raised issue priority, so that on a SIMD they share with the
 // side launch's wavefronts they go first.  Off unless built with -DSMR_BULK_PRIO=1..3
@@ -2029,6 +2031,7 @@ struct smr_mp_cluster {
     int rest_par = 0;
     const uint32_t *rest_ackctl = nullptr;
     uint32_t lead_hint = 0;          // the replica most groups are led by (smr_mp_preset_leader): the tally's speculative loads
+    bool spread_open = false;        // a smr_mp_spread tick is open on this block (between its segment 0 and its end / abort): no save, no load
     bool profile = false;
     std::vector<ProfEv> evs;
     double prof_ms[5] = {0, 0, 0, 0, 0};
@@ -2384,6 +2387,7 @@ int smr_mp_end_tick(smr_mp_cluster *c) {
     if (c->marked && c->side_on) c->lpar ^= 1;
     c->marked = false;
     c->side_on = false;
+    c->spread_open = false;
     return SMR_OK;
 }
 
@@ -2690,6 +2694,12 @@ int smr_mp_clear_acks(smr_mp_cluster *c, uint8_t rep, void *stream) {
     return SMR_OK;
 }
 
+int smr_mp_debug_arena_view(smr_mp_cluster *c, void **base_dev, uint64_t *n_bytes) {
+    if (!c || !base_dev || !n_bytes) return fail(SMR_ERR_ARG, "mp: bad argument");
+    *base_dev = c->arena.base; *n_bytes = c->arena.size;
+    return SMR_OK;
+}
+
 int smr_mp_replica_log_view(smr_mp_cluster *c, uint8_t rep, smr_qread_log *out) {
     if (!c || !out || rep >= c->cfg.population) return fail(SMR_ERR_ARG, "mp: bad argument");
     const MpRep &v = c->hp.rep[rep];
@@ -2764,23 +2774,14 @@ int smr_mp_dump_range(smr_mp_cluster *c, uint8_t rep, uint32_t g0, uint32_t n, c
             const size_t o = (size_t)(s & (W - 1)) * G + g;                     // host index
             const size_t t = tix((uint32_t)W, s & (uint32_t)(W - 1), (uint32_t)g);   // index inside the copied tiles
             uint32_t m = meta[t];
-            if (s >= bal_lo[g]) bal[t] = hb->bal_max_seen[g];                    // inside the run the ballot is not stored
-            if (s >= bal_lo[g] && hb->leader[g] != rep)                          // a follower's run: nor the meta word (mp_device.h)
-                m = (s < hb->commit_bar[g] ? SMR_ST_EXECUTED : SMR_ST_ACCEPTING) | M_RBK | ((uint32_t)hb->leader[g] << M_SRC_SH) |
-                    (VM_SAME << M_VMODE_SH) | (val[t] ? M_NONEMPTY : 0u);
-            else if (s >= bal_lo[g] && s < hb->commit_bar[g]) m = (m & ~M_STATUS) | SMR_ST_EXECUTED;   // nor the statuses the bars imply
-            hb->s_bal[o] = bal[t]; hb->s_status[o] = (uint8_t)(m & M_STATUS); hb->s_reqs[o] = val[t];
-            uint32_t vm = (m >> M_VMODE_SH) & 3u;
-            hb->s_vbal[o] = vm == VM_SAME ? bal[t] : (vm == VM_SIDE ? vbal[t] : 0);
-            hb->s_vreqs[o] = vm == VM_SAME ? val[t] : (vm == VM_SIDE ? vval[t] : 0);
-            bool lbk = m & M_LBK, rbk = m & M_RBK;
-            hb->s_flags[o] = (uint8_t)((lbk ? 1 : 0) | (rbk ? 2 : 0) | ((m & M_EXT) ? 4 : 0));
-            hb->s_acks[o] = lbk ? (uint8_t)((m >> M_ACKS_SH) & 0xFF) : 0;
-            hb->s_packs[o] = lbk ? (uint8_t)((m >> M_PACKS_SH) & 0xFF) : 0;
-            bool lx = lbk && (m & M_LBKX), rx = rbk && (m & M_RBKX);
-            hb->s_pmax[o] = lx ? pmax[t] : 0; hb->s_ltrig[o] = lx ? ltrig[t] : 0; hb->s_lendp[o] = lx ? lendp[t] : 0;
-            hb->s_src[o] = rbk ? (uint8_t)((m >> M_SRC_SH) & 7) : 0;
-            hb->s_rtrig[o] = rx ? rtrig[t] : 0; hb->s_rendp[o] = rx ? rendp[t] : 0;
+            // what the ring leaves unstored, and the explicit Instance fields: the rules the snapshot kernels use (mp_snapshot.h)
+            mp_slot_stored(s, bal_lo[g], hb->leader[g], rep, hb->commit_bar[g], hb->bal_max_seen[g], val[t], bal[t], m);
+            const SnapSlot k = mp_slot_canon(m, bal[t], val[t], vbal[t], vval[t], pmax[t], ltrig[t], lendp[t], rtrig[t], rendp[t]);
+            hb->s_bal[o] = k.bal; hb->s_status[o] = k.status; hb->s_reqs[o] = k.reqs;
+            hb->s_vbal[o] = k.vbal; hb->s_vreqs[o] = k.vreqs;
+            hb->s_flags[o] = k.flags; hb->s_acks[o] = k.acks; hb->s_packs[o] = k.packs;
+            hb->s_pmax[o] = k.pmax; hb->s_ltrig[o] = k.ltrig; hb->s_lendp[o] = k.lendp;
+            hb->s_src[o] = k.src; hb->s_rtrig[o] = k.rtrig; hb->s_rendp[o] = k.rendp;
         }
     }
     return SMR_OK;
@@ -3032,6 +3033,7 @@ int smr_mp_spread_segment(smr_mp_spread *s, int segment, const smr_mp_tick_in *i
     s->next_segment = (segment == 3 || (segment == 2 && !heartbeat)) ? 0 : segment + 1;
     int rc;
     const size_t n = s->cl.size();
+    for (smr_mp_cluster *c : s->cl) c->spread_open = true;       // until smr_mp_end_tick or smr_mp_spread_abort_tick
     hipStream_t st = (hipStream_t)stream;
     switch (segment) {
     case 0:                                                  // R1 everywhere, then the outboxes into the send buffer
@@ -3072,6 +3074,7 @@ int smr_mp_spread_abort_tick(smr_mp_spread *s) {
     if (!s) return fail(SMR_ERR_ARG, "mp spread: null argument");
     s->next_segment = 0;
     s->tick_heartbeat = 0;
+    for (smr_mp_cluster *c : s->cl) c->spread_open = false;
     return SMR_OK;
 }
 
@@ -3108,6 +3111,250 @@ int smr_mp_spread_tick(smr_mp_spread *s, const smr_mp_tick_in *in, int heartbeat
             return rc;
         }
     }
+    return SMR_OK;
+}
+
+/* ---- save / load of a cluster's state on the device (mp_snapshot.h: the image and its two kernels) ------------------------------
+ * The crash-restart loop of summerset_server/src/main.rs:124-167 brings a replica back from its snapshot file and WAL
+ * (snapshot.rs:121-186, recovery.rs); a batched cluster is saved and brought back whole, between two ticks, by one kernel each. */
+struct smr_mp_snapshot {
+    uint32_t G = 0;
+    uint8_t R = 0, commit_extra = 0, live = 0;
+    uint8_t *dev = nullptr;
+    uint64_t cap_slots = 0, cap_ob = 0, cap_cl = 0;              // records the device buffer's three sections have room for
+    bool filled = false, hdr_known = false;                      // a save / import has run; `hdr` is the image's header
+    SnapHdr hdr;
+    uint32_t lead_hint = 0;                                      // (scheduling only: not part of the image)
+};
+
+static SnapImg snap_img(const smr_mp_snapshot *s) {
+    SnapImg S;
+    S.base = s->dev; S.cap_slots = s->cap_slots; S.cap_ob = s->cap_ob; S.cap_cl = s->cap_cl;
+    S.geo = snap_geom(s->G, s->R, s->live); S.commit_extra = s->commit_extra;
+    return S;
+}
+static int snap_alloc(smr_mp_snapshot *s, uint64_t cap_slots, uint64_t cap_ob, uint64_t cap_cl) {
+    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
+    s->cap_slots = cap_slots; s->cap_ob = cap_ob; s->cap_cl = cap_cl;
+    const SnapImg S = snap_img(s);
+    const uint64_t bytes = snap_off_clist(S) + cap_cl * 8;
+    hipError_t e = hipMalloc((void **)&s->dev, bytes);
+    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("mp snapshot: hipMalloc: ") + hipGetErrorString(e)); }
+    return SMR_OK;
+}
+// room for the worst case of a cluster with c's window, outbox_cap and commit_list_cap: every ring row live, every outbox
+// full.  A save can then never find the snapshot too small, so it stays a call that only enqueues and whose result needs no
+// confirmation before the state moves on (the abort-restore path loads it after the cluster has).  The worst case is a
+// fraction of the arena (56 B of its ~150 B per ring row, no ack matrix, no scratch); untouched pages cost nothing but
+// address space.  Grows (host-known sizes: no read-back) when a cluster with larger capacities is saved into it.
+static int snap_room(smr_mp_snapshot *s, const smr_mp_cluster *c) {
+    const SnapGeom q = snap_geom(s->G, s->R, s->live);
+    const uint64_t GL = (uint64_t)s->G * q.L;
+    const uint64_t ns = GL * c->cfg.window, no = GL * c->cfg.outbox_cap, nc = (uint64_t)q.L * c->cfg.commit_list_cap;
+    if (s->dev && ns <= s->cap_slots && no <= s->cap_ob && nc <= s->cap_cl) return SMR_OK;
+    s->filled = false; s->hdr_known = false;                     // (what it held goes with the old buffer)
+    return snap_alloc(s, ns > s->cap_slots ? ns : s->cap_slots, no > s->cap_ob ? no : s->cap_ob, nc > s->cap_cl ? nc : s->cap_cl);
+}
+// the image's header on the host (synchronises once after a save)
+static int snap_header(smr_mp_snapshot *s) {
+    if (!s->filled) return fail(SMR_ERR_STATE, "mp snapshot: nothing saved or imported yet");
+    if (s->hdr_known) return SMR_OK;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(SnapHdr), hipMemcpyDeviceToHost));
+    const SnapHdr &h = s->hdr;
+    // (cannot happen: the kernel clamps a group's counts to the window and outbox_cap the room was made for)
+    if (h.n_slots > s->cap_slots || h.n_outbox > s->cap_ob || h.n_commits > s->cap_cl) {
+        s->filled = false;
+        return fail(SMR_ERR_STATE, "mp snapshot: the saved state exceeds the snapshot's room");
+    }
+    s->hdr_known = true;
+    return SMR_OK;
+}
+static bool snap_like(const smr_mp_snapshot *s, const smr_mp_cluster *c) {
+    return s->G == c->cfg.n_groups && s->R == c->cfg.population && s->commit_extra == c->cfg.commit_extra && s->live == (uint8_t)c->hp.live;
+}
+
+int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    if (like->hp.live == 0) return fail(SMR_ERR_ARG, "mp snapshot: the cluster has no live replica");
+    smr_mp_snapshot *s = new smr_mp_snapshot();
+    s->G = like->cfg.n_groups; s->R = like->cfg.population; s->commit_extra = like->cfg.commit_extra; s->live = (uint8_t)like->hp.live;
+    memset(&s->hdr, 0, sizeof(s->hdr));
+    if (int rc = snap_room(s, like)) { delete s; return rc; }
+    *out = s;
+    return SMR_OK;
+}
+
+void smr_mp_snapshot_destroy(smr_mp_snapshot *s) {
+    if (!s) return;
+    if (s->dev) { (void)hipDeviceSynchronize(); (void)hipFree(s->dev); }
+    delete s;
+}
+
+int smr_mp_save_state(smr_mp_cluster *c, smr_mp_snapshot *s, void *stream) {
+    if (!c || !s) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    if (!snap_like(s, c)) return fail(SMR_ERR_ARG, "mp snapshot: made for another n_groups / population / commit_extra / live mask");
+    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, "mp snapshot: save inside an open tick");
+    if (int rc = snap_room(s, c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // A deferred R3 rest holds the caller's ackctl pointer and must not outlive the boundary.  Defence only: today
+    // smr_mp_run_ticks never defers the rest of a batch's last tick and flushes what is left before it returns, so no boundary
+    // a caller can see has one pending and this branch does not run.
+    if (c->rest_pending) {
+        c->rest_pending = false;
+        hipLaunchKernelGGL(mp_round_replies, mp_grid(c), dim3(MP_BLOCK), 0, st, c->dp, c->rest_par, c->rest_ackctl, 0, 0);
+        SMR_HIP_TRY(hipGetLastError());
+    }
+    const SnapImg S = snap_img(s);
+    hipLaunchKernelGGL(mp_snap_pack, dim3(S.geo.nblock), dim3(256), 0, st, c->dp, c->par, S);
+    SMR_HIP_TRY(hipGetLastError());
+    s->filled = true; s->hdr_known = false;
+    s->lead_hint = c->lead_hint;
+    return SMR_OK;
+}
+
+int smr_mp_load_state(smr_mp_cluster *c, const smr_mp_snapshot *cs, void *stream) {
+    if (!c || !cs) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);      // (the header is read back and cached on first use)
+    if (!snap_like(s, c)) return fail(SMR_ERR_ARG, "mp snapshot: made for another n_groups / population / commit_extra / live mask");
+    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, "mp snapshot: load inside an open tick");
+    if (int rc = snap_header(s)) return rc;
+    const SnapHdr &h = s->hdr;
+    if (h.n_groups != c->cfg.n_groups || h.population != c->cfg.population || h.commit_extra != c->cfg.commit_extra || h.live_mask != (uint8_t)c->hp.live)
+        return fail(SMR_ERR_ARG, "mp snapshot: the image is of another n_groups / population / commit_extra / live mask");
+    if (h.max_live > c->cfg.window)
+        return fail(SMR_ERR_ARG, "mp snapshot: a log of " + std::to_string(h.max_live) + " live slots does not fit window " + std::to_string(c->cfg.window));
+    if (h.max_outbox > c->cfg.outbox_cap)
+        return fail(SMR_ERR_ARG, "mp snapshot: " + std::to_string(h.max_outbox) + " pending outbox entries do not fit outbox_cap " + std::to_string(c->cfg.outbox_cap));
+    if (h.max_commits > c->cfg.commit_list_cap)
+        return fail(SMR_ERR_ARG, "mp snapshot: " + std::to_string(h.max_commits) + " unpolled commits do not fit commit_list_cap " + std::to_string(c->cfg.commit_list_cap));
+    c->rest_pending = false;                                     // whatever the cluster had pending belongs to the state that goes
+    c->lead_hint = s->lead_hint < c->cfg.population ? s->lead_hint : 0u;
+    const SnapImg S = snap_img(s);
+    hipLaunchKernelGGL(mp_snap_unpack, dim3(S.geo.nblock), dim3(256), 0, (hipStream_t)stream, c->dp, c->par, S);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_mp_snapshot_info_get(const smr_mp_snapshot *cs, smr_mp_snapshot_info *out) {
+    if (!cs || !out) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);
+    if (int rc = snap_header(s)) return rc;
+    const SnapHdr &h = s->hdr;
+    memset(out, 0, sizeof(*out));
+    out->bytes = h.bytes; out->n_slots = h.n_slots; out->n_outbox = h.n_outbox;
+    out->n_groups = h.n_groups; out->max_live = h.max_live; out->max_outbox = h.max_outbox;
+    out->population = h.population; out->commit_extra = h.commit_extra; out->live_mask = h.live_mask;
+    return SMR_OK;
+}
+
+int64_t smr_mp_snapshot_export(const smr_mp_snapshot *cs, uint8_t *host, uint64_t cap) {
+    if (!cs || !host) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);
+    if (int rc = snap_header(s)) return rc;
+    const SnapHdr &h = s->hdr;
+    if (cap < h.bytes) return fail(SMR_ERR_ARG, "mp snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
+    const SnapImg S = snap_img(s);
+    const SnapGeom &q = S.geo;
+    uint8_t *p = host;
+    SMR_HIP_TRY(hipMemcpy(p, s->dev, q.fixed, hipMemcpyDeviceToHost)); p += q.fixed;
+    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(p, s->dev + q.fixed, h.n_slots * sizeof(SnapSlot), hipMemcpyDeviceToHost));
+    p += h.n_slots * sizeof(SnapSlot);
+    if (h.n_outbox) SMR_HIP_TRY(hipMemcpy(p, s->dev + snap_off_msgs(S), h.n_outbox * sizeof(SnapMsg), hipMemcpyDeviceToHost));
+    p += h.n_outbox * sizeof(SnapMsg);
+    if (h.n_commits) SMR_HIP_TRY(hipMemcpy(p, s->dev + snap_off_clist(S), h.n_commits * 8, hipMemcpyDeviceToHost));
+    // the list's order across groups is the order the wavefronts' appends happened to land in (smr_mp_poll_commits: unspecified):
+    // canonical is a replica's groups ascending, a group's entries in the order they came
+    std::vector<uint64_t> e;
+    for (uint32_t i = 0; i < q.L; i++) {
+        SnapRep rp;
+        memcpy(&rp, host + q.off_rep + (size_t)i * sizeof(SnapRep), sizeof(rp));
+        e.resize(rp.clist_carried);
+        if (rp.clist_carried) {
+            memcpy(e.data(), p, rp.clist_carried * 8);
+            std::stable_sort(e.begin(), e.end(), [](uint64_t a, uint64_t b) { return (a >> 32) < (b >> 32); });
+            memcpy(p, e.data(), rp.clist_carried * 8);
+        }
+        p += rp.clist_carried * 8;
+    }
+    return (int64_t)h.bytes;
+}
+
+int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len) {
+    if (!s || !host) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    if (len < sizeof(SnapHdr)) return fail(SMR_ERR_ARG, "mp snapshot: image shorter than its header");
+    SnapHdr h;
+    memcpy(&h, host, sizeof(h));
+    if (h.magic != SNAP_MAGIC) return fail(SMR_ERR_ARG, "mp snapshot: not a snapshot image (magic)");
+    if (h.version != SNAP_VERSION) return fail(SMR_ERR_ARG, "mp snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(SNAP_VERSION));
+    if (h.n_groups != s->G || h.population != s->R || h.commit_extra != s->commit_extra || h.live_mask != s->live || h.reserved0 || h.reserved1)
+        return fail(SMR_ERR_ARG, "mp snapshot: the image is of another n_groups / population / commit_extra / live mask");
+    const SnapGeom q = snap_geom(s->G, s->R, s->live);
+    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed) return fail(SMR_ERR_ARG, "mp snapshot: truncated image");
+    const uint64_t room = h.bytes - q.fixed;                      // the three record sections; each count bounded before it is multiplied
+    if (h.n_slots > room / sizeof(SnapSlot) || h.n_outbox > room / sizeof(SnapMsg) || h.n_commits > room / 8 ||
+        h.n_slots * sizeof(SnapSlot) + h.n_outbox * sizeof(SnapMsg) + h.n_commits * 8 != room)
+        return fail(SMR_ERR_ARG, "mp snapshot: the header's counts do not add up to the image's size");
+    // the body against the header: counts and maxima recomputed from the scalars, the records' enumerated fields in range
+    const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("mp snapshot: malformed image: ") + what); };
+    for (uint64_t p = s->G; p < snap_a8(s->G); p++) if (host[q.off_ovf + p]) return bad("padding is not zero");
+    uint64_t n_slots = 0, n_outbox = 0, n_commits = 0;
+    uint32_t max_live = 0, max_outbox = 0, max_commits = 0;
+    for (uint32_t i = 0; i < q.L; i++) {
+        const uint8_t *b = host + q.off_scal + (size_t)i * q.scal_stride;
+        for (uint32_t g = 0; g < s->G; g++) {
+            uint32_t st, ln, nob;
+            memcpy(&st, b + q.o_start + 4 * (size_t)g, 4); memcpy(&ln, b + q.o_len + 4 * (size_t)g, 4); memcpy(&nob, b + q.o_nob + 4 * (size_t)g, 4);
+            if (ln < st || ln - st > (1u << 20)) return bad("log_len below start_slot, or a log longer than any window");
+            uint32_t bars[3];                                     // accept_bar, commit_bar, exec_bar: inside [start_slot, log_len]
+            memcpy(&bars[0], b + q.o_abar + 4 * (size_t)g, 4); memcpy(&bars[1], b + q.o_cbar + 4 * (size_t)g, 4); memcpy(&bars[2], b + q.o_ebar + 4 * (size_t)g, 4);
+            for (uint32_t bar : bars) if (bar < st || bar > ln) return bad("a bar outside [start_slot, log_len]");
+            if (nob > OB_SLOT_MASK) return bad("outbox count");
+            const uint8_t ld = b[q.o_leader + g];
+            if (ld != NO_REP && ld >= s->R) return bad("leader id");
+            n_slots += ln - st; n_outbox += nob;
+            max_live = ln - st > max_live ? ln - st : max_live; max_outbox = nob > max_outbox ? nob : max_outbox;
+        }
+        for (uint64_t p = q.o_leader + s->G; p < q.scal_stride; p++) if (b[p]) return bad("padding is not zero");
+        SnapRep rp;
+        memcpy(&rp, host + q.off_rep + (size_t)i * sizeof(SnapRep), sizeof(rp));
+        if (rp.clist_carried > rp.clist_total || rp.clist_total > 0xFFFFFFFFull) return bad("commit list counts");
+        n_commits += rp.clist_carried;
+        max_commits = rp.clist_carried > max_commits ? (uint32_t)rp.clist_carried : max_commits;
+    }
+    if (n_slots != h.n_slots || n_outbox != h.n_outbox || n_commits != h.n_commits || max_live != h.max_live || max_outbox != h.max_outbox ||
+        max_commits != h.max_commits)
+        return bad("the header's counts and maxima contradict the body");
+    const uint8_t *p = host + q.fixed;
+    for (uint64_t k = 0; k < h.n_slots; k++, p += sizeof(SnapSlot)) {
+        SnapSlot c;
+        memcpy(&c, p, sizeof(c));
+        if (c.status > SMR_ST_EXECUTED || c.flags > 7 || c.src >= s->R || c.pad[0] || c.pad[1] || c.pad[2]) return bad("slot record");
+    }
+    for (uint64_t k = 0; k < h.n_outbox; k++, p += sizeof(SnapMsg)) {
+        SnapMsg m;
+        memcpy(&m, p, sizeof(m));
+        if ((m.slot >> OB_KIND_SH) == 0 || m.pad) return bad("outbox record");
+    }
+    for (uint64_t k = 0; k < h.n_commits; k++, p += 8) {
+        uint64_t e;
+        memcpy(&e, p, 8);
+        if ((e >> 32) >= s->G) return bad("commit entry of a group beyond n_groups");
+    }
+    if (h.n_slots > s->cap_slots || h.n_outbox > s->cap_ob || h.n_commits > s->cap_cl)
+        if (int rc = snap_alloc(s, h.n_slots > s->cap_slots ? h.n_slots : s->cap_slots, h.n_outbox > s->cap_ob ? h.n_outbox : s->cap_ob,
+                                h.n_commits > s->cap_cl ? h.n_commits : s->cap_cl)) return rc;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    s->filled = false;
+    const SnapImg S = snap_img(s);
+    p = host;
+    SMR_HIP_TRY(hipMemcpy(s->dev, p, q.fixed, hipMemcpyHostToDevice)); p += q.fixed;
+    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(s->dev + q.fixed, p, h.n_slots * sizeof(SnapSlot), hipMemcpyHostToDevice));
+    p += h.n_slots * sizeof(SnapSlot);
+    if (h.n_outbox) SMR_HIP_TRY(hipMemcpy(s->dev + snap_off_msgs(S), p, h.n_outbox * sizeof(SnapMsg), hipMemcpyHostToDevice));
+    p += h.n_outbox * sizeof(SnapMsg);
+    if (h.n_commits) SMR_HIP_TRY(hipMemcpy(s->dev + snap_off_clist(S), p, h.n_commits * 8, hipMemcpyHostToDevice));
+    s->hdr = h; s->filled = true; s->hdr_known = true; s->lead_hint = 0;
     return SMR_OK;
 }
 

@@ -209,6 +209,14 @@ struct RepView {
     SMR_HD SMR_G uint64_t *ob_rbal(int p) const { return sh(b.ob_rbal[p]); }
 };
 
+// the meta word a follower's steady-state append would have stored for a slot of its run (mp_device.h: Lane::end_run): fresh
+// ReplicaBookkeeping from leader `ldr`, voted = (ballot, reqs), Accepting, or Executed once the bars passed it.  The one place
+// that says it: Lane, the state dump and the snapshot kernels read run slots through here
+SMR_HD uint32_t follower_run_meta(uint32_t tok, uint32_t ldr, bool executed) {
+    return (executed ? (uint32_t)SMR_ST_EXECUTED : (uint32_t)SMR_ST_ACCEPTING) | M_RBK | (ldr << M_SRC_SH) | (VM_SAME << M_VMODE_SH) |
+           (tok ? M_NONEMPTY : 0u);
+}
+
 struct MpParams {
     uint32_t G, W, Wmask, cap, pcap, win_reserve, clist_cap;
     uint32_t R, quorum, thresh, rspaxos;

@@ -26,6 +26,50 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+class MpSnapshot:
+    """A cluster's state between two ticks, held on the device (`smr_mp_snapshot`): what `MultiPaxosCluster.save_state`
+    fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any two clusters that hold the
+    same logical state -- and `from_bytes` takes one back."""
+
+    def __init__(self, like):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        check(self._L.smr_mp_snapshot_create(like._h, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.smr_mp_snapshot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def info(self):
+        """sizes of what was saved (synchronises): bytes, n_slots, n_outbox, n_groups, max_live, max_outbox, population,
+        commit_extra, live_mask"""
+        st = _lib.MpSnapshotInfo()
+        check(self._L.smr_mp_snapshot_info_get(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
+
+    def export(self):
+        n = self.info()["bytes"]
+        buf = (C.c_uint8 * n)()
+        got = self._L.smr_mp_snapshot_export(self._h, buf, n)
+        if got < 0:
+            check(int(got))
+        return C.string_at(buf, got)
+
+    @classmethod
+    def from_bytes(cls, data, like):
+        """the snapshot an exported image holds; `like`: a cluster of the image's n_groups, population, commit_extra and
+        live mask (its window and capacities do not matter)"""
+        snap = cls(like)
+        data = bytes(data)
+        check(snap._L.smr_mp_snapshot_import(snap._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
+        return snap
+
+
 class MultiPaxosCluster:
     def __init__(self, n_groups, population=5, window=64, win_reserve=None, outbox_cap=None, commit_extra=0,
                  commit_list_cap=0, straggler_ticks=0):
@@ -97,6 +141,12 @@ class MultiPaxosCluster:
     def end_tick(self):
         check(self._L.smr_mp_end_tick(self._h))
 
+    def debug_arena_view(self):
+        """debug / measurement only: (device pointer, bytes) of the one allocation that holds all of the cluster's arrays (`smr_mp_debug_arena_view`)"""
+        p, n = C.c_void_p(), C.c_uint64()
+        check(self._L.smr_mp_debug_arena_view(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def ack_matrix_ptr(self, rep):
         p, n = C.c_void_p(), C.c_uint64()
         check(self._L.smr_mp_ack_matrix(self._h, rep, C.byref(p), C.byref(n)))
@@ -149,6 +199,18 @@ class MultiPaxosCluster:
             setattr(bufs, name, out[name].ctypes.data_as(C.c_void_p))
         check(self._L.smr_mp_dump_range(self._h, rep, int(g0), G, C.byref(bufs)))
         return out
+
+    def save_state(self, snap=None, stream=None):
+        """the whole logical state into a device-resident snapshot (a new one, or `snap` again), between two ticks; one
+        kernel, enqueued on `stream` (`smr_mp_save_state`)"""
+        snap = MpSnapshot(self) if snap is None else snap
+        check(self._L.smr_mp_save_state(self._h, snap._h, stream_ptr(stream)))
+        return snap
+
+    def load_state(self, snap, stream=None):
+        """overwrite the whole logical state with a snapshot's (`smr_mp_load_state`): same n_groups, population, commit_extra
+        and live mask; window, outbox_cap and commit_list_cap at least what the snapshot holds"""
+        check(self._L.smr_mp_load_state(self._h, snap._h, stream_ptr(stream)))
 
     def counters(self, rep):
         arr = (C.c_uint64 * 3)()

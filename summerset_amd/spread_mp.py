@@ -199,6 +199,20 @@ class SpreadMultiPaxos:
         run tick and are the caller's to restore"""
         check(self._L.smr_mp_spread_abort_tick(self._spread))
 
+    def save_state(self, snaps=None, stream=None):
+        """this rank's blocks into snapshots (block -> `MpSnapshot`; `snaps`: the ones of an earlier call, filled again),
+        between two ticks.  What `load_state` takes after an `abort_tick`"""
+        snaps = {} if snaps is None else snaps
+        for b, (cl, _, _, _) in self.blocks.items():
+            snaps[b] = cl.save_state(snaps.get(b), stream=stream)
+        return snaps
+
+    def load_state(self, snaps, stream=None):
+        """the live replicas of this rank's blocks back to what `save_state` saved.  After `abort_tick`: the documented way
+        out of a failed segment or collective -- the tick is then run again as a whole"""
+        for b, (cl, _, _, _) in self.blocks.items():
+            cl.load_state(snaps[b], stream=stream)
+
     def _exchange(self, phase, stream=None):
         self._pack(phase, stream)
         self._collective(phase)
@@ -324,6 +338,17 @@ class in_process:
     def preset_leader(self, rep=0):
         for r in self.ranks:
             r.preset_leader(rep)
+
+    def save_state(self, snaps=None):
+        return [r.save_state(None if snaps is None else snaps[i]) for i, r in enumerate(self.ranks)]
+
+    def load_state(self, snaps):
+        for r, s in zip(self.ranks, snaps):
+            r.load_state(s)
+
+    def abort_tick(self):
+        for r in self.ranks:
+            r.abort_tick()
 
     def tick(self, inputs, heartbeat=False):
         """every rank through a segment before any rank starts the next one -- the order the collectives impose on separate
