@@ -659,6 +659,67 @@ int smr_raft_craft_dump_masks(smr_raft_leader *l, uint8_t *mask_host, uint64_t *
  * bounded memory, shared with the oracle: size `window` so that this stays 0 -- the parity tests assert it. */
 int smr_raft_ring_guard_hits(smr_raft_leader *l, uint64_t *out);
 
+/* Save / load of ONE replica object's whole logical state, between two handler calls, on the device.
+ * replaces: the snapshot file and WAL a replica comes back from (raft/snapshot.rs take_new_snapshot / recover_from_snapshot,
+ *           raft/recovery.rs recover_from_wal, craft/snapshot.rs) inside the crash-restart loop of
+ *           summerset_server/src/main.rs:124-167 -- plus the volatile state that loop rebuilds from nothing and a checkpoint
+ *           must not lose (role, votes, the leader's per-peer indices, CRaft's heartbeat counters and queued Reconstructs).
+ * A Raft replica is an object of its own, so one replica can be taken away and brought back (in this process or, as bytes,
+ * in another) while the other replicas of its cluster go on.
+ * The image carries, per group: role, leader, curr_term, voted_for, votes, log_len, start_slot, last_commit, last_snap,
+ * ring_lo, n_exec, n_trunc; next_slot / try_next_slot / match_slot per peer (the replica's own row zero, as
+ * smr_raft_leader_dump gives it); the term of every LIVE entry -- [max(start_slot, ring_lo, log_len - window), log_len), the
+ * span smr_raft_leader_dump and smr_raft_craft_dump_masks give -- and the eight counters summed over their shards.  CRaft
+ * replicas: also the live entries' shard bitmaps, full_copy, alive, hb_replied / hb_seen / hb_repeat, partial, last_recon and
+ * the Reconstruct queue smr_raft_craft_poll_reconstructs would hand over.  Not carried: ring rows outside the live span (load
+ * leaves them alone; the dumps give zero there) and the CRaft payload store's shard bytes (smr_craft_pstore_*: a restored
+ * replica's store is refilled by follow / Reconstruct as after any restart).
+ *   smr_raft_snapshot_create   room for the worst case of `like` (every ring row live, a full Reconstruct queue), so a save
+ *                              never finds the snapshot too small; a replica with a larger window saved into it later makes
+ *                              it grow in that save call (sizes the host knows: no read-back);
+ *   smr_raft_save_state        one kernel on `stream`, enqueues only.  The snapshot must have been made for the replica's
+ *                              n_groups, population, replica id, commit_extra and variant (SMR_ERR_ARG);
+ *   smr_raft_load_state        the inverse, one kernel: overwrites the replica's whole logical state.  Needs the same
+ *                              n_groups, population, replica id (cfg.leader_id), commit_extra and variant (plain or CRaft
+ *                              with the same fault_tolerance and repeat_threshold) and window >= max_live -- else SMR_ERR_ARG
+ *                              and the replica is untouched.  Synchronises once per save to read the image's header;
+ *   smr_raft_snapshot_info_get synchronises;
+ *   smr_raft_snapshot_export / _import   the image as host bytes (little-endian).  The format is canonical:
+ *                              two replicas that hold the same logical state export the same bytes, whichever calls ran
+ *                              their ticks (handler by handler, smr_raft_cluster_replicate, smr_raft_cluster_tick,
+ *                              smr_raft_leader_run_ticks) and whatever their windows, as long as neither ring has dropped an
+ *                              entry (ring_lo equal).  Once a smaller ring has moved ring_lo the logical states differ (the
+ *                              dumps do too) and so may the bytes.  Import checks everything (SMR_ERR_ARG) and never reads
+ *                              past len.  Export returns the bytes written, < 0 on error (SMR_ERR_ARG: cap below info.bytes);
+ *   smr_raft_cluster_save_state / _load_state   n <= 8 distinct replicas of one device that share n_groups / population /
+ *                              variant, each with its own snapshot, in ONE launch: the images and states of the n single
+ *                              calls.  The replicas are reached through the device copies of their views: the call
+ *                              allocates and copies nothing (a load reads back the headers it has not seen yet). */
+typedef struct smr_raft_snapshot smr_raft_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint64_t n_entries;             /* live entries over all groups */
+    uint64_t n_reconstructs;        /* CRaft: queued Reconstruct slots over all groups */
+    uint32_t n_groups, max_live, max_reconstructs;   /* the longest live span / Reconstruct queue of one group */
+    uint8_t population, replica_id, commit_extra;
+    uint8_t craft;                  /* 0 plain Raft, 1 CRaft */
+    uint8_t fault_tolerance, repeat_threshold, reserved[2];   /* CRaft */
+} smr_raft_snapshot_info;
+int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **out);
+void smr_raft_snapshot_destroy(smr_raft_snapshot *s);
+int smr_raft_save_state(smr_raft_leader *l, smr_raft_snapshot *s, void *stream);
+int smr_raft_load_state(smr_raft_leader *l, const smr_raft_snapshot *s, void *stream);
+int smr_raft_snapshot_info_get(const smr_raft_snapshot *s, smr_raft_snapshot_info *out);
+int64_t smr_raft_snapshot_export(const smr_raft_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t len);
+int smr_raft_cluster_save_state(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, void *stream);
+int smr_raft_cluster_load_state(uint32_t n, smr_raft_leader *const *reps, const smr_raft_snapshot *const *snaps, void *stream);
+/* debug / measurement only: the device allocation that holds the replica's arrays (ring rows dead or alive, counter shards) and,
+ * for a CRaft replica, the block smr_raft_craft_enable added (NULL / 0 otherwise), i.e. what a wholesale copy of the replica's
+ * state would move -- tools/time_raft_snapshot.py times those copies beside smr_raft_save_state.  The layout inside is the
+ * library's own; nothing else may depend on it. */
+int smr_raft_debug_arena_view(smr_raft_leader *l, void **base_dev, uint64_t *n_bytes, void **craft_base_dev, uint64_t *craft_n_bytes);
+
 /* ------------------------------------------------------------------------
  * EPaxos command leader / acceptor over G groups (one replica id per group)
  * replaces: EPaxosReplica::handle_req_batch (epaxos/request.rs:10-108) with

@@ -11,7 +11,7 @@ from ._lib import SummersetError, SMR_CTL_IDENTITY, SMR_NO_REPLICA  # noqa: F401
 from .rscoding import RSCodewordBatch, rs_matrix, rs_shard_len  # noqa: F401
 from .multipaxos import MpSnapshot, MultiPaxosCluster  # noqa: F401
 from .quorumread import KvStateMachine, QuorumReadGroup, StringKvStateMachine  # noqa: F401
-from .raft import CRaftLeaderGroup, RaftLeaderGroup  # noqa: F401
+from .raft import CRaftLeaderGroup, RaftLeaderGroup, RaftSnapshot, load_cluster_state, save_cluster_state  # noqa: F401
 from .epaxos import EPaxosReplicaGroup  # noqa: F401
 from .rspaxos import RSPaxosReplicaGroup  # noqa: F401
 from .rsp_payload import CRaftPayloadStore, RSPaxosPayloadStore, RSPaxosReplicaWithPayload  # noqa: F401

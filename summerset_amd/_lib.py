@@ -60,6 +60,13 @@ class MpGroupState(C.Structure):
                 ("peer_exec_bar", C.c_uint32 * SMR_MAX_REPLICAS)]
 
 
+class RaftSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_entries", C.c_uint64), ("n_reconstructs", C.c_uint64), ("n_groups", C.c_uint32),
+                ("max_live", C.c_uint32), ("max_reconstructs", C.c_uint32), ("population", C.c_uint8), ("replica_id", C.c_uint8),
+                ("commit_extra", C.c_uint8), ("craft", C.c_uint8), ("fault_tolerance", C.c_uint8), ("repeat_threshold", C.c_uint8),
+                ("reserved", C.c_uint8 * 2)]
+
+
 class MpSnapshotInfo(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("n_slots", C.c_uint64), ("n_outbox", C.c_uint64), ("n_groups", C.c_uint32),
                 ("max_live", C.c_uint32), ("max_outbox", C.c_uint32), ("population", C.c_uint8), ("commit_extra", C.c_uint8),
@@ -296,6 +303,16 @@ SYMBOLS = [
     ("smr_raft_craft_handle_reconstruct", _i, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("smr_raft_craft_dump_masks", _i, [_vp, _vp, _vp]),
     ("smr_raft_ring_guard_hits", _i, [_vp, C.POINTER(_u64)]),
+    ("smr_raft_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_raft_snapshot_destroy", None, [_vp]),
+    ("smr_raft_save_state", _i, [_vp, _vp, _vp]),
+    ("smr_raft_load_state", _i, [_vp, _vp, _vp]),
+    ("smr_raft_snapshot_info_get", _i, [_vp, C.POINTER(RaftSnapshotInfo)]),
+    ("smr_raft_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_raft_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_raft_cluster_save_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_raft_cluster_load_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_raft_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_raft_craft_poll_reconstructs", _i, [_vp, _u32, _vp, _vp, _vp, _vp]),
     ("smr_raft_craft_handle_reconstruct_reply", _i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     ("smr_ep_replica_create", _i, [C.POINTER(EpCfg), C.POINTER(_vp)]),

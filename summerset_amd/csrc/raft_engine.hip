@@ -1206,6 +1206,8 @@ __global__ __launch_bounds__(64 * (RMAX + 1)) void raft_cluster_tick_kernel(cons
 
 }  // namespace smr
 
+#include "raft_snapshot.h"
+
 using namespace smr;
 
 struct smr_raft_leader {
@@ -1215,10 +1217,12 @@ struct smr_raft_leader {
     bool craft = false;
     CraftView cv;
     uint8_t *craft_base = nullptr;
+    size_t craft_bytes = 0;
     int device = -1;                 // the device current when the object was created: where its arena is
     unsigned long long *wire_acc = nullptr;   // smr_raft_leader_handle_wire_replies: the counters of the call in flight + blocks done (zero between calls)
     RaftView *d_view = nullptr;      // a device copy of v for smr_raft_cluster_replicate (made on first use; craft_enable changes v)
     bool d_view_ok = false;
+    CraftView *d_cv = nullptr;       // ... and of cv, for the cluster forms of save / load (filled by craft_enable)
 };
 
 namespace smr {
@@ -1287,7 +1291,10 @@ int smr_raft_leader_create(const smr_raft_cfg *cfg, smr_raft_leader **out) {
     if (e == hipSuccess) e = hipMemset(l->wire_acc, 0, RW_ACC_WORDS * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&l->d_view, sizeof(RaftView));
     if (e == hipSuccess) e = hipMemcpy(l->d_view, &l->v, sizeof(RaftView), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&l->d_cv, sizeof(CraftView));
+    if (e == hipSuccess) e = hipMemset(l->d_cv, 0, sizeof(CraftView));
     if (e != hipSuccess) {
+        if (l->d_cv) (void)hipFree(l->d_cv);
         if (l->d_view) (void)hipFree(l->d_view);
         if (l->wire_acc) (void)hipFree(l->wire_acc);
         (void)hipFree(l->arena.base); delete l;
@@ -1303,6 +1310,7 @@ void smr_raft_leader_destroy(smr_raft_leader *l) {
     if (l->arena.base) (void)hipFree(l->arena.base);
     if (l->craft_base) (void)hipFree(l->craft_base);
     if (l->d_view) (void)hipFree(l->d_view);
+    if (l->d_cv) (void)hipFree(l->d_cv);
     if (l->wire_acc) (void)hipFree(l->wire_acc);
     delete l;
 }
@@ -1388,6 +1396,7 @@ int smr_raft_craft_enable(smr_raft_leader *l, uint8_t fault_tolerance, uint8_t r
     const size_t total = 2 * n8 + n1 + 2 * ng + nm + ng + 2 * ng4 + nq4 + nq8;
     SMR_HIP_TRY(hipMalloc((void **)&l->craft_base, total));
     SMR_HIP_TRY(hipMemset(l->craft_base, 0, total));
+    l->craft_bytes = total;
     CraftView &cv = l->cv;
     uint8_t *b = l->craft_base;
     cv.hb_replied = (uint64_t *)b; b += n8; cv.hb_seen = (uint64_t *)b; b += n8;
@@ -1405,6 +1414,7 @@ int smr_raft_craft_enable(smr_raft_leader *l, uint8_t fault_tolerance, uint8_t r
     l->v.thresh = quorum + fault_tolerance;
     l->craft = true;
     SMR_HIP_TRY(hipMemcpy(l->d_view, &l->v, sizeof(RaftView), hipMemcpyHostToDevice));   // (the threshold moved: the view's device copy follows)
+    SMR_HIP_TRY(hipMemcpy(l->d_cv, &l->cv, sizeof(CraftView), hipMemcpyHostToDevice));
     l->d_view_ok = true;
     return SMR_OK;
 }
@@ -1473,7 +1483,7 @@ int smr_raft_leader_dump(smr_raft_leader *l, const smr_raft_dump_bufs *hb) {
         hb->next_slot[(size_t)v.me * G + g] = 0; hb->try_next_slot[(size_t)v.me * G + g] = 0;
         hb->match_slot[(size_t)v.me * G + g] = 0;
         for (size_t w = 0; w < W; w++) hb->entry_term[w * G + g] = 0;
-        uint32_t len = hb->log_len[g], lo = rlo[g] > hb->start_slot[g] ? rlo[g] : hb->start_slot[g];
+        const uint32_t len = hb->log_len[g], lo = raft_live_lo(hb->start_slot[g], rlo[g], len, v.W);   // (raft_snapshot.h: the live span)
         for (uint32_t s = lo; s < len; s++) hb->entry_term[(size_t)(s & (W - 1)) * G + g] = et[(size_t)(s & (W - 1)) * G + g];
     }
     return SMR_OK;
@@ -1578,8 +1588,7 @@ int smr_raft_craft_dump_masks(smr_raft_leader *l, uint8_t *mask_host, uint64_t *
     counters[0] = c[4]; counters[1] = c[5];
     memset(mask_host, 0, W * G);                               // canonical form: only the slots the log (and the ring) holds
     for (size_t g = 0; g < G; g++) {
-        uint32_t end = len[g], lo = end > W ? end - (uint32_t)W : start[g];
-        if (lo < rlo[g]) lo = rlo[g];
+        const uint32_t end = len[g], lo = raft_live_lo(start[g], rlo[g], end, v.W);   // (raft_snapshot.h: the live span)
         for (uint32_t s2 = lo; s2 < end; s2++) mask_host[(size_t)(s2 & (W - 1)) * G + g] = m[(size_t)(s2 & (W - 1)) * G + g];
     }
     return SMR_OK;
@@ -1715,6 +1724,262 @@ int smr_raft_cluster_tick(smr_raft_leader *leader, const uint32_t *n_new_dev, ui
     else { if (leader->craft) RAFT_TICK(true, RMAX); else RAFT_TICK(false, RMAX); }
 #undef RAFT_TICK
     SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+/* ---- save / load of one replica's state on the device (raft_snapshot.h: the image and its two kernels) -------------------------
+ * The crash-restart loop of summerset_server/src/main.rs:124-167 brings a replica back from its snapshot file and WAL
+ * (raft/snapshot.rs, raft/recovery.rs, craft/snapshot.rs); a batched replica object is saved and brought back whole, between
+ * two handler calls, by one kernel each, while the other replicas of its cluster go on. */
+}  // extern "C"
+
+struct smr_raft_snapshot {
+    uint32_t G = 0;
+    uint8_t R = 0, me = 0, commit_extra = 0, craft = 0, ft = 0, rep_thr = 0;
+    int device = -1;
+    uint8_t *dev = nullptr;
+    uint64_t cap_e = 0, cap_rq = 0;                              // records the device buffer's sections have room for
+    bool filled = false, hdr_known = false;                      // a save / import has run; `hdr` is the image's header
+    RaftSnapHdr hdr;
+};
+
+namespace smr {
+static RaftSnapGeom rsnap_geom_of(const smr_raft_snapshot *s) { return rsnap_geom(s->G, s->R, s->craft != 0); }
+static int rsnap_alloc(smr_raft_snapshot *s, uint64_t cap_e, uint64_t cap_rq) {
+    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
+    s->cap_e = cap_e; s->cap_rq = cap_rq;
+    const RaftSnapImg S{nullptr, cap_e, cap_rq};
+    hipError_t e = hipMalloc((void **)&s->dev, rsnap_dev_bytes(rsnap_geom_of(s), S));
+    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("raft snapshot: hipMalloc: ") + hipGetErrorString(e)); }
+    return SMR_OK;
+}
+// room for the worst case of a replica with l's window: every ring row live, a full Reconstruct queue.  A save can then never
+// find the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica
+// with a larger window is saved into it.
+static int rsnap_room(smr_raft_snapshot *s, const smr_raft_leader *l) {
+    const uint64_t ne = (uint64_t)s->G * l->cfg.window, nq = s->craft ? (uint64_t)s->G * CRAFT_RQ : 0;
+    if (s->dev && ne <= s->cap_e && nq <= s->cap_rq) return SMR_OK;
+    s->filled = false; s->hdr_known = false;                     // (what it held goes with the old buffer)
+    return rsnap_alloc(s, ne > s->cap_e ? ne : s->cap_e, nq > s->cap_rq ? nq : s->cap_rq);
+}
+// the image's header on the host (synchronises once after a save)
+static int rsnap_header(smr_raft_snapshot *s) {
+    if (!s->filled) return fail(SMR_ERR_STATE, "raft snapshot: nothing saved or imported yet");
+    if (s->hdr_known) return SMR_OK;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(RaftSnapHdr), hipMemcpyDeviceToHost));
+    // (cannot happen: the kernel's counts are bounded by the window and queue length the room was made for)
+    if (s->hdr.n_entries > s->cap_e || s->hdr.n_rq > s->cap_rq) {
+        s->filled = false;
+        return fail(SMR_ERR_STATE, "raft snapshot: the saved state exceeds the snapshot's room");
+    }
+    s->hdr_known = true;
+    return SMR_OK;
+}
+static bool rsnap_like(const smr_raft_snapshot *s, const smr_raft_leader *l) {
+    return s->G == l->cfg.n_groups && s->R == l->cfg.population && s->me == l->cfg.leader_id && s->commit_extra == l->cfg.commit_extra &&
+           (s->craft != 0) == l->craft && (!l->craft || (s->ft == l->cv.ft && s->rep_thr == l->cv.rep_thr));
+}
+static bool rsnap_hdr_like(const RaftSnapHdr &h, const smr_raft_snapshot *s) {
+    return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.commit_extra == s->commit_extra && h.variant == s->craft &&
+           h.fault_tolerance == s->ft && h.repeat_threshold == s->rep_thr;
+}
+static const char *const RSNAP_OTHER = "another n_groups / population / replica id / commit_extra / variant (plain or CRaft, fault_tolerance, repeat_threshold)";
+
+// the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
+static int rsnap_setup(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, bool load, RaftSnapArgs &A) {
+    if (!reps || !snaps) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    if (n == 0 || n > RMAX) return fail(SMR_ERR_ARG, "raft snapshot: 1 .. 8 replicas");
+    memset(&A, 0, sizeof(A));
+    for (uint32_t k = 0; k < n; k++) {
+        smr_raft_leader *l = reps[k];
+        smr_raft_snapshot *s = snaps[k];
+        if (!l || !s) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+        for (uint32_t j = 0; j < k; j++)
+            if (reps[j] == l || snaps[j] == s) return fail(SMR_ERR_ARG, "raft snapshot: a replica or a snapshot is listed twice");
+        if (l->v.G != reps[0]->v.G || l->v.R != reps[0]->v.R || l->craft != reps[0]->craft)
+            return fail(SMR_ERR_ARG, "raft snapshot: the replicas differ in groups / population / variant");
+        if (l->device != reps[0]->device || s->device != l->device) return fail(SMR_ERR_ARG, "raft snapshot: a replica or snapshot lives on another device");
+        if (!rsnap_like(s, l)) return fail(SMR_ERR_ARG, std::string("raft snapshot: made for ") + RSNAP_OTHER);
+        if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, "raft snapshot: a replica has no device copy of its view");
+    }
+    for (uint32_t k = 0; k < n; k++) {
+        smr_raft_leader *l = reps[k];
+        smr_raft_snapshot *s = snaps[k];
+        if (load) {
+            if (int rc = rsnap_header(s)) return rc;
+            const RaftSnapHdr &h = s->hdr;
+            if (!rsnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("raft snapshot: the image is of ") + RSNAP_OTHER);
+            if (h.max_live > l->cfg.window)
+                return fail(SMR_ERR_ARG, "raft snapshot: a log of " + std::to_string(h.max_live) + " live entries does not fit window " + std::to_string(l->cfg.window));
+        } else if (int rc = rsnap_room(s, l)) return rc;
+    }
+    A.geo = rsnap_geom(reps[0]->v.G, reps[0]->v.R, reps[0]->craft);
+    for (uint32_t k = 0; k < n; k++) {
+        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.img[k] = snaps[k]->dev; A.cap_e[k] = snaps[k]->cap_e; A.cap_rq[k] = snaps[k]->cap_rq;
+        A.commit_extra[k] = reps[k]->cfg.commit_extra;
+    }
+    return SMR_OK;
+}
+}  // namespace smr
+
+extern "C" {
+
+int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    smr_raft_snapshot *s = new smr_raft_snapshot();
+    s->G = like->cfg.n_groups; s->R = like->cfg.population; s->me = like->cfg.leader_id; s->commit_extra = like->cfg.commit_extra;
+    s->craft = like->craft ? 1 : 0; s->ft = like->craft ? (uint8_t)like->cv.ft : 0; s->rep_thr = like->craft ? (uint8_t)like->cv.rep_thr : 0;
+    s->device = like->device;
+    memset(&s->hdr, 0, sizeof(s->hdr));
+    if (int rc = rsnap_room(s, like)) { delete s; return rc; }
+    *out = s;
+    return SMR_OK;
+}
+
+void smr_raft_snapshot_destroy(smr_raft_snapshot *s) {
+    if (!s) return;
+    if (s->dev) { (void)hipDeviceSynchronize(); (void)hipFree(s->dev); }
+    delete s;
+}
+
+int smr_raft_cluster_save_state(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, void *stream) {
+    RaftSnapArgs A;
+    if (int rc = rsnap_setup(n, reps, snaps, false, A)) return rc;
+    hipLaunchKernelGGL(raft_snap_pack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < n; k++) { snaps[k]->filled = true; snaps[k]->hdr_known = false; }
+    return SMR_OK;
+}
+
+int smr_raft_cluster_load_state(uint32_t n, smr_raft_leader *const *reps, const smr_raft_snapshot *const *snaps, void *stream) {
+    RaftSnapArgs A;                                              // (a snapshot's header is read back and cached on first use)
+    if (int rc = rsnap_setup(n, reps, const_cast<smr_raft_snapshot *const *>(snaps), true, A)) return rc;
+    hipLaunchKernelGGL(raft_snap_unpack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_raft_save_state(smr_raft_leader *l, smr_raft_snapshot *s, void *stream) {
+    if (!l || !s) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    return smr_raft_cluster_save_state(1, &l, &s, stream);
+}
+
+int smr_raft_load_state(smr_raft_leader *l, const smr_raft_snapshot *s, void *stream) {
+    if (!l || !s) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    return smr_raft_cluster_load_state(1, &l, &s, stream);
+}
+
+int smr_raft_debug_arena_view(smr_raft_leader *l, void **base_dev, uint64_t *n_bytes, void **craft_base_dev, uint64_t *craft_n_bytes) {
+    if (!l || !base_dev || !n_bytes || !craft_base_dev || !craft_n_bytes) return fail(SMR_ERR_ARG, "raft: null argument");
+    *base_dev = l->arena.base; *n_bytes = l->arena.size;
+    *craft_base_dev = l->craft ? l->craft_base : nullptr; *craft_n_bytes = l->craft ? l->craft_bytes : 0;
+    return SMR_OK;
+}
+
+int smr_raft_snapshot_info_get(const smr_raft_snapshot *cs, smr_raft_snapshot_info *out) {
+    if (!cs || !out) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    smr_raft_snapshot *s = const_cast<smr_raft_snapshot *>(cs);
+    if (int rc = rsnap_header(s)) return rc;
+    const RaftSnapHdr &h = s->hdr;
+    memset(out, 0, sizeof(*out));
+    out->bytes = h.bytes; out->n_entries = h.n_entries; out->n_reconstructs = h.n_rq;
+    out->n_groups = h.n_groups; out->max_live = h.max_live; out->max_reconstructs = h.max_rq;
+    out->population = h.population; out->replica_id = h.me; out->commit_extra = h.commit_extra; out->craft = h.variant;
+    out->fault_tolerance = h.fault_tolerance; out->repeat_threshold = h.repeat_threshold;
+    return SMR_OK;
+}
+
+int64_t smr_raft_snapshot_export(const smr_raft_snapshot *cs, uint8_t *host, uint64_t cap) {
+    if (!cs || !host) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    smr_raft_snapshot *s = const_cast<smr_raft_snapshot *>(cs);
+    if (int rc = rsnap_header(s)) return rc;
+    const RaftSnapHdr &h = s->hdr;
+    if (cap < h.bytes) return fail(SMR_ERR_ARG, "raft snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
+    const RaftSnapGeom q = rsnap_geom_of(s);
+    const RaftSnapImg S{s->dev, s->cap_e, s->cap_rq};
+    uint8_t *p = host;
+    SMR_HIP_TRY(hipMemcpy(p, s->dev, q.fixed, hipMemcpyDeviceToHost)); p += q.fixed;
+    if (h.n_entries) SMR_HIP_TRY(hipMemcpy(p, s->dev + q.fixed, h.n_entries * 8, hipMemcpyDeviceToHost));
+    p += h.n_entries * 8;
+    if (s->craft) {
+        if (h.n_rq) SMR_HIP_TRY(hipMemcpy(p, s->dev + rsnap_off_rq(q, S), h.n_rq * sizeof(RaftSnapRq), hipMemcpyDeviceToHost));
+        p += h.n_rq * sizeof(RaftSnapRq);
+        if (h.n_entries) SMR_HIP_TRY(hipMemcpy(p, s->dev + rsnap_off_mask(q, S), h.n_entries, hipMemcpyDeviceToHost));
+        memset(p + h.n_entries, 0, rsnap_a8(h.n_entries) - h.n_entries);
+    }
+    return (int64_t)h.bytes;
+}
+
+int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t len) {
+    if (!s || !host) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    if (len < sizeof(RaftSnapHdr)) return fail(SMR_ERR_ARG, "raft snapshot: image shorter than its header");
+    RaftSnapHdr h;
+    memcpy(&h, host, sizeof(h));
+    if (h.magic != RSNAP_MAGIC) return fail(SMR_ERR_ARG, "raft snapshot: not a snapshot image (magic)");
+    if (h.version != RSNAP_VERSION)
+        return fail(SMR_ERR_ARG, "raft snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(RSNAP_VERSION));
+    if (h.me >= h.population) return fail(SMR_ERR_ARG, "raft snapshot: the image's replica id is not below its population");
+    bool res = h.reserved1 != 0;
+    for (int k = 0; k < 6; k++) res = res || h.reserved0[k];
+    if (!rsnap_hdr_like(h, s) || res) return fail(SMR_ERR_ARG, std::string("raft snapshot: the image is of ") + RSNAP_OTHER);
+    const RaftSnapGeom q = rsnap_geom_of(s);
+    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed) return fail(SMR_ERR_ARG, "raft snapshot: truncated image");
+    const uint64_t room = h.bytes - q.fixed;                      // the record sections; each count bounded before it is multiplied
+    if (h.n_entries > room / 8 || h.n_rq > room / sizeof(RaftSnapRq) || (!s->craft && h.n_rq) || rsnap_bytes(q, h.n_entries, h.n_rq) != h.bytes)
+        return fail(SMR_ERR_ARG, "raft snapshot: the header's counts do not add up to the image's size");
+    // the body against the header: counts and maxima recomputed from the scalars, ids in range
+    const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("raft snapshot: malformed image: ") + what); };
+    const uint8_t *b = host + q.off_scal, *c = host + q.off_craft;
+    const auto u32at = [](const uint8_t *p, uint64_t i) { uint32_t x; memcpy(&x, p + 4 * i, 4); return x; };
+    uint64_t n_e = 0, n_rq = 0;
+    uint32_t max_live = 0, max_rq = 0;
+    for (uint32_t g = 0; g < s->G; g++) {
+        const uint32_t ln = u32at(b + q.o_len, g), st = u32at(b + q.o_start, g), rlo = u32at(b + q.o_rlo, g);
+        const uint32_t n = raft_live_n(st, rlo, ln, RSNAP_MAX_LOG);
+        if (n > h.max_live) return bad("a group's live span above the header's max_live");
+        if (b[q.o_role + g] > ROLE_LEADER) return bad("role");
+        const uint8_t ld = b[q.o_leader + g], vf = b[q.o_voted + g];
+        if ((ld != NO_REP && ld >= s->R) || (vf != NO_REP && vf >= s->R)) return bad("leader or voted_for not below the population");
+        if (b[q.o_votes + g] >> s->R) return bad("votes of replicas beyond the population");
+        if (u32at(b + q.o_next, (uint64_t)s->me * s->G + g) || u32at(b + q.o_try, (uint64_t)s->me * s->G + g) || u32at(b + q.o_match, (uint64_t)s->me * s->G + g))
+            return bad("the replica's own peer row is not zero");
+        n_e += n; max_live = n > max_live ? n : max_live;
+        if (s->craft) {
+            const uint32_t nq = u32at(c + q.c_rqn, g);
+            if (nq > CRAFT_RQ || nq > h.max_rq) return bad("a group's Reconstruct queue above the header's max_rq");
+            if (c[q.c_alive + g] >> s->R) return bad("alive bits of replicas beyond the population");
+            n_rq += nq; max_rq = nq > max_rq ? nq : max_rq;
+        }
+    }
+    for (uint64_t p = q.scal_end; p < rsnap_a8(q.scal_end); p++) if (b[p]) return bad("padding is not zero");
+    if (s->craft) for (uint64_t p = q.craft_end; p < rsnap_a8(q.craft_end); p++) if (c[p]) return bad("padding is not zero");
+    if (n_e != h.n_entries || n_rq != h.n_rq || max_live != h.max_live || max_rq != h.max_rq) return bad("the header's counts and maxima contradict the body");
+    const uint8_t *p = host + q.fixed + h.n_entries * 8;
+    if (s->craft) {
+        for (uint64_t k = 0; k < h.n_rq; k++, p += sizeof(RaftSnapRq)) {
+            RaftSnapRq e;
+            memcpy(&e, p, sizeof(e));
+            if (e.pad) return bad("Reconstruct queue record");
+        }
+        for (uint64_t k = 0; k < h.n_entries; k++) if (p[k] >> s->R) return bad("shard bitmap of replicas beyond the population");
+        for (uint64_t k = h.n_entries; k < rsnap_a8(h.n_entries); k++) if (p[k]) return bad("padding is not zero");
+    }
+    if (h.n_entries > s->cap_e || h.n_rq > s->cap_rq)
+        if (int rc = rsnap_alloc(s, h.n_entries > s->cap_e ? h.n_entries : s->cap_e, h.n_rq > s->cap_rq ? h.n_rq : s->cap_rq)) return rc;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    s->filled = false;
+    const RaftSnapImg S{s->dev, s->cap_e, s->cap_rq};
+    p = host;
+    SMR_HIP_TRY(hipMemcpy(s->dev, p, q.fixed, hipMemcpyHostToDevice)); p += q.fixed;
+    if (h.n_entries) SMR_HIP_TRY(hipMemcpy(s->dev + q.fixed, p, h.n_entries * 8, hipMemcpyHostToDevice));
+    p += h.n_entries * 8;
+    if (s->craft) {
+        if (h.n_rq) SMR_HIP_TRY(hipMemcpy(s->dev + rsnap_off_rq(q, S), p, h.n_rq * sizeof(RaftSnapRq), hipMemcpyHostToDevice));
+        p += h.n_rq * sizeof(RaftSnapRq);
+        if (h.n_entries) SMR_HIP_TRY(hipMemcpy(s->dev + rsnap_off_mask(q, S), p, h.n_entries, hipMemcpyHostToDevice));
+    }
+    s->hdr = h; s->filled = true; s->hdr_known = true;
     return SMR_OK;
 }
 

@@ -1,0 +1,409 @@
+// Save / load of ONE Raft or CRaft replica object's state on the device: the canonical image and its two kernels.
+// (included by raft_engine.hip behind RaftView / CraftView)
+//
+// A snapshot holds what the replica's next handler call depends on: what the reference writes into and reads back from its
+// snapshot file and WAL (raft/snapshot.rs, raft/recovery.rs recover_from_wal, craft/snapshot.rs) plus the volatile state its
+// crash-restart loop (summerset_server/src/main.rs:124-167) loses and a checkpoint must not -- role, votes, the leader's
+// per-peer indices, the CRaft heartbeat counters and the queued Reconstruct slots.  It is the logical state and nothing of the
+// arena's layout: a replica's window does not show in it as long as its ring has dropped no entry (ring_lo equal); once a
+// smaller ring has moved ring_lo the logical states differ (the dumps do too) and so may the bytes.
+// Not carried: wire_acc (zero between calls), ring rows outside the live span (load leaves them alone, the dumps give zero
+// there) and the CRaft payload store's shard bytes (smr_craft_pstore_*: a restored replica's store is refilled by follow /
+// Reconstruct as after any restart).
+//
+// Image (little-endian; every section starts on a multiple of 8; padding bytes are zero):
+//   RaftSnapHdr                                      64 B
+//   counters u64[8]                                  commits, redirects, rejects, entries sent, reconstruct_data calls, postponed
+//                                                    executions, ring-guard hits, spare -- summed over their 256 shards
+//   scalars, structure-of-arrays over groups         curr_term u64[G]; log_len, start_slot, last_commit, last_snap, ring_lo,
+//                                                    n_exec, n_trunc u32[G]; next_slot, try_next_slot, match_slot u32[R][G]
+//                                                    (row `me` zero); role, leader, voted_for, votes u8[G]; padded to 8
+//   CRaft only                                       hb_replied, hb_seen u64[R][G]; last_recon, rq_n u32[G]; hb_repeat u8[R][G];
+//                                                    full_copy, alive, partial u8[G]; padded to 8
+//   entry_term u64[n_entries]                        tile-major (64 groups), then row k = slot - lo, then group: the groups of
+//                                                    a row that hold a k-th live entry, packed -- a wavefront's stores of a row
+//                                                    are one contiguous piece
+//   CRaft only: RaftSnapRq[n_rq]                     the Reconstruct queue, the same order, row = queue position
+//   CRaft only: entry_mask u8[n_entries]             the order of entry_term; padded to 8
+// ring_lo is stored as what it stands for, max(ring_lo, log_len - W) (raft_live_lo): the image then tells its live spans
+// without the window it came from.  On the device the record sections sit at fixed capacities behind the fixed part; export
+// closes the gaps.
+#pragma once
+#include "smr_common.h"
+
+#ifndef SMR_HD
+#if defined(__HIPCC__)
+#define SMR_HD __host__ __device__ __forceinline__
+#else
+#define SMR_HD inline
+#endif
+#endif
+
+namespace smr {
+
+constexpr uint32_t RSNAP_MAGIC = 0x53465253u;      // "SRFS"
+constexpr uint32_t RSNAP_VERSION = 1;
+constexpr uint32_t RSNAP_MAX_WAVES = 1024;          // wavefronts of a launch per replica; each takes a contiguous piece of the group tiles
+constexpr uint32_t RSNAP_MAX_LOG = 1u << 20;        // no window is larger
+
+struct RaftSnapHdr {
+    uint32_t magic, version;
+    uint32_t n_groups; uint8_t population, me, commit_extra, variant;      // variant: 0 plain Raft, 1 CRaft
+    uint8_t fault_tolerance, repeat_threshold, reserved0[6];
+    uint64_t bytes, n_entries, n_rq;
+    uint32_t max_live, max_rq;
+    uint64_t reserved1;
+};
+struct RaftSnapRq { uint64_t term; uint32_t slot, pad; };
+static_assert(sizeof(RaftSnapHdr) == 64 && sizeof(RaftSnapRq) == 16, "image records");
+
+// ---- the one place that knows which entries of a log are live (shared with smr_raft_leader_dump and
+// smr_raft_craft_dump_masks): [max(start_slot, ring_lo, log_len > W ? log_len - W : 0), log_len), empty when truncation left
+// log_len below it
+SMR_HD uint32_t raft_ring_lo(uint32_t rlo, uint32_t len, uint32_t W) { return (len > W && len - W > rlo) ? len - W : rlo; }
+SMR_HD uint32_t raft_live_lo(uint32_t start, uint32_t rlo, uint32_t len, uint32_t W) {
+    const uint32_t lo = raft_ring_lo(rlo, len, W);
+    return start > lo ? start : lo;
+}
+SMR_HD uint32_t raft_live_n(uint32_t start, uint32_t rlo, uint32_t len, uint32_t W) {
+    const uint32_t lo = raft_live_lo(start, rlo, len, W);
+    return len > lo ? len - lo : 0u;
+}
+
+// ---- where things are in an image ---------------------------------------------------------------------------------------
+struct RaftSnapGeom {
+    uint32_t G, R, craft, ntile, tpw, nwave, nblock;
+    uint64_t off_ctr, off_scal, off_craft, fixed;
+    uint64_t o_term, o_len, o_start, o_commit, o_snap, o_rlo, o_nexec, o_ntrunc, o_next, o_try, o_match, o_role, o_leader, o_voted, o_votes, scal_end;
+    uint64_t c_hbr, c_hbs, c_lrecon, c_rqn, c_hbrep, c_full, c_alive, c_partial, craft_end;
+};
+SMR_HD uint64_t rsnap_a8(uint64_t x) { return (x + 7) & ~(uint64_t)7; }
+SMR_HD RaftSnapGeom rsnap_geom(uint32_t G, uint32_t R, bool craft) {
+    RaftSnapGeom q;
+    q.G = G; q.R = R; q.craft = craft ? 1u : 0u;
+    q.ntile = (G + 63) / 64;
+    q.tpw = (q.ntile + RSNAP_MAX_WAVES - 1) / RSNAP_MAX_WAVES;
+    q.nwave = (q.ntile + q.tpw - 1) / q.tpw;
+    q.nblock = (q.nwave + 3) / 4;
+    const uint64_t g = G, gr = (uint64_t)G * R;
+    q.off_ctr = sizeof(RaftSnapHdr);
+    q.off_scal = q.off_ctr + 8 * 8;
+    q.o_term = 0; q.o_len = 8 * g; q.o_start = 12 * g; q.o_commit = 16 * g; q.o_snap = 20 * g; q.o_rlo = 24 * g; q.o_nexec = 28 * g;
+    q.o_ntrunc = 32 * g; q.o_next = 36 * g; q.o_try = q.o_next + 4 * gr; q.o_match = q.o_try + 4 * gr;
+    q.o_role = q.o_match + 4 * gr; q.o_leader = q.o_role + g; q.o_voted = q.o_leader + g; q.o_votes = q.o_voted + g;
+    q.scal_end = q.o_votes + g;
+    q.off_craft = q.off_scal + rsnap_a8(q.scal_end);
+    q.c_hbr = 0; q.c_hbs = 8 * gr; q.c_lrecon = 16 * gr; q.c_rqn = q.c_lrecon + 4 * g; q.c_hbrep = q.c_rqn + 4 * g;
+    q.c_full = q.c_hbrep + gr; q.c_alive = q.c_full + g; q.c_partial = q.c_alive + g; q.craft_end = q.c_partial + g;
+    q.fixed = q.off_craft + (craft ? rsnap_a8(q.craft_end) : 0);
+    return q;
+}
+// one replica's image on the device: the fixed part, then room for cap_e entry terms, cap_rq queue records, cap_e masks
+struct RaftSnapImg {
+    uint8_t *base;
+    uint64_t cap_e, cap_rq;
+};
+SMR_HD uint64_t rsnap_off_rq(const RaftSnapGeom &q, const RaftSnapImg &S) { return q.fixed + S.cap_e * 8; }
+SMR_HD uint64_t rsnap_off_mask(const RaftSnapGeom &q, const RaftSnapImg &S) { return rsnap_off_rq(q, S) + S.cap_rq * sizeof(RaftSnapRq); }
+SMR_HD uint64_t rsnap_dev_bytes(const RaftSnapGeom &q, const RaftSnapImg &S) { return rsnap_off_mask(q, S) + (q.craft ? rsnap_a8(S.cap_e) : 0); }
+SMR_HD uint64_t rsnap_bytes(const RaftSnapGeom &q, uint64_t n_e, uint64_t n_rq) {
+    return q.fixed + n_e * 8 + (q.craft ? n_rq * sizeof(RaftSnapRq) + rsnap_a8(n_e) : 0);
+}
+
+// the scalar arrays inside an image
+struct RaftSnapScal {
+    uint64_t *term;
+    uint32_t *len, *start, *commit, *snap, *rlo, *nexec, *ntrunc, *next, *tryn, *match;
+    uint8_t *role, *leader, *voted, *votes;
+    uint64_t *hbr, *hbs;
+    uint32_t *lrecon, *rqn;
+    uint8_t *hbrep, *full, *alive, *partial;
+};
+SMR_HD RaftSnapScal rsnap_scal(uint8_t *base, const RaftSnapGeom &q) {
+    uint8_t *b = base + q.off_scal, *c = base + q.off_craft;
+    RaftSnapScal s;
+    s.term = (uint64_t *)(b + q.o_term);
+    s.len = (uint32_t *)(b + q.o_len); s.start = (uint32_t *)(b + q.o_start); s.commit = (uint32_t *)(b + q.o_commit);
+    s.snap = (uint32_t *)(b + q.o_snap); s.rlo = (uint32_t *)(b + q.o_rlo); s.nexec = (uint32_t *)(b + q.o_nexec);
+    s.ntrunc = (uint32_t *)(b + q.o_ntrunc); s.next = (uint32_t *)(b + q.o_next); s.tryn = (uint32_t *)(b + q.o_try);
+    s.match = (uint32_t *)(b + q.o_match);
+    s.role = b + q.o_role; s.leader = b + q.o_leader; s.voted = b + q.o_voted; s.votes = b + q.o_votes;
+    s.hbr = (uint64_t *)(c + q.c_hbr); s.hbs = (uint64_t *)(c + q.c_hbs);
+    s.lrecon = (uint32_t *)(c + q.c_lrecon); s.rqn = (uint32_t *)(c + q.c_rqn);
+    s.hbrep = c + q.c_hbrep; s.full = c + q.c_full; s.alive = c + q.c_alive; s.partial = c + q.c_partial;
+    return s;
+}
+
+// ---- the kernels --------------------------------------------------------------------------------------------------------
+// blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1); the replicas are reached
+// through the device copies of their views, as smr_raft_cluster_replicate's followers are.  Lane = group, a wavefront = a
+// contiguous piece of the 64-group tiles, 4 wavefronts a block.  A record's place follows from the live counts of every group
+// in front of it, by the scheme of mp_snapshot.h: the block sums the groups in front of its own tiles itself
+// (12 to 16 B per group out of the L2: no block waits for another), the wavefront adds the tiles of its block in front of its
+// own, and inside a tile a row's records go to the lanes that hold one, packed (ballot + prefix count).
+struct RaftSnapArgs {
+    const RaftView *rv[RMAX];
+    const CraftView *cv[RMAX];
+    uint8_t *img[RMAX];
+    uint64_t cap_e[RMAX], cap_rq[RMAX];
+    uint8_t commit_extra[RMAX];
+    RaftSnapGeom geo;
+};
+
+__device__ __forceinline__ uint64_t rsnap_wave_sum(uint64_t x) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+__device__ __forceinline__ uint32_t rsnap_wave_max(uint32_t x) {
+    for (int off = 32; off > 0; off >>= 1) { const uint32_t y = __shfl_xor(x, off); x = y > x ? y : x; }
+    return x;
+}
+
+// live entries and queued Reconstruct slots of group g: the replica's own (PACK) or the image's
+template <bool PACK>
+__device__ __forceinline__ void rsnap_count(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, uint32_t g, uint32_t &ne,
+                                            uint32_t &nq) {
+    if (PACK) {
+        ne = raft_live_n(v.start_slot[g], v.ring_lo[g], v.log_len[g], v.W);
+        nq = craft ? cv.rq_n[g] : 0u;
+    } else {
+        ne = raft_live_n(sc.start[g], sc.rlo[g], sc.len[g], RSNAP_MAX_LOG);
+        if (ne > v.W) ne = v.W;                              // (load has refused such an image: max_live <= window)
+        nq = craft ? sc.rqn[g] : 0u;
+    }
+    if (nq > CRAFT_RQ) nq = CRAFT_RQ;
+}
+
+// sums and maxima over the groups [0, g_wave0); g_block0 <= g_wave0 is the same for the whole block
+template <bool PACK>
+__device__ __forceinline__ void rsnap_bases(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, uint32_t g_block0,
+                                            uint32_t g_wave0, uint64_t &be, uint64_t &bq, uint32_t &me_, uint32_t &mq) {
+    __shared__ uint64_t sh_e[4], sh_q[4];
+    __shared__ uint32_t sh_me[4], sh_mq[4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t e = 0, q = 0;
+    uint32_t xe = 0, xq = 0;
+    for (uint32_t g = threadIdx.x; g < g_block0; g += 256) {
+        uint32_t ne, nq;
+        rsnap_count<PACK>(v, cv, craft, sc, g, ne, nq);
+        e += ne; q += nq; xe = ne > xe ? ne : xe; xq = nq > xq ? nq : xq;
+    }
+    e = rsnap_wave_sum(e); q = rsnap_wave_sum(q); xe = rsnap_wave_max(xe); xq = rsnap_wave_max(xq);
+    if (lane == 0) { sh_e[w] = e; sh_q[w] = q; sh_me[w] = xe; sh_mq[w] = xq; }
+    __syncthreads();
+    be = sh_e[0] + sh_e[1] + sh_e[2] + sh_e[3];
+    bq = sh_q[0] + sh_q[1] + sh_q[2] + sh_q[3];
+    me_ = sh_me[0]; mq = sh_mq[0];
+    for (int k = 1; k < 4; k++) { me_ = sh_me[k] > me_ ? sh_me[k] : me_; mq = sh_mq[k] > mq ? sh_mq[k] : mq; }
+    e = 0; q = 0; xe = 0; xq = 0;
+    for (uint32_t g = g_block0 + lane; g < g_wave0; g += 64) {
+        uint32_t ne, nq;
+        rsnap_count<PACK>(v, cv, craft, sc, g, ne, nq);
+        e += ne; q += nq; xe = ne > xe ? ne : xe; xq = nq > xq ? nq : xq;
+    }
+    be += rsnap_wave_sum(e); bq += rsnap_wave_sum(q);
+    xe = rsnap_wave_max(xe); xq = rsnap_wave_max(xq);
+    me_ = xe > me_ ? xe : me_; mq = xq > mq ? xq : mq;
+}
+
+// the replica of this block: views in registers, the image's descriptor
+struct RaftSnapSel {
+    RaftView v;
+    CraftView cv;
+    RaftSnapImg S;
+    uint32_t commit_extra;
+};
+__device__ __forceinline__ RaftSnapSel rsnap_select(const RaftSnapArgs &A) {
+    const RaftView *rvp = nullptr;
+    const CraftView *cvp = nullptr;
+    RaftSnapSel s;
+    s.S.base = nullptr; s.S.cap_e = 0; s.S.cap_rq = 0; s.commit_extra = 0;
+#pragma unroll
+    for (int k = 0; k < (int)RMAX; k++)
+        if (blockIdx.y == (unsigned)k) {
+            rvp = A.rv[k]; cvp = A.cv[k]; s.S.base = A.img[k]; s.S.cap_e = A.cap_e[k]; s.S.cap_rq = A.cap_rq[k]; s.commit_extra = A.commit_extra[k];
+        }
+    s.v = *rvp;                                              // copies in registers
+    if (A.geo.craft) s.cv = *cvp; else s.cv = CraftView{};
+    return s;
+}
+
+__global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
+    const RaftSnapGeom &Q = A.geo;
+    const RaftSnapSel X = rsnap_select(A);
+    const RaftView &v = X.v;
+    const CraftView &cv = X.cv;
+    const RaftSnapImg &S = X.S;
+    const bool craft = Q.craft != 0;
+    const RaftSnapScal sc = rsnap_scal(S.base, Q);
+    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
+    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
+    const uint32_t gb0 = tb0 * 64 < v.G ? tb0 * 64 : v.G, gw0 = t0 * 64 < v.G ? t0 * 64 : v.G;
+    const size_t G = v.G;
+    uint64_t be, bq;
+    uint32_t mx_e, mx_q;
+    rsnap_bases<true>(v, cv, craft, sc, gb0, gw0, be, bq, mx_e, mx_q);
+    uint64_t *const terms = (uint64_t *)(S.base + Q.fixed);
+    RaftSnapRq *const rqs = (RaftSnapRq *)(S.base + rsnap_off_rq(Q, S));
+    uint8_t *const masks = S.base + rsnap_off_mask(Q, S);
+    for (uint32_t t = t0; t < t1; t++) {
+        const uint32_t g = t * 64 + lane;
+        const bool in = g < v.G;
+        uint32_t n = 0, lo = 0, nq = 0;
+        if (in) {
+            const uint32_t len = v.log_len[g], start = v.start_slot[g], rlo = raft_ring_lo(v.ring_lo[g], len, v.W);
+            lo = raft_live_lo(start, rlo, len, v.W); n = len > lo ? len - lo : 0u;
+            sc.term[g] = v.curr_term[g]; sc.len[g] = len; sc.start[g] = start; sc.commit[g] = v.last_commit[g]; sc.snap[g] = v.last_snap[g];
+            sc.rlo[g] = rlo; sc.nexec[g] = v.n_exec[g]; sc.ntrunc[g] = v.n_trunc[g];
+            sc.role[g] = v.role[g]; sc.leader[g] = v.leader[g]; sc.voted[g] = v.voted_for[g]; sc.votes[g] = v.votes[g];
+            for (uint32_t p = 0; p < v.R; p++) {
+                const size_t o = (size_t)p * G + g;
+                const bool peer = p != v.me;
+                sc.next[o] = peer ? v.next_slot[o] : 0u; sc.tryn[o] = peer ? v.try_next_slot[o] : 0u; sc.match[o] = peer ? v.match_slot[o] : 0u;
+            }
+            if (craft) {
+                nq = cv.rq_n[g];
+                if (nq > CRAFT_RQ) nq = CRAFT_RQ;
+                sc.full[g] = cv.full_copy[g]; sc.alive[g] = cv.alive[g]; sc.partial[g] = cv.partial[g];
+                sc.lrecon[g] = cv.last_recon[g]; sc.rqn[g] = nq;
+                for (uint32_t p = 0; p < v.R; p++) {
+                    const size_t o = (size_t)p * G + g;
+                    sc.hbr[o] = cv.hb_replied[o]; sc.hbs[o] = cv.hb_seen[o]; sc.hbrep[o] = cv.hb_repeat[o];
+                }
+            }
+        }
+        const uint32_t maxn = rsnap_wave_max(n), maxq = rsnap_wave_max(nq);
+        mx_e = maxn > mx_e ? maxn : mx_e; mx_q = maxq > mx_q ? maxq : mx_q;
+        for (uint32_t k = 0; k < maxn; k++) {
+            const bool act = k < n;
+            const unsigned long long mask = __ballot(act);
+            if (act) {
+                const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
+                const uint64_t pos = be + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (pos < S.cap_e) {
+                    terms[pos] = v.entry_term[i];
+                    if (craft) masks[pos] = v.entry_mask[i];
+                }
+            }
+            be += (uint64_t)__popcll(mask);
+        }
+        for (uint32_t j = 0; j < maxq; j++) {
+            const bool act = j < nq;
+            const unsigned long long mask = __ballot(act);
+            if (act) {
+                const size_t i = (size_t)j * G + g;
+                RaftSnapRq e;
+                e.term = cv.rq_term[i]; e.slot = cv.rq_slot[i]; e.pad = 0;
+                const uint64_t pos = bq + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (pos < S.cap_rq) rqs[pos] = e;
+            }
+            bq += (uint64_t)__popcll(mask);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) {                   // the counters' shards summed (smr_common.h)
+        unsigned long long x[SMR_CTR_STRIDE];
+        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) x[k] = 0;
+        for (uint32_t sh = lane; sh < SMR_CTR_SHARDS; sh += 64)
+            for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) x[k] += v.counters[(size_t)sh * SMR_CTR_STRIDE + k];
+        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) x[k] = rsnap_wave_sum(x[k]);
+        if (lane == 0)
+            for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) ((uint64_t *)(S.base + Q.off_ctr))[k] = x[k];
+    }
+    if (t0 < Q.ntile && t1 == Q.ntile && lane == 0) {            // the wavefront of the last tile knows the totals
+        RaftSnapHdr h;
+        h.magic = RSNAP_MAGIC; h.version = RSNAP_VERSION;
+        h.n_groups = v.G; h.population = (uint8_t)v.R; h.me = (uint8_t)v.me; h.commit_extra = (uint8_t)X.commit_extra; h.variant = craft ? 1 : 0;
+        h.fault_tolerance = craft ? (uint8_t)cv.ft : (uint8_t)0; h.repeat_threshold = craft ? (uint8_t)cv.rep_thr : (uint8_t)0;
+        for (int k = 0; k < 6; k++) h.reserved0[k] = 0;
+        h.n_entries = be; h.n_rq = bq; h.bytes = rsnap_bytes(Q, be, bq);
+        h.max_live = mx_e; h.max_rq = mx_q; h.reserved1 = 0;
+        *(RaftSnapHdr *)S.base = h;
+        for (uint64_t p = Q.scal_end; p < rsnap_a8(Q.scal_end); p++) S.base[Q.off_scal + p] = 0;       // padding is zero
+        if (craft) {
+            for (uint64_t p = Q.craft_end; p < rsnap_a8(Q.craft_end); p++) S.base[Q.off_craft + p] = 0;
+            for (uint64_t p = be; p < rsnap_a8(be); p++) if (p < rsnap_a8(S.cap_e)) masks[p] = 0;
+        }
+    }
+}
+
+// Load re-establishes: every scalar and peer row (row `me` as smr_raft_leader_create leaves it), the live entries' ring rows,
+// ring_lo for THIS window, the counters as one shard, the whole Reconstruct queue.  Ring rows outside the live span keep
+// what they held: no handler reads them (RaftLane::term_at, the leader's rlo guards) and the dumps give zero there.
+__global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) {
+    const RaftSnapGeom &Q = A.geo;
+    const RaftSnapSel X = rsnap_select(A);
+    const RaftView &v = X.v;
+    const CraftView &cv = X.cv;
+    const RaftSnapImg &S = X.S;
+    const bool craft = Q.craft != 0;
+    const RaftSnapScal sc = rsnap_scal(S.base, Q);
+    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
+    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
+    const uint32_t gb0 = tb0 * 64 < v.G ? tb0 * 64 : v.G, gw0 = t0 * 64 < v.G ? t0 * 64 : v.G;
+    const size_t G = v.G;
+    uint64_t be, bq;
+    uint32_t mx_e, mx_q;
+    rsnap_bases<false>(v, cv, craft, sc, gb0, gw0, be, bq, mx_e, mx_q);
+    const uint64_t *const terms = (const uint64_t *)(S.base + Q.fixed);
+    const RaftSnapRq *const rqs = (const RaftSnapRq *)(S.base + rsnap_off_rq(Q, S));
+    const uint8_t *const masks = S.base + rsnap_off_mask(Q, S);
+    for (uint32_t t = t0; t < t1; t++) {
+        const uint32_t g = t * 64 + lane;
+        const bool in = g < v.G;
+        uint32_t n = 0, lo = 0, nq = 0;
+        if (in) {
+            const uint32_t len = sc.len[g], start = sc.start[g], rlo = sc.rlo[g];
+            lo = raft_live_lo(start, rlo, len, RSNAP_MAX_LOG); n = len > lo ? len - lo : 0u;
+            if (n > v.W) { lo += n - v.W; n = v.W; }              // (refused by the host: max_live <= window)
+            v.curr_term[g] = sc.term[g]; v.log_len[g] = len; v.start_slot[g] = start; v.last_commit[g] = sc.commit[g]; v.last_snap[g] = sc.snap[g];
+            v.ring_lo[g] = raft_ring_lo(rlo, len, v.W); v.n_exec[g] = sc.nexec[g]; v.n_trunc[g] = sc.ntrunc[g];
+            v.role[g] = sc.role[g]; v.leader[g] = sc.leader[g]; v.voted_for[g] = sc.voted[g]; v.votes[g] = sc.votes[g];
+            for (uint32_t p = 0; p < v.R; p++) {
+                const size_t o = (size_t)p * G + g;
+                const bool peer = p != v.me;
+                v.next_slot[o] = peer ? sc.next[o] : 1u; v.try_next_slot[o] = peer ? sc.tryn[o] : 1u; v.match_slot[o] = peer ? sc.match[o] : 0u;
+            }
+            if (craft) {
+                nq = sc.rqn[g];
+                if (nq > CRAFT_RQ) nq = CRAFT_RQ;
+                cv.full_copy[g] = sc.full[g]; cv.alive[g] = sc.alive[g]; cv.partial[g] = sc.partial[g];
+                cv.last_recon[g] = sc.lrecon[g]; cv.rq_n[g] = nq;
+                for (uint32_t p = 0; p < v.R; p++) {
+                    const size_t o = (size_t)p * G + g;
+                    cv.hb_replied[o] = sc.hbr[o]; cv.hb_seen[o] = sc.hbs[o]; cv.hb_repeat[o] = sc.hbrep[o];
+                }
+            }
+        }
+        const uint32_t maxn = rsnap_wave_max(n), maxq = rsnap_wave_max(nq);
+        for (uint32_t k = 0; k < maxn; k++) {
+            const bool act = k < n;
+            const unsigned long long mask = __ballot(act);
+            const uint64_t pos = be + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (act && pos < S.cap_e) {
+                const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
+                v.entry_term[i] = terms[pos];
+                if (craft) v.entry_mask[i] = masks[pos];
+            }
+            be += (uint64_t)__popcll(mask);
+        }
+        for (uint32_t j = 0; j < maxq; j++) {
+            const bool act = j < nq;
+            const unsigned long long mask = __ballot(act);
+            const uint64_t pos = bq + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+            if (act && pos < S.cap_rq) {
+                const size_t i = (size_t)j * G + g;
+                const RaftSnapRq e = rqs[pos];
+                cv.rq_term[i] = e.term; cv.rq_slot[i] = e.slot;
+            }
+            bq += (uint64_t)__popcll(mask);
+        }
+    }
+    static_assert(SMR_CTR_SHARDS == 256, "one thread of block 0 per counter shard");
+    if (blockIdx.x == 0)                                         // the sums into shard 0, the other shards zero
+        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++)
+            v.counters[(size_t)threadIdx.x * SMR_CTR_STRIDE + k] = threadIdx.x == 0 ? ((const uint64_t *)(S.base + Q.off_ctr))[k] : 0ull;
+}
+
+}  // namespace smr

@@ -21,6 +21,70 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+class RaftSnapshot:
+    """One replica object's state between two handler calls, held on the device (`smr_raft_snapshot`): what
+    `RaftLeaderGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
+    two replicas that hold the same logical state -- and `import_` takes one back."""
+
+    def __init__(self, like):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        check(self._L.smr_raft_snapshot_create(like._h, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.smr_raft_snapshot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def info(self):
+        """sizes of what was saved (synchronises): bytes, n_entries, n_reconstructs, n_groups, max_live, max_reconstructs,
+        population, replica_id, commit_extra, craft, fault_tolerance, repeat_threshold"""
+        st = _lib.RaftSnapshotInfo()
+        check(self._L.smr_raft_snapshot_info_get(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
+
+    def export(self):
+        n = self.info()["bytes"]
+        buf = (C.c_uint8 * n)()
+        got = self._L.smr_raft_snapshot_export(self._h, buf, n)
+        if got < 0:
+            check(int(got))
+        return C.string_at(buf, got)
+
+    def import_(self, data):
+        """take an exported image (of a replica like the one this snapshot was made for; its window does not matter)"""
+        data = bytes(data)
+        check(self._L.smr_raft_snapshot_import(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
+        return self
+
+
+def save_cluster_state(reps, snaps=None, stream=None):
+    """`reps[k].save_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch
+    (`smr_raft_cluster_save_state`); returns the snapshots (new ones without `snaps`)"""
+    snaps = [RaftSnapshot(r) for r in reps] if snaps is None else list(snaps)
+    n = len(reps)
+    if len(snaps) != n:
+        raise ValueError("save_cluster_state: %d replicas, %d snapshots" % (n, len(snaps)))
+    L = _lib.load()
+    check(L.smr_raft_cluster_save_state(n, (C.c_void_p * n)(*[r._h for r in reps]), (C.c_void_p * len(snaps))(*[s._h for s in snaps]),
+                                        stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_state(reps, snaps, stream=None):
+    """`reps[k].load_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch (`smr_raft_cluster_load_state`)"""
+    n = len(reps)
+    if len(snaps) != n:
+        raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (n, len(snaps)))
+    L = _lib.load()
+    check(L.smr_raft_cluster_load_state(n, (C.c_void_p * n)(*[r._h for r in reps]), (C.c_void_p * len(snaps))(*[s._h for s in snaps]),
+                                        stream_ptr(stream)))
+
+
 class RaftLeaderGroup:
     def __init__(self, n_groups, population=5, leader_id=0, window=64, term=1, commit_extra=0):
         self.G, self.R, self.W, self.me = int(n_groups), int(population), int(window), int(leader_id)
@@ -147,6 +211,25 @@ class RaftLeaderGroup:
         n = C.c_uint64()
         check(self._L.smr_raft_leader_total_commits(self._h, C.byref(n)))
         return int(n.value)
+
+    def save_state(self, snap=None, stream=None):
+        """my whole logical state into a device-resident snapshot (a new one, or `snap` again), between two handler calls; one
+        kernel on `stream`, nothing read back (`smr_raft_save_state`)"""
+        snap = RaftSnapshot(self) if snap is None else snap
+        check(self._L.smr_raft_save_state(self._h, snap._h, stream_ptr(stream)))
+        return snap
+
+    def load_state(self, snap, stream=None):
+        """overwrite my whole logical state with a snapshot's (`smr_raft_load_state`): same n_groups, population, replica id,
+        commit_extra and variant; window at least the snapshot's max_live"""
+        check(self._L.smr_raft_load_state(self._h, snap._h, stream_ptr(stream)))
+
+    def debug_arena_view(self):
+        """debug / measurement only: [(device pointer, bytes)] of the allocations that hold my arrays -- the arena and, for a CRaft
+        replica, the variant's block (`smr_raft_debug_arena_view`)"""
+        p, n, cp, cn = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        check(self._L.smr_raft_debug_arena_view(self._h, C.byref(p), C.byref(n), C.byref(cp), C.byref(cn)))
+        return [(p.value, int(n.value))] + ([(cp.value, int(cn.value))] if cn.value else [])
 
     # ---- follower side and elections (device tensors, one entry per group) ----
     def preset(self, role, leader, term, voted_for=0xFF):
