@@ -124,12 +124,27 @@ int smr_rs_encode_lut(const uint8_t *data_dev, uint64_t data_len, uint64_t cw_st
  * pattern.  shards_dev: shard k of codeword i at i*cw_stride + k*shard_stride,
  * shard_len bytes each, k in [0, d+p).  present_mask bit k = shard k valid.
  * data_only != 0 rebuilds data shards only (reconstruct_data).  Returns
- * SMR_ERR_ARG when fewer than d shards are present. */
+ * SMR_ERR_ARG when fewer than d shards are present.
+ *
+ * Layout: no two shards may share a byte.  Accepted are
+ *   shard_stride >= shard_len and cw_stride >= (d+p-1)*shard_stride + shard_len   (codeword buffers, packed or padded), or
+ *   cw_stride >= shard_len and shard_stride >= (n_cw-1)*cw_stride + shard_len     (shard-major stores);
+ * n_cw <= 1 asks for shard_stride >= shard_len only.  Anything else, a NULL shards_dev, and more codewords than one launch
+ * holds (ceil(shard_len / 16) * n_cw > 0xFFFFFF * 256) are SMR_ERR_ARG with nothing launched and nothing written.
+ *
+ * Bounds: with span = (n_cw-1)*cw_stride + (d+p-1)*shard_stride + shard_len, every access lies in
+ * [shards_dev, shards_dev + span) -- no byte before the first shard or behind the last one is touched, whatever the
+ * alignment of shards_dev and of shard_len.  WRITTEN are exactly the bytes of the shards rebuilt (missing, and data if
+ * data_only).  READ are the first d present shards; the last partial 16-byte column of such a shard may be fetched as one
+ * whole load where that stays inside the span, so up to 15 bytes behind a shard (a gap, or the neighbouring shard) can be
+ * loaded -- they never reach a result. */
 int smr_rs_reconstruct(uint8_t *shards_dev, uint64_t shard_len, uint64_t shard_stride,
                        uint64_t cw_stride, uint64_t n_cw, int d, int p, uint32_t present_mask,
                        int data_only, void *stream);
 
-/* verify_parity for n_cw codewords; ok_dev[i] = 1 if parity matches. */
+/* verify_parity for n_cw codewords; ok_dev[i] = 1 if parity matches, 0 if not.  Layout rule, refusals and read bounds as
+ * smr_rs_reconstruct (NULL ok_dev refused too): reads stay inside [shards_dev, shards_dev + span), the only bytes written
+ * are ok_dev[0 .. n_cw), and a refused call leaves ok_dev as it was. */
 int smr_rs_verify(const uint8_t *shards_dev, uint64_t shard_len, uint64_t shard_stride,
                   uint64_t cw_stride, uint64_t n_cw, int d, int p, uint8_t *ok_dev, void *stream);
 

@@ -439,6 +439,15 @@ static int rs_encode_impl(const uint8_t *data, uint64_t data_len, uint64_t cw_st
     return rs_launch<LUT>(a, (hipStream_t)stream);
 }
 
+// The layouts smr_rs_reconstruct / smr_rs_verify take: no two shards of the batch may share a byte.  Either the shards of a
+// codeword lie inside its cw_stride (a codeword buffer), or the codewords of a shard lie inside its shard_stride (shard-major
+// stores, the rule of smr_rs_from_data_encode_stores).  One codeword has no cw_stride to speak of.
+static bool rs_layout_ok(uint64_t shard_len, uint64_t shard_stride, uint64_t cw_stride, uint64_t n_cw, int t) {
+    if (n_cw <= 1) return shard_stride >= shard_len;
+    if (shard_stride >= shard_len && cw_stride >= (uint64_t)(t - 1) * shard_stride + shard_len) return true;
+    return cw_stride >= shard_len && shard_stride >= (n_cw - 1) * cw_stride + shard_len;
+}
+
 }  // namespace smr
 
 using namespace smr;
@@ -522,6 +531,8 @@ int smr_rs_reconstruct(uint8_t *shards_dev, uint64_t shard_len, uint64_t shard_s
                        uint64_t n_cw, int d, int p, uint32_t present_mask, int data_only, void *stream) {
     if (d <= 0 || d > RS_MAX_IN || p < 0 || p > RS_MAX_OUT) return fail(SMR_ERR_ARG, "rs: bad scheme");
     if (shard_len == 0) return fail(SMR_ERR_ARG, "codeword is null");
+    if (!shards_dev) return fail(SMR_ERR_ARG, "rs: null buffer");
+    if (!rs_layout_ok(shard_len, shard_stride, cw_stride, n_cw, d + p)) return fail(SMR_ERR_ARG, "rs: shard layout overlaps itself");
     int t = d + p, have = 0;
     for (int k = 0; k < t; k++) have += (present_mask >> k) & 1;
     if (have < d) return fail(SMR_ERR_ARG, "too few shards present");
@@ -538,8 +549,11 @@ int smr_rs_reconstruct(uint8_t *shards_dev, uint64_t shard_len, uint64_t shard_s
     RsArgs a = {};
     a.in_base = shards_dev; a.out_base = shards_dev;
     a.in_cw_stride = cw_stride; a.out_cw_stride = cw_stride;
-    a.shard_len = shard_len; a.in_valid = ~0ull >> 1; a.n_cw = n_cw; a.n_in = d;
-    a.in_bytes = n_cw ? (n_cw - 1) * cw_stride + (uint64_t)(t - 1) * shard_stride + shard_len : 0;
+    a.shard_len = shard_len; a.n_cw = n_cw; a.n_in = d;
+    // a codeword's bytes end with its last shard, the batch's with the last codeword's: a shard's last partial block is a whole
+    // 16-byte load only where that stays below both (load_cols), so nothing is read at or beyond in_base + in_bytes
+    a.in_valid = (uint64_t)(t - 1) * shard_stride + shard_len;
+    a.in_bytes = n_cw ? (n_cw - 1) * cw_stride + a.in_valid : 0;
     for (int c = 0; c < d; c++) a.in_off[c] = (uint64_t)src[c] * shard_stride;
     int n_out = 0;
     for (int k = 0; k < t; k++) {
@@ -566,16 +580,21 @@ int smr_rs_verify(const uint8_t *shards_dev, uint64_t shard_len, uint64_t shard_
                   uint64_t n_cw, int d, int p, uint8_t *ok_dev, void *stream) {
     if (d <= 0 || d > RS_MAX_IN || p < 0 || p > RS_MAX_OUT) return fail(SMR_ERR_ARG, "rs: bad scheme");
     if (shard_len == 0) return fail(SMR_ERR_ARG, "codeword is null");
+    if (!shards_dev || !ok_dev) return fail(SMR_ERR_ARG, "rs: null buffer");
+    if (!rs_layout_ok(shard_len, shard_stride, cw_stride, n_cw, d + p)) return fail(SMR_ERR_ARG, "rs: shard layout overlaps itself");
+    const uint64_t nblk = (shard_len + 15) / 16;
+    if (p && nblk && n_cw > (0xFFFFFFull * 256) / nblk) return fail(SMR_ERR_ARG, "rs: too many codewords for one launch");
     hipStream_t st = (hipStream_t)stream;
-    SMR_HIP_TRY(hipMemsetAsync(ok_dev, 1, n_cw, st));
+    SMR_HIP_TRY(hipMemsetAsync(ok_dev, 1, n_cw, st));              // (behind every check: a refused call writes nothing)
     if (p == 0 || n_cw == 0) return SMR_OK;
     uint8_t m[(RS_MAX_IN + RS_MAX_OUT) * RS_MAX_IN];
     if (!rs_build_matrix(d, p, m)) return fail(SMR_ERR_ARG, "rs: cannot build coding matrix");
     RsArgs a = {};
     a.in_base = shards_dev; a.out_base = const_cast<uint8_t *>(shards_dev);
     a.in_cw_stride = cw_stride; a.out_cw_stride = cw_stride;
-    a.shard_len = shard_len; a.in_valid = ~0ull >> 1; a.n_cw = n_cw; a.n_in = d; a.n_out = p;
-    a.in_bytes = n_cw ? (n_cw - 1) * cw_stride + (uint64_t)(d + p - 1) * shard_stride + shard_len : 0;
+    a.shard_len = shard_len; a.n_cw = n_cw; a.n_in = d; a.n_out = p;
+    a.in_valid = (uint64_t)(d + p - 1) * shard_stride + shard_len;     // as in smr_rs_reconstruct: no read at or beyond in_base + in_bytes
+    a.in_bytes = n_cw ? (n_cw - 1) * cw_stride + a.in_valid : 0;
     for (int c = 0; c < d; c++) a.in_off[c] = (uint64_t)c * shard_stride;
     for (int r = 0; r < p; r++) {
         a.out_off[r] = (uint64_t)(d + r) * shard_stride;
@@ -584,7 +603,6 @@ int smr_rs_verify(const uint8_t *shards_dev, uint64_t shard_len, uint64_t shard_
     rs_finish_args(a);
     uint64_t blocks = (a.n_cw * a.nblk + 255) / 256;
     dim3 grid((unsigned)blocks), block(256);
-    if (blocks > 0xFFFFFFull) return fail(SMR_ERR_ARG, "rs: too many codewords for one launch");
     RS_DISPATCH(rs_verify_xtime, a, grid, block, 0, st, a, ok_dev);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;

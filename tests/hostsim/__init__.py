@@ -185,3 +185,51 @@ def patched(defines=()):
     finally:
         for o, n, v in saved:
             setattr(o, n, v)
+
+
+class RedZoneHits:
+    """what `red_zones` hands back: `count` kernel accesses ran into a poisoned range, `first` is the first one's text"""
+    count, first = 0, ""
+
+
+def _extent(a):
+    """(address, bytes) of a contiguous torch CPU tensor or numpy array"""
+    if hasattr(a, "data_ptr"):
+        assert a.device.type == "cpu" and a.is_contiguous()
+        return int(a.data_ptr()), int(a.numel() * a.element_size())
+    assert a.flags["C_CONTIGUOUS"]
+    return int(a.ctypes.data), int(a.nbytes)
+
+
+@contextlib.contextmanager
+def red_zones(buf, lo, hi, *more):
+    """Inside the block, the kernels may touch bytes [lo, hi) of `buf` (a contiguous torch CPU tensor or numpy array) and nothing
+    else of it: the rest of the array is poisoned (hipsim_redzone_add), in recording mode -- a kernel access into it is counted
+    and goes on (the memory is the array's own) instead of aborting the test process.  `more`: further (buf, lo, hi) triples of
+    the same call.  Yields a RedZoneHits that is filled in on the way out; the ranges are lifted and recording is switched off
+    whatever happened inside, since a range left behind would abort a later test whose buffer lands on the same address."""
+    lib = C.CDLL(build())
+    lib.hipsim_redzone_add.argtypes, lib.hipsim_redzone_add.restype = [C.c_void_p, C.c_size_t], None
+    lib.hipsim_redzone_remove.argtypes, lib.hipsim_redzone_remove.restype = [C.c_void_p], None
+    lib.hipsim_redzone_record.argtypes, lib.hipsim_redzone_record.restype = [C.c_int], None
+    lib.hipsim_redzone_hits.argtypes, lib.hipsim_redzone_hits.restype = [C.c_char_p, C.c_size_t, C.c_int], C.c_ulong
+    windows = [(buf, lo, hi)] + list(more)
+    hits, zones = RedZoneHits(), []
+    try:
+        for a, l, h in windows:
+            base, size = _extent(a)
+            assert 0 <= l <= h <= size, (l, h, size)
+            for start, n in ((base, l), (base + h, size - h)):
+                if n:
+                    lib.hipsim_redzone_add(start, n)
+                    zones.append(start)
+        lib.hipsim_redzone_hits(None, 0, 1)
+        lib.hipsim_redzone_record(1)
+        yield hits
+    finally:
+        lib.hipsim_redzone_record(0)
+        for start in zones:
+            lib.hipsim_redzone_remove(start)
+        text = C.create_string_buffer(512)
+        hits.count = int(lib.hipsim_redzone_hits(text, len(text), 1))
+        hits.first = text.value.decode("utf-8", "replace")

@@ -52,10 +52,18 @@ void *dyn_shared();
 /* memory no kernel may touch (the gaps -DSMR_ARENA_GUARD leaves between the arrays of an arena); a kernel
  * access into one aborts with the access site.  dev_free lifts the marks inside the freed block. */
 void poison(const void *p, size_t n);
+void unpoison(const void *p);                /* lifts the range that starts at p */
 void *dev_malloc(size_t n);
 void dev_free(void *p);
 }  // namespace hipsim
 extern "C" unsigned long hipsim_partial_wave_ops(void);   /* wave operations that met with live lanes elsewhere */
+extern "C" void hipsim_traffic(unsigned long long *out, int reset);   /* bytes loaded, bytes stored, loads, stores of the kernels */
+/* red zones of a test's own: poison [p, p + n) / lift the range that starts at p; recording on: a hit is counted and the access
+ * goes on (default: abort); hits: the count, the first hit's text into first[cap], reset != 0 forgets both */
+extern "C" void hipsim_redzone_add(const void *p, size_t n);
+extern "C" void hipsim_redzone_remove(const void *p);
+extern "C" void hipsim_redzone_record(int on);
+extern "C" unsigned long hipsim_redzone_hits(char *first, size_t cap, int reset);
 
 typedef void *hipStream_t;
 typedef void *hipEvent_t;

@@ -231,6 +231,9 @@ std::map<uintptr_t, uintptr_t> poisoned;          // start -> end
 std::vector<std::pair<uintptr_t, uintptr_t>> poison_flat;
 bool poison_dirty;
 std::map<uintptr_t, size_t> blocks;               // hipMalloc'd blocks
+bool poison_record;                               // count the hits and let the access go on (hipsim_redzone_record) instead of aborting
+unsigned long poison_hits;
+std::string poison_first;                         // the first recorded hit, in the words of the abort
 
 // A lane is about to touch memory that is not its own stack (the library is compiled with
 // -fsanitize=thread only to get this call in front of every such load and store): it parks, and goes on
@@ -252,10 +255,15 @@ void before_access(const void *addr, size_t size, int is_store, const void *site
         }
         auto it = std::upper_bound(poison_flat.begin(), poison_flat.end(), std::make_pair(a + size - 1, ~(uintptr_t)0));
         if (it != poison_flat.begin() && (--it)->second > a) {
-            fprintf(stderr, "hipsim: kernel access of %zu bytes at %p runs into an arena guard gap [%p, %p): site +0x%lx, block (%u,%u) "
-                    "thread %u\n", size, addr, (void *)it->first, (void *)it->second, (unsigned long)((uintptr_t)site - lib_base),
-                    blockIdx.x, blockIdx.y, threadIdx.x);
-            abort();
+            char msg[320];
+            snprintf(msg, sizeof(msg), "hipsim: kernel %s of %zu bytes at %p runs into an arena guard gap [%p, %p): site +0x%lx, block (%u,%u) "
+                     "thread %u", is_store ? "store" : "load", size, addr, (void *)it->first, (void *)it->second,
+                     (unsigned long)((uintptr_t)site - lib_base), blockIdx.x, blockIdx.y, threadIdx.x);
+            if (!poison_record) {
+                fprintf(stderr, "%s\n", msg);
+                abort();
+            }
+            if (!poison_hits++) poison_first = msg;               // the memory is real: the access goes on
         }
     }
     Fiber &f = F[cur];
@@ -268,6 +276,7 @@ void before_access(const void *addr, size_t size, int is_store, const void *site
 void *dyn_shared() { return dyn.data(); }
 
 void poison(const void *p, size_t n) { if (n) { poisoned[(uintptr_t)p] = (uintptr_t)p + n; poison_dirty = true; } }
+void unpoison(const void *p) { if (poisoned.erase((uintptr_t)p)) poison_dirty = true; }
 void *dev_malloc(size_t n) {
     void *p = malloc(n ? n : 1);
     if (p) blocks[(uintptr_t)p] = n;
@@ -318,6 +327,19 @@ extern "C" unsigned long hipsim_partial_wave_ops(void) { return hipsim::partial_
 extern "C" void hipsim_traffic(unsigned long long *out, int reset) {
     out[0] = hipsim::mem_bytes[0]; out[1] = hipsim::mem_bytes[1]; out[2] = hipsim::mem_ops[0]; out[3] = hipsim::mem_ops[1];
     if (reset) hipsim::mem_bytes[0] = hipsim::mem_bytes[1] = hipsim::mem_ops[0] = hipsim::mem_ops[1] = 0;
+}
+// Red zones a test puts around a buffer of its own: [p, p + n) joins the ranges no kernel may touch (hipsim::poison), and
+// hipsim_redzone_remove(p) lifts the range that starts at p.  With recording on, a hit is counted, the first one's text is kept
+// and the access goes on; off (the default), a hit aborts.  hipsim_redzone_hits returns the count and copies the first hit's
+// text (NUL-terminated, cut to cap) into first; reset != 0 forgets both.
+extern "C" void hipsim_redzone_add(const void *p, size_t n) { hipsim::poison(p, n); }
+extern "C" void hipsim_redzone_remove(const void *p) { hipsim::unpoison(p); }
+extern "C" void hipsim_redzone_record(int on) { hipsim::poison_record = on != 0; }
+extern "C" unsigned long hipsim_redzone_hits(char *first, size_t cap, int reset) {
+    const unsigned long n = hipsim::poison_hits;
+    if (first && cap) snprintf(first, cap, "%s", hipsim::poison_first.c_str());
+    if (reset) { hipsim::poison_hits = 0; hipsim::poison_first.clear(); }
+    return n;
 }
 
 // the -fsanitize=thread hooks (no ThreadSanitizer runtime is linked; these are all there is)

@@ -1,5 +1,6 @@
 // tests/hostsim/selftest.cpp -- what the emulation promises, checked on tiny kernels (built and run by
-// tests/test_hostsim.py with the same flags as the library).  `selftest guard` must die on the guard gap.
+// tests/test_hostsim.py with the same flags as the library).  `selftest guard` must die on the guard gap; with recording on
+// the same access is counted and goes on.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -101,6 +102,25 @@ int main(int argc, char **argv) {
             for (unsigned i = 0; i <= (t & 7u); i++) want += 64 - 8 * i;
             if (out[t] != want) { printf("loop: lane %u got %u want %u\n", t, out[t], want); bad++; break; }
         }
+    }
+    {
+        // a red zone in recording mode: the hit is counted, its text kept, the kernel finishes (the memory is real); once the
+        // range is removed the same launch hits nothing
+        static unsigned a[64 + 64];
+        char first[256];
+        memset(a, 0, sizeof(a));
+        hipsim_redzone_add(a + 64, 64 * 4);
+        hipsim_redzone_record(1);
+        hipLaunchKernelGGL(k_oob, dim3(1), dim3(64), 0, 0, a, 62u);      // threads 2..63 land in the zone
+        unsigned long hits = hipsim_redzone_hits(first, sizeof(first), 1);
+        bool ok = hits == 62 && strstr(first, "arena guard gap") && strstr(first, "store of 4 bytes") && strstr(first, "thread 2");
+        for (unsigned i = 62; i < 126; i++) ok = ok && a[i] == 1;
+        ok = ok && hipsim_redzone_hits(first, sizeof(first), 0) == 0 && first[0] == 0;
+        hipsim_redzone_remove(a + 64);
+        hipLaunchKernelGGL(k_oob, dim3(1), dim3(64), 0, 0, a, 62u);
+        ok = ok && hipsim_redzone_hits(nullptr, 0, 1) == 0;
+        hipsim_redzone_record(0);
+        if (!ok) { printf("red zone: %lu hits, first \"%s\"\n", hits, first); bad++; }
     }
     printf(bad ? "FAILED\n" : "ok\n");
     return bad ? 1 : 0;

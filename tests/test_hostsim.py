@@ -296,7 +296,7 @@ def test_rs_kernels_on_the_host(sim, oracle):
             t.test_golden_vectors("cpu", oracle, lut)
         for L in (1, 2, 3, 5, 16, 31, 48, 97, 1000, 4099, 4113):
             t.test_encode_matches_oracle_ragged("cpu", oracle, L)
-        for scheme in ((3, 2), (6, 4), (12, 8), (5, 5), (4, 1), (1, 1)):
+        for scheme in ((3, 2), (6, 4), (9, 6), (12, 8), (5, 5), (4, 1), (1, 1)):
             t.test_other_schemes("cpu", oracle, scheme)
         t.test_all_erasure_patterns_rs32("cpu", oracle)
         t.test_error_cases_mirror_reference("cpu")
@@ -307,6 +307,14 @@ def test_rs_kernels_on_the_host(sim, oracle):
         for scheme, L in (((3, 2), 1), ((3, 2), 2), ((3, 2), 47), ((3, 2), 4099), ((6, 4), 777), ((1, 1), 33), ((12, 8), 1000), ((3, 0), 100)):
             t.test_from_data_and_encode_one_pass("cpu", oracle, scheme, L)
         t.test_from_data_and_encode_fans_the_shards_out("cpu", oracle)
+        # tests/rs_cases.py (tests/test_rs_bounds.py runs all of it inside red zones): the widest instances and the edge of every
+        # bucket once more here, bytes only -- every layout, every size of erasure pattern
+        import rs_cases as c
+        c.matrix_matches_oracle(oracle)
+        for d, p in ((1, 8), (4, 4), (5, 5), (8, 3), (13, 3), (16, 1), (16, 8)):
+            for layout in c.LAYOUTS:
+                c.one_case("cpu", oracle, c.no_zones, d, p, 33 * d + 5, layout)
+        c.error_paths("cpu", oracle, c.no_zones)
 
 
 def test_rspaxos_kernels_on_the_host(sim, oracle):

@@ -179,7 +179,9 @@ def test_coding_matrix_against_an_independent_restatement(oracle):
                     a[r] = [x ^ mul(f, y) for x, y in zip(a[r], a[c])]
         return [row[n:] for row in a]
 
-    for d, p in [(3, 2), (2, 1), (4, 2), (5, 5), (6, 4), (10, 4), (12, 8), (17, 3)]:
+    # (the second row: the schemes of tests/rs_cases.py, whose matrices the RS kernels are held to; (17, 3): the oracle has no cap on d)
+    for d, p in [(3, 2), (2, 1), (4, 2), (5, 5), (6, 4), (10, 4), (12, 8), (17, 3),
+                 (1, 1), (1, 8), (2, 8), (4, 4), (8, 3), (8, 8), (9, 6), (13, 3), (16, 1), (16, 8)]:
         v = [[power(r, c) for c in range(d)] for r in range(d + p)]
         top = invert(v[:d])
         want = [[0] * d for _ in range(d + p)]
