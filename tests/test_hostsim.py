@@ -342,6 +342,41 @@ def test_rspaxos_device_steady_loop_on_the_host(sim, oracle):
         t.test_one_launch_cluster_argument_errors("cpu")
 
 
+# ---- tests/test_zzzz_rsp_edges_gpu.py, small: RSPaxos beyond five replicas, leader 0 and 32-bit ballots (tests/rsp_edges.py) ----
+def test_rspaxos_edges_engine_on_the_host(sim, oracle):
+    """other populations through the handler calls, ballots across 2^32, leader changes past the ring, the steady tick (call by
+    call and as one launch) at other populations and leaders and from a wide ballot"""
+    import rsp_edges as e
+    with sim.patched():
+        e.run_populations("cpu", oracle, 3, 1, G=70)
+        e.run_populations("cpu", oracle, 8, 3, G=70)
+        e.run_random_calls("cpu", oracle, 8, 7, 3, G=70, steps=60)
+        e.run_wide_ballots("cpu", oracle, 2**24 - 2, 5, 1, 16, G=70)
+        e.run_wide_ballots("cpu", oracle, 2**24 - 2, 3, 0, 8, G=70)
+        e.run_random_calls("cpu", oracle, 5, 2, 1, G=70, steps=60, round0=2**24 - 1)
+        e.run_past_the_ring("cpu", oracle, 5, 1, G=66, seed=2)
+        for R, leader, ft in ((5, 3, 1), (3, 2, 1), (8, 7, 1)):
+            for one_launch in (True, False):
+                e.run_steady_case("cpu", oracle, R, leader, ft, 65, one_launch)
+        for one_launch in (True, False):
+            e.run_steady_case("cpu", oracle, 5, 3, 1, 65, one_launch, round0=2**24 - 1)
+            e.run_steady_case("cpu", oracle, 8, 7, 1, 65, one_launch, round0=2**55 - 1)
+
+
+def test_rspaxos_edges_payload_stores_on_the_host(sim, oracle):
+    """the payload stores behind three and eight replicas, every (n, d) scheme of the put kernels, the creation errors"""
+    import rsp_edges as e
+    with sim.patched():
+        e.run_payload_closed_loop("cpu", oracle, 3, 0, 133)
+        e.run_payload_closed_loop("cpu", oracle, 8, 1, 333)
+        for n, d in e.MAJORITY_SCHEMES + e.OTHER_SCHEMES:
+            for L in e.SWEEP_LENGTHS:
+                e.run_scheme_sweep("cpu", oracle, n, d, L)
+        e.run_craft_stores("cpu", oracle, 3, False)                              # the CRaft stores behind three / seven replicas
+        e.run_craft_stores("cpu", oracle, 7, "one_call")
+        e.creation_errors("cpu")
+
+
 def test_spread_rspaxos_exchange_on_the_host(sim, oracle):
     """layout L2 of the RSPaxos engine with every rank in this process (tests/test_spread_rsp.py): against the co-located steady loop"""
     import test_spread_rsp as t

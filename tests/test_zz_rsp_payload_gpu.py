@@ -106,10 +106,9 @@ def check_executed(rep, dev, exp, where):
     return len(g)
 
 
-def run_closed_loop(dev, oracle, G, W, ft, loss, L, T=21, staging=False):
+def run_closed_loop(dev, oracle, G, W, ft, loss, L, T=21, staging=False, R=5):
     import rsp_scenarios as sc
     from summerset_amd import rsp_payload as rp
-    R = 5
     reps, engs = make_cluster(dev, G, R, W, ft, L, staging)
     exp = Expect(oracle, R, R // 2 + 1, L)
     n_exec = [0]

@@ -49,14 +49,13 @@ def run_schedule_matches_oracle(dev, oracle, G, W, ft, loss, T, seed):
     return stats, ev
 
 
-def run_three_arms(dev, oracle, monkeypatch, G, W, ft, loss, L, T, seed, arms=("A", "B", "C")):
-    """see the module's docstring; `arms`: which of A, B, C run (B always).  Returns what the run covered."""
+def run_three_arms(dev, oracle, monkeypatch, G, W, ft, loss, L, T, seed, arms=("A", "B", "C"), R=5):
+    """see the module's docstring; `arms`: which of A, B, C run (B always); R: the population.  Returns what the run covered."""
     import rsp_one_call as oc
     import test_zz_rsp_payload_gpu as tp
     from test_craft_payload import _stores_equal
     from summerset_amd.rsp_payload import REQS, VOTED, RSPaxosPayloadStore
     assert "B" in arms
-    R = 5
     monkeypatch.delenv("SMR_PS_DELIVER", raising=False)
     exp = tp.Expect(oracle, R, R // 2 + 1, L)
     orcs = [oracle.RspOracle(G, R, me=r, W=W, fault_tolerance=ft) for r in range(R)]
