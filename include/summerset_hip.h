@@ -1091,6 +1091,66 @@ int smr_rsp_dump(smr_rsp_replica *e, const smr_rsp_dump_bufs *host_bufs);
  * many; the first `cap` are written (NULL host arrays: count only).  The next handler call starts a new list. */
 int smr_rsp_exec_poll(smr_rsp_replica *e, uint32_t *group_host, uint32_t *slot_host, uint32_t *val_host, uint64_t cap, uint64_t *n_out);
 
+/* Save / load of ONE replica object's whole logical state, between two handler calls, on the device.
+ * replaces: the snapshot file and WAL a replica comes back from (rspaxos/snapshot.rs, rspaxos/recovery.rs) inside the
+ *           crash-restart loop of summerset_server/src/main.rs:124-167 -- plus the volatile state that loop rebuilds from nothing
+ *           and a checkpoint must not lose (ballots, the leader's and the replica's bookkeeping of every live instance, the
+ *           peers' exec bars, the executed commands the host has not polled yet).
+ * An RSPaxos replica is an object of its own, so one replica can be taken away and brought back (in this process or, as bytes,
+ * in another) while the other replicas of its cluster go on.
+ * The image carries, per group: leader, bal_prep_sent, bal_prepared, bal_max_seen, len, commit_bar, exec_bar, snap_bar,
+ * peer_exec_bar per peer, digest; every LIVE instance -- [len > window ? len - window : 0, len), the span smr_rsp_dump gives --
+ * as a 56-byte record in smr_rsp_dump's canonical form (bookkeeping fields only where the instance has that bookkeeping); the
+ * execution list smr_rsp_exec_poll would hand over; the four counters summed over their shards.  Not carried: ring cells
+ * outside the live span (load leaves them alone; the dump gives null instances there) and the payload store's shard bytes
+ * (smr_rsp_pstore_*).
+ * Save and load are defined BETWEEN two handler calls / ticks of the replica.  A caller inside an open smr_rsp_spread tick
+ * (smr_rsp_spread_segment without the tick's last segment) closes it or calls smr_rsp_spread_abort_tick first: the replica
+ * cannot see the spread object, and a half-run tick's messages are not part of the image.
+ *   smr_rsp_snapshot_create    room for the worst case of `like` (every ring row live, a full execution list), so a save never
+ *                              finds the snapshot too small; a replica with a larger window saved into it later makes it grow
+ *                              in that save call (sizes the host knows: no read-back);
+ *   smr_rsp_save_state         one kernel on `stream`, enqueues only.  The snapshot must have been made for the replica's
+ *                              n_groups, population, replica id and fault_tolerance (SMR_ERR_ARG);
+ *   smr_rsp_load_state         the inverse, one kernel: overwrites the replica's whole logical state.  Needs the same n_groups,
+ *                              population, replica id, fault_tolerance AND window -- else SMR_ERR_ARG and the replica is
+ *                              untouched.  (The engine holds a slot iff slot + window >= len; in another ring the cells around
+ *                              the saved span would count as held or as lost.)  Synchronises once per save to read the header;
+ *   smr_rsp_snapshot_info_get  synchronises;
+ *   smr_rsp_snapshot_export / _import   the image as host bytes (little-endian).  The format is canonical: two
+ *                              replicas that hold the same logical state export the same bytes, whichever calls ran their
+ *                              ticks (handler by handler, smr_rsp_cluster_steady_tick).  Import checks the FORMAT -- sizes,
+ *                              counts against the scalars, padding, ids and masks in range, canonical bookkeeping fields
+ *                              (SMR_ERR_ARG) -- and never reads past len; it does not ask that the state is one a run of the
+ *                              protocol reaches (commit_bar against len, an executed slot against exec_bar): such an image
+ *                              loads as written, within bounds.  Export returns the bytes written, < 0 on error
+ *                              (SMR_ERR_ARG: cap below info.bytes);
+ *   smr_rsp_cluster_save_state / _load_state   n <= 8 distinct replicas that share n_groups / population, each with its own
+ *                              snapshot, in ONE launch: the images and states of the n single calls.  The replicas' views
+ *                              travel in the launch's arguments: the call allocates and copies nothing (a load reads back the
+ *                              headers it has not seen yet). */
+typedef struct smr_rsp_snapshot smr_rsp_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint64_t n_slots;               /* live instances over all groups */
+    uint64_t n_exec;                /* unpolled executed commands over all groups */
+    uint32_t n_groups, window, max_live, max_exec;   /* the longest live span / execution list of one group */
+    uint8_t population, replica_id, fault_tolerance, reserved[5];
+} smr_rsp_snapshot_info;
+int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out);
+void smr_rsp_snapshot_destroy(smr_rsp_snapshot *s);
+int smr_rsp_save_state(smr_rsp_replica *e, smr_rsp_snapshot *s, void *stream);
+int smr_rsp_load_state(smr_rsp_replica *e, const smr_rsp_snapshot *s, void *stream);
+int smr_rsp_snapshot_info_get(const smr_rsp_snapshot *s, smr_rsp_snapshot_info *out);
+int64_t smr_rsp_snapshot_export(const smr_rsp_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t len);
+int smr_rsp_cluster_save_state(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, void *stream);
+int smr_rsp_cluster_load_state(uint32_t n, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *snaps, void *stream);
+/* debug / measurement only: the device allocation that holds the replica's arrays (ring rows dead or alive, counter shards), i.e.
+ * what a wholesale copy of the replica's state would move -- tools/time_rsp_snapshot.py times that copy beside
+ * smr_rsp_save_state.  The layout inside is the library's own; nothing else may depend on it. */
+int smr_rsp_debug_arena_view(smr_rsp_replica *e, void **base_dev, uint64_t *n_bytes);
+
 /* ------------------------------------------------------------------------
  * RSPaxos payload store: the shard BYTES behind a replica's instances, resident in HBM, keyed by (slot, shard) --
  * `inst.reqs_cw` and the voted copy `inst.voted.1` (rspaxos/mod.rs:168-233) as two planes (0 = reqs, 1 = voted), each a
@@ -1188,6 +1248,50 @@ int smr_rsp_pstore_counters(smr_rsp_pstore *s, uint64_t *out4_host);
 /* of `copied`: the shards a sender's put launch wrote straight into this store (smr_*_pstore_put_follow_all, below: a follower's
  * steady-tick copy out of the leader's row is done by the launch that has the leader's bytes in registers); 0 with SMR_PS_DELIVER=0 */
 int smr_rsp_pstore_debug_delivered(smr_rsp_pstore *s, uint64_t *out_host);
+
+/* Save / load of ONE payload store's state, between two calls on the store (in the sense of the one-stream rule above), on the device.
+ * One implementation serves both kinds: the two-plane RSPaxos store and the one-plane CRaft store of smr_craft_pstore_create; the
+ * image records which, and a load into the other kind is refused.
+ * replaces: what rspaxos/snapshot.rs + recovery.rs (craft/snapshot.rs) bring back of `inst.reqs_cw` / `inst.voted.1` / a log
+ *           entry's codeword inside the crash-restart loop of summerset_server/src/main.rs:124-167 -- here the shard bytes.
+ * The store is keyed by ring row plus token, so the image is too.  It carries, for every plane the store has, the cell headers as
+ * smr_rsp_pstore_dump gives them (tok, dlen, avail; where tok is null the rest is zero); the VOTED plane's alias bytes
+ * (smr_rsp_pstore_voted_alias: observable state, carried, not re-derived); the bytes of every shard that is present and not an
+ * alias -- ceil(dlen / d) bytes each, zero-padded to 16; an aliased vote's bytes are carried once, in the REQS cell -- and the five
+ * counters (copied, rebuilt, unsatisfied, rekeyed, delivered).  The image is independent of max_data_len, of the planes' strides
+ * and of the store's allocations.  Not state, never read and never written: the work list of smr_rsp_pstore_follow, the GF table,
+ * row bytes behind a shard's length.
+ *   smr_rsp_pstore_snapshot_create   room for the worst case of `like` (every cell holding every shard at max_data_len: the
+ *                              planes' own size), so a save never finds it too small; a store with a larger max_data_len saved
+ *                              into it later makes it grow in that save call;
+ *   smr_rsp_pstore_save        two launches on `stream` (headers and offsets, then bytes), enqueues only, touches only what is live;
+ *   smr_rsp_pstore_load        the inverse: overwrites every header, the alias array, the present shards' bytes and the counters.
+ *                              Needs the same n_groups, n_shards, n_data_shards, window and kind, and max_data_len >= the image's
+ *                              max_dlen -- else SMR_ERR_ARG and the store is untouched.  A store with a larger max_data_len
+ *                              (other strides) loads the image and behaves identically afterwards;
+ *   smr_rsp_pstore_snapshot_export / _import   the image as host bytes, canonical: two stores with the same
+ *                              content export the same bytes whatever their max_data_len.  Import checks everything
+ *                              (SMR_ERR_ARG) and never reads past len. */
+typedef struct smr_rsp_pstore_snapshot smr_rsp_pstore_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint64_t n_cells;               /* cells that hold a token, over the planes */
+    uint64_t n_shards_stored;       /* shards whose bytes the image carries (present and not an alias) */
+    uint64_t shard_bytes;           /* of them, padded to 16 each */
+    uint32_t n_groups, window, max_dlen;
+    uint8_t n_shards, n_data_shards, planes, craft;
+} smr_rsp_pstore_snapshot_info;
+int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_snapshot **out);
+void smr_rsp_pstore_snapshot_destroy(smr_rsp_pstore_snapshot *s);
+int smr_rsp_pstore_save(smr_rsp_pstore *s, smr_rsp_pstore_snapshot *snap, void *stream);
+int smr_rsp_pstore_load(smr_rsp_pstore *s, const smr_rsp_pstore_snapshot *snap, void *stream);
+int smr_rsp_pstore_snapshot_info_get(const smr_rsp_pstore_snapshot *s, smr_rsp_pstore_snapshot_info *out);
+int64_t smr_rsp_pstore_snapshot_export(const smr_rsp_pstore_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *host, uint64_t len);
+/* debug / measurement only: the store's three device allocations (headers and lists, REQS plane, VOTED plane -- 0 bytes for a
+ * CRaft store), i.e. what a wholesale copy of the store would move -- tools/time_rsp_snapshot.py times those copies beside
+ * smr_rsp_pstore_save.  The layout inside is the library's own; nothing else may depend on it. */
+int smr_rsp_pstore_debug_allocs(smr_rsp_pstore *s, void **base_dev3, uint64_t *n_bytes3);
 
 /* CRaft: the same store keyed by LOG INDEX -- the shard bytes of `LogEntry::reqs_cw` (/root/reference/src/protocols/craft/mod.rs:129-150)
  * behind a CRaft replica (smr_raft_leader with smr_raft_craft_enable: leader or follower).  The engine keeps an entry's codeword as

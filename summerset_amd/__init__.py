@@ -13,8 +13,8 @@ from .multipaxos import MpSnapshot, MultiPaxosCluster  # noqa: F401
 from .quorumread import KvStateMachine, QuorumReadGroup, StringKvStateMachine  # noqa: F401
 from .raft import CRaftLeaderGroup, RaftLeaderGroup, RaftSnapshot, load_cluster_state, save_cluster_state  # noqa: F401
 from .epaxos import EPaxosReplicaGroup  # noqa: F401
-from .rspaxos import RSPaxosReplicaGroup  # noqa: F401
-from .rsp_payload import CRaftPayloadStore, RSPaxosPayloadStore, RSPaxosReplicaWithPayload  # noqa: F401
+from .rspaxos import RSPaxosReplicaGroup, RSPaxosSnapshot  # noqa: F401
+from .rsp_payload import CRaftPayloadStore, PayloadStoreSnapshot, RSPaxosPayloadStore, RSPaxosReplicaWithPayload  # noqa: F401
 from .repnothing import RepNothingReplica  # noqa: F401
 from .heartbeater import Heartbeater  # noqa: F401
 from .leaseman import LeaseManager  # noqa: F401

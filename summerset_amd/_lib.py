@@ -67,6 +67,18 @@ class RaftSnapshotInfo(C.Structure):
                 ("reserved", C.c_uint8 * 2)]
 
 
+class RspSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_slots", C.c_uint64), ("n_exec", C.c_uint64), ("n_groups", C.c_uint32), ("window", C.c_uint32),
+                ("max_live", C.c_uint32), ("max_exec", C.c_uint32), ("population", C.c_uint8), ("replica_id", C.c_uint8),
+                ("fault_tolerance", C.c_uint8), ("reserved", C.c_uint8 * 5)]
+
+
+class PstoreSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_cells", C.c_uint64), ("n_shards_stored", C.c_uint64), ("shard_bytes", C.c_uint64),
+                ("n_groups", C.c_uint32), ("window", C.c_uint32), ("max_dlen", C.c_uint32), ("n_shards", C.c_uint8),
+                ("n_data_shards", C.c_uint8), ("planes", C.c_uint8), ("craft", C.c_uint8)]
+
+
 class MpSnapshotInfo(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("n_slots", C.c_uint64), ("n_outbox", C.c_uint64), ("n_groups", C.c_uint32),
                 ("max_live", C.c_uint32), ("max_outbox", C.c_uint32), ("population", C.c_uint8), ("commit_extra", C.c_uint8),
@@ -373,6 +385,16 @@ SYMBOLS = [
     ("smr_rsp_bcast_heartbeat", _i, [_vp, _vp, C.POINTER(RspHeartbeat), _vp]),
     ("smr_rsp_dump", _i, [_vp, C.POINTER(RspDumpBufs)]),
     ("smr_rsp_exec_poll", _i, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    ("smr_rsp_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_rsp_snapshot_destroy", None, [_vp]),
+    ("smr_rsp_save_state", _i, [_vp, _vp, _vp]),
+    ("smr_rsp_load_state", _i, [_vp, _vp, _vp]),
+    ("smr_rsp_snapshot_info_get", _i, [_vp, C.POINTER(RspSnapshotInfo)]),
+    ("smr_rsp_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_rsp_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_rsp_cluster_save_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_rsp_cluster_load_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_rsp_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_rsp_pstore_create", _i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("smr_rsp_pstore_destroy", None, [_vp]),
     ("smr_rsp_pstore_put", _i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp]),
@@ -389,6 +411,14 @@ SYMBOLS = [
     ("smr_rsp_pstore_voted_alias", _i, [_vp, C.POINTER(_vp), _vp]),
     ("smr_rsp_pstore_counters", _i, [_vp, _vp]),
     ("smr_rsp_pstore_debug_delivered", _i, [_vp, _vp]),
+    ("smr_rsp_pstore_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_rsp_pstore_snapshot_destroy", None, [_vp]),
+    ("smr_rsp_pstore_save", _i, [_vp, _vp, _vp]),
+    ("smr_rsp_pstore_load", _i, [_vp, _vp, _vp]),
+    ("smr_rsp_pstore_snapshot_info_get", _i, [_vp, C.POINTER(PstoreSnapshotInfo)]),
+    ("smr_rsp_pstore_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_rsp_pstore_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_rsp_pstore_debug_allocs", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_craft_pstore_create", _i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("smr_craft_pstore_put", _i, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp]),
     ("smr_craft_pstore_follow", _i, [_vp, _vp, _u32, _vp, _vp, _vp]),

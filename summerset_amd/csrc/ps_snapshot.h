@@ -1,0 +1,307 @@
+// Save / load of ONE payload store's state on the device -- the two-plane RSPaxos store and the one-plane CRaft store alike: the
+// canonical image and its kernels.  (included by rsp_payload.hip behind PsView)
+//
+// The store is keyed by ring row plus token (it does not know slots), so the image is keyed by ring row too.  It carries the
+// cell headers of every plane the store has, the VOTED plane's alias bytes (observable: a put / ingest into a REQS row takes the
+// aliased votes with it, so they are carried, not re-derived), the bytes of every shard that is present and not an alias, and the
+// five counters.  It is independent of max_data_len / cap_sl, of the planes' strides and of the store's three allocations.
+// Not state, never read and never written: the work list (it_*, flip), dlv (zero between calls), the GF table, row bytes behind
+// a shard's length.
+//
+// Image (little-endian; every section starts on a multiple of 8, the shard bytes on a multiple of 16; padding bytes are zero):
+//   PsSnapHdr                                        64 B
+//   counters u64[5]                                  copied, rebuilt, unsatisfied, rekeyed, delivered -- summed over their shards
+//   per plane p < planes: tok u32[W][G], dlen u32[W][G], avail u8[W][G]   each array padded to 8; where tok is null the rest is zero
+//   planes == 2: alias u8[W][G]                      the VOTED cells' shards that live in the REQS row; padded to 8; then zero
+//                                                    bytes up to a multiple of 16
+//   shard bytes                                      tile-major (64 groups), then plane, ring row, group, and of a cell every shard
+//                                                    that is present and not an alias, ascending: ceil(dlen / d) bytes each, zero-
+//                                                    padded to a multiple of 16 (the pad is written as zeros, never copied from
+//                                                    the row).  An aliased shard's bytes are carried once, in the REQS cell.
+// The image is dense: the device buffer holds exactly the exported bytes.
+#pragma once
+#include "smr_common.h"
+
+#ifndef SMR_HD
+#if defined(__HIPCC__)
+#define SMR_HD __host__ __device__ __forceinline__
+#else
+#define SMR_HD inline
+#endif
+#endif
+
+namespace smr {
+
+constexpr uint32_t PSSNAP_MAGIC = 0x42505253u;      // "SRPB"
+constexpr uint32_t PSSNAP_VERSION = 1;
+constexpr uint32_t PSSNAP_MAX_WAVES = 1024;          // wavefronts of the header launch; each takes a contiguous piece of the group tiles
+constexpr uint32_t PSSNAP_BYTE_BLOCKS = 2048;        // of the byte launch (a grid-stride loop over (cell, shard), a wavefront each)
+
+struct PsSnapHdr {
+    uint32_t magic, version, n_groups, window;
+    uint8_t n_shards, n_data_shards, planes, craft;
+    uint32_t max_dlen;
+    uint64_t bytes, n_cells, n_shards_stored, shard_bytes, reserved;
+};
+static_assert(sizeof(PsSnapHdr) == 64, "image header");
+
+SMR_HD uint64_t pssnap_a8(uint64_t x) { return (x + 7) & ~(uint64_t)7; }
+SMR_HD uint64_t pssnap_a16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
+// the one place that knows what a cell contributes to the shard section: its shards that are present and not aliases, each
+// ceil(dlen / d) bytes padded to 16 (shared by the kernels and the import's checks)
+SMR_HD uint32_t pssnap_shard_len(uint32_t dlen, uint32_t d) { return (dlen + d - 1) / d; }
+SMR_HD uint32_t pssnap_stored(uint32_t avail, uint32_t alias) { return avail & ~alias & 0xFFu; }
+SMR_HD uint64_t pssnap_cell_bytes(uint32_t stored, uint32_t dlen, uint32_t d) {
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < 8; k++) n += (stored >> k) & 1u;
+    return (uint64_t)n * pssnap_a16(pssnap_shard_len(dlen, d));
+}
+
+struct PsSnapGeom {
+    uint32_t G, W, planes, ntile, tpw, nwave, nblock;
+    uint64_t cells, off_ctr, o_tok[2], o_dlen[2], o_avail[2], o_alias, hdr_end, fixed;
+};
+SMR_HD PsSnapGeom pssnap_geom(uint32_t G, uint32_t W, uint32_t planes) {
+    PsSnapGeom q;
+    q.G = G; q.W = W; q.planes = planes;
+    q.ntile = (G + 63) / 64;
+    q.tpw = (q.ntile + PSSNAP_MAX_WAVES - 1) / PSSNAP_MAX_WAVES;
+    q.nwave = (q.ntile + q.tpw - 1) / q.tpw;
+    q.nblock = (q.nwave + 3) / 4;
+    q.cells = (uint64_t)G * W;
+    q.off_ctr = sizeof(PsSnapHdr);
+    uint64_t off = q.off_ctr + 5 * 8;
+    for (uint32_t p = 0; p < 2; p++) {
+        q.o_tok[p] = off; if (p < planes) off += pssnap_a8(4 * q.cells);
+        q.o_dlen[p] = off; if (p < planes) off += pssnap_a8(4 * q.cells);
+        q.o_avail[p] = off; if (p < planes) off += pssnap_a8(q.cells);
+    }
+    q.o_alias = off; if (planes == 2) off += pssnap_a8(q.cells);
+    q.hdr_end = off;
+    q.fixed = pssnap_a16(off);
+    return q;
+}
+
+// ---- the kernels --------------------------------------------------------------------------------------------------------
+// Two launches each way, no host read-back between them.
+//   (1) ps_snap_head: lane = group, a wavefront = a contiguous piece of the 64-group tiles, 4 wavefronts a block, by the scheme of
+//       mp_snapshot.h: the block sums the byte totals of the groups in front of its own tiles itself (no block
+//       waits for another), the wavefront adds the tiles of its block in front of its own; inside a tile, per (plane, row), a
+//       prefix over the 64 lanes gives every cell the offset of its first stored shard (cell_off, a scratch array of the snapshot,
+//       not part of the image).  The same pass moves the cell headers (canonical) and, from the last tile, writes the image header.
+//   (2) ps_snap_bytes: shaped like ps_bytes_kernel -- one wavefront per (cell, shard), one lane per 16-byte column, 16-byte loads
+//       and stores on both sides; every byte offset is 64-bit.
+struct PsSnapArgs {
+    PsView v;
+    uint8_t *img;
+    uint64_t *cell_off;      // [planes][W][G]
+    uint64_t cap_bytes;      // room of the shard section
+    uint32_t craft;
+    PsSnapGeom geo;
+};
+
+__device__ __forceinline__ uint64_t pssnap_wave_sum(uint64_t x) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+__device__ __forceinline__ uint32_t pssnap_wave_max(uint32_t x) {
+    for (int off = 32; off > 0; off >>= 1) { const uint32_t y = __shfl_xor(x, off); x = y > x ? y : x; }
+    return x;
+}
+
+struct PsSnapCell { uint32_t tok, dlen, avail, alias; };
+// cell i of plane P: the store's own, canonical (PACK), or the image's
+template <bool PACK, int P>
+__device__ __forceinline__ PsSnapCell pssnap_cell(const PsSnapArgs &A, size_t i) {
+    PsSnapCell c;
+    if (PACK) {
+        const PsPlane &pl = A.v.pl[P];
+        c.tok = pl.tok[i];
+        const bool some = c.tok != PS_NULL;
+        c.dlen = some ? pl.dlen[i] : 0u; c.avail = some ? (uint32_t)pl.avail[i] : 0u;
+        c.alias = (P == 1 && some && pl.alias) ? ((uint32_t)pl.alias[i] & c.avail) : 0u;
+    } else {
+        const uint8_t *b = A.img;
+        c.tok = ((const uint32_t *)(b + A.geo.o_tok[P]))[i]; c.dlen = ((const uint32_t *)(b + A.geo.o_dlen[P]))[i];
+        c.avail = b[A.geo.o_avail[P] + i]; c.alias = P == 1 ? (uint32_t)b[A.geo.o_alias + i] : 0u;
+    }
+    return c;
+}
+struct PsSnapSums { uint64_t bytes, cells, shards; uint32_t max_dlen; };
+template <bool PACK, int P>
+__device__ __forceinline__ void pssnap_add_group(const PsSnapArgs &A, uint32_t g, PsSnapSums &s) {
+    for (uint32_t r = 0; r < A.geo.W; r++) {
+        const PsSnapCell c = pssnap_cell<PACK, P>(A, (size_t)r * A.geo.G + g);
+        const uint32_t st = pssnap_stored(c.avail, c.alias);
+        s.bytes += pssnap_cell_bytes(st, c.dlen, A.v.d);
+        s.cells += c.tok != PS_NULL ? 1u : 0u; s.shards += (uint32_t)__popc(st);
+        s.max_dlen = c.dlen > s.max_dlen ? c.dlen : s.max_dlen;
+    }
+}
+template <bool PACK>
+__device__ __forceinline__ void pssnap_add_groups(const PsSnapArgs &A, uint32_t g0, uint32_t g1, uint32_t step, PsSnapSums &s) {
+    for (uint32_t g = g0; g < g1; g += step) {
+        pssnap_add_group<PACK, 0>(A, g, s);
+        if (A.geo.planes == 2) pssnap_add_group<PACK, 1>(A, g, s);
+    }
+}
+__device__ __forceinline__ void pssnap_wave_reduce(PsSnapSums &s) {
+    s.bytes = pssnap_wave_sum(s.bytes); s.cells = pssnap_wave_sum(s.cells); s.shards = pssnap_wave_sum(s.shards); s.max_dlen = pssnap_wave_max(s.max_dlen);
+}
+// sums over the groups [0, g_wave0); g_block0 <= g_wave0 is the same for the whole block
+template <bool PACK>
+__device__ __forceinline__ PsSnapSums pssnap_bases(const PsSnapArgs &A, uint32_t g_block0, uint32_t g_wave0) {
+    __shared__ uint64_t sh_b[4], sh_c[4], sh_s[4];
+    __shared__ uint32_t sh_m[4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    PsSnapSums s{0, 0, 0, 0};
+    pssnap_add_groups<PACK>(A, threadIdx.x, g_block0, 256, s);
+    pssnap_wave_reduce(s);
+    if (lane == 0) { sh_b[w] = s.bytes; sh_c[w] = s.cells; sh_s[w] = s.shards; sh_m[w] = s.max_dlen; }
+    __syncthreads();
+    PsSnapSums t{sh_b[0] + sh_b[1] + sh_b[2] + sh_b[3], sh_c[0] + sh_c[1] + sh_c[2] + sh_c[3], sh_s[0] + sh_s[1] + sh_s[2] + sh_s[3], sh_m[0]};
+    for (int k = 1; k < 4; k++) t.max_dlen = sh_m[k] > t.max_dlen ? sh_m[k] : t.max_dlen;
+    PsSnapSums u{0, 0, 0, 0};
+    pssnap_add_groups<PACK>(A, g_block0 + lane, g_wave0, 64, u);
+    pssnap_wave_reduce(u);
+    t.bytes += u.bytes; t.cells += u.cells; t.shards += u.shards; t.max_dlen = u.max_dlen > t.max_dlen ? u.max_dlen : t.max_dlen;
+    return t;
+}
+
+// one (plane, row) of a tile: the headers across, the cells' offsets from a prefix over the lanes
+template <bool PACK, int P>
+__device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r, uint32_t g, bool in, uint32_t lane, PsSnapSums &run, PsSnapSums &mine) {
+    const PsSnapGeom &Q = A.geo;
+    const size_t i = (size_t)r * Q.G + (in ? g : 0u);
+    uint64_t c = 0;
+    if (in) {
+        const PsSnapCell x = pssnap_cell<PACK, P>(A, i);
+        if (PACK) {
+            ((uint32_t *)(A.img + Q.o_tok[P]))[i] = x.tok; ((uint32_t *)(A.img + Q.o_dlen[P]))[i] = x.dlen;
+            A.img[Q.o_avail[P] + i] = (uint8_t)x.avail;
+            if (P == 1) A.img[Q.o_alias + i] = (uint8_t)x.alias;
+        } else {
+            const PsPlane &pl = A.v.pl[P];
+            pl.tok[i] = x.tok; pl.dlen[i] = x.dlen; pl.avail[i] = (uint8_t)x.avail;
+            if (P == 1 && pl.alias) pl.alias[i] = (uint8_t)x.alias;
+        }
+        const uint32_t st = pssnap_stored(x.avail, x.alias);
+        c = pssnap_cell_bytes(st, x.dlen, A.v.d);
+        mine.cells += x.tok != PS_NULL ? 1u : 0u; mine.shards += (uint32_t)__popc(st);
+        mine.max_dlen = x.dlen > mine.max_dlen ? x.dlen : mine.max_dlen;
+    }
+    uint64_t incl = c;
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint64_t y = __shfl(incl, (int)(lane >= off ? lane - off : lane));
+        if (lane >= off) incl += y;
+    }
+    if (in) A.cell_off[((size_t)P * Q.W + r) * Q.G + g] = run.bytes + (incl - c);
+    run.bytes += __shfl(incl, 63);
+}
+
+template <bool PACK>
+__global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) {
+    const PsSnapGeom &Q = A.geo;
+    const PsView &v = A.v;
+    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
+    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
+    const uint32_t gb0 = tb0 * 64 < Q.G ? tb0 * 64 : Q.G, gw0 = t0 * 64 < Q.G ? t0 * 64 : Q.G;
+    PsSnapSums run = pssnap_bases<PACK>(A, gb0, gw0);
+    PsSnapSums mine{0, 0, 0, 0};
+    for (uint32_t t = t0; t < t1; t++) {
+        const uint32_t g = t * 64 + lane;
+        const bool in = g < Q.G;
+        for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 0>(A, r, g, in, lane, run, mine);
+        if (Q.planes == 2)
+            for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 1>(A, r, g, in, lane, run, mine);
+    }
+    static_assert(SMR_CTR_SHARDS == 256, "one thread of block 0 per counter shard");
+    if (PACK) {
+        if (blockIdx.x == 0 && threadIdx.x < 64) {               // the counters' shards summed (smr_common.h)
+            unsigned long long x0 = 0, x1 = 0, x2 = 0, x3 = 0, x4 = 0;
+            for (uint32_t sh = lane; sh < SMR_CTR_SHARDS; sh += 64) {
+                const unsigned long long *c = v.counters + (size_t)sh * SMR_CTR_STRIDE;
+                x0 += c[0]; x1 += c[1]; x2 += c[2]; x3 += c[3]; x4 += c[4];
+            }
+            x0 = pssnap_wave_sum(x0); x1 = pssnap_wave_sum(x1); x2 = pssnap_wave_sum(x2); x3 = pssnap_wave_sum(x3); x4 = pssnap_wave_sum(x4);
+            if (lane == 0) {
+                uint64_t *c = (uint64_t *)(A.img + Q.off_ctr);
+                c[0] = x0; c[1] = x1; c[2] = x2; c[3] = x3; c[4] = x4;
+            }
+        }
+        if (t0 < Q.ntile && t1 == Q.ntile) {                     // the wavefront of the last tile knows the totals
+            pssnap_wave_reduce(mine);
+            if (lane == 0) {
+                PsSnapHdr h;
+                h.magic = PSSNAP_MAGIC; h.version = PSSNAP_VERSION; h.n_groups = Q.G; h.window = Q.W;
+                h.n_shards = (uint8_t)v.n; h.n_data_shards = (uint8_t)v.d; h.planes = (uint8_t)Q.planes; h.craft = (uint8_t)A.craft;
+                h.max_dlen = mine.max_dlen > run.max_dlen ? mine.max_dlen : run.max_dlen;
+                h.n_cells = run.cells + mine.cells; h.n_shards_stored = run.shards + mine.shards; h.shard_bytes = run.bytes;
+                h.bytes = Q.fixed + run.bytes; h.reserved = 0;
+                *(PsSnapHdr *)A.img = h;
+                for (uint32_t p = 0; p < Q.planes; p++) {        // padding is zero
+                    for (uint64_t b = Q.o_tok[p] + 4 * Q.cells; b < Q.o_dlen[p]; b++) A.img[b] = 0;
+                    for (uint64_t b = Q.o_dlen[p] + 4 * Q.cells; b < Q.o_avail[p]; b++) A.img[b] = 0;
+                    for (uint64_t b = Q.o_avail[p] + Q.cells; b < Q.o_avail[p] + pssnap_a8(Q.cells); b++) A.img[b] = 0;
+                }
+                if (Q.planes == 2)
+                    for (uint64_t b = Q.o_alias + Q.cells; b < Q.hdr_end; b++) A.img[b] = 0;
+                for (uint64_t b = Q.hdr_end; b < Q.fixed; b++) A.img[b] = 0;
+            }
+        }
+    } else if (blockIdx.x == 0) {                                // the sums into shard 0, the other shards zero
+        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++)
+            v.counters[(size_t)threadIdx.x * SMR_CTR_STRIDE + k] = (threadIdx.x == 0 && k < 5) ? ((const uint64_t *)(A.img + Q.off_ctr))[k] : 0ull;
+    }
+}
+
+// the low nb bytes of a word, the rest zero
+__device__ __forceinline__ uint32_t pssnap_keep(uint32_t w, uint32_t nb) { return nb >= 4u ? w : (nb ? (w & ((1u << (8u * nb)) - 1u)) : 0u); }
+
+template <bool PACK>
+__global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) {
+    const PsSnapGeom &Q = A.geo;
+    const PsView &v = A.v;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wv = (uint64_t)blockIdx.x * 4 + SMR_WAVE_UNIFORM(threadIdx.x >> 6), nwv = (uint64_t)gridDim.x * 4;
+    const uint64_t items = (uint64_t)Q.planes * Q.cells * v.n;
+    for (uint64_t it = wv; it < items; it += nwv) {
+        const uint64_t ci64 = it / v.n;                          // plane * cells + cell: up to 2^33 (W x G < 2^32 cells, see ps_create)
+        const uint32_t k = (uint32_t)(it - ci64 * v.n);
+        const bool p1 = ci64 >= Q.cells;
+        const size_t i = (size_t)(ci64 - (p1 ? Q.cells : 0));
+        const uint32_t avail = A.img[(p1 ? Q.o_avail[1] : Q.o_avail[0]) + i];
+        const uint32_t alias = p1 ? (uint32_t)A.img[Q.o_alias + i] : 0u;
+        const uint32_t stored = pssnap_stored(avail, alias);
+        if (!((stored >> k) & 1u)) continue;
+        const uint32_t dlen = ((const uint32_t *)(A.img + (p1 ? Q.o_dlen[1] : Q.o_dlen[0])))[i];
+        const uint32_t sl = pssnap_shard_len(dlen, v.d), sl16 = (uint32_t)pssnap_a16(sl);
+        const uint64_t off = A.cell_off[ci64] + (uint64_t)__popc(stored & ((1u << k) - 1u)) * sl16;
+        if (sl16 > v.cap_sl || off + sl16 > A.cap_bytes) continue;                    // (refused by the host / cannot happen)
+        const uint32_t row = (uint32_t)(i / Q.G), g = (uint32_t)(i - (size_t)row * Q.G);
+        const size_t ro = ps_off(v, row, k, g);
+        uint8_t *const ip = A.img + Q.fixed + off;
+        for (uint32_t c0 = lane * 16u; c0 < sl16; c0 += 1024u) {
+            if (PACK) {
+                // where ps_rd reads a shard whose alias bit is clear: the plane's own row.  (The aliased ones are not read here at
+                // all -- stored = avail & ~alias; their bytes are the REQS cell's.  Calling ps_rd itself with a per-wavefront plane
+                // put the PsPlane's three pointers into scratch, 24 B: its choice between two fields is a choice between addresses.)
+                const uint8_t *const rp = (p1 ? v.pl[1].bytes : v.pl[0].bytes) + ro;
+                ps_u32x4 x = ps_load16(rp + c0);
+                const uint32_t left = sl - c0;                   // bytes of this column that are the shard's: the rest is written as zeros
+                if (left < 16u) {
+                    x.x = pssnap_keep(x.x, left); x.y = pssnap_keep(x.y, left > 4u ? left - 4u : 0u);
+                    x.z = pssnap_keep(x.z, left > 8u ? left - 8u : 0u); x.w = pssnap_keep(x.w, left > 12u ? left - 12u : 0u);
+                }
+                ps_store16(ip + c0, x);
+            } else {
+                uint8_t *rp = (p1 ? v.pl[1].bytes : v.pl[0].bytes) + ro;
+                if (c0 + 16u <= sl) ps_store16(rp + c0, ps_load16(ip + c0));
+                else for (uint32_t b = c0; b < sl; b++) rp[b] = ip[b];            // bytes behind the shard's length are not the store's state
+            }
+        }
+    }
+}
+
+}  // namespace smr

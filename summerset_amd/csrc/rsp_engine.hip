@@ -637,6 +637,8 @@ __global__ __launch_bounds__(SMR_MAX_REPLICAS * 64) void rsp_cluster_tick_kernel
 
 }  // namespace smr
 
+#include "rsp_snapshot.h"
+
 using namespace smr;
 
 struct smr_rsp_replica {
@@ -888,7 +890,7 @@ int smr_rsp_dump(smr_rsp_replica *e, const smr_rsp_dump_bufs *hb) {
     for (size_t w = 0; w < W; w++)
         for (size_t g = 0; g < G; g++) {
             const size_t o = w * G + g;
-            const uint32_t end = hb->len[g], lo = end > W ? end - (uint32_t)W : 0;
+            const uint32_t end = hb->len[g], lo = rsp_live_lo(end, v.W);      // (rsp_snapshot.h: the live span)
             uint32_t s = (lo & ~(uint32_t)(W - 1)) | (uint32_t)w;
             if (s < lo) s += (uint32_t)W;
             const bool live = s < end;
@@ -896,9 +898,13 @@ int smr_rsp_dump(smr_rsp_replica *e, const smr_rsp_dump_bufs *hb) {
                 hb->s_bal[o] = 0; hb->s_status[o] = 0; hb->s_val[o] = 0xFFFFFFFFu; hb->s_mask[o] = 0; hb->s_vbal[o] = 0;
                 hb->s_vval[o] = 0xFFFFFFFFu; hb->s_vmask[o] = 0; hb->s_flags[o] = 0;
             }
-            const uint8_t fl = hb->s_flags[o];
-            if (!(fl & 1)) { hb->s_ltrig[o] = 0; hb->s_lendp[o] = 0; hb->s_packs[o] = 0; hb->s_aacks[o] = 0; hb->s_pmax[o] = 0; }
-            if (!(fl & 2)) { hb->s_rsrc[o] = 0xFF; hb->s_rtrig[o] = 0; hb->s_rendp[o] = 0; }
+            RspSnapSlot r;                                                   // (rsp_snapshot.h: the canonical bookkeeping fields)
+            r.flags = hb->s_flags[o];
+            r.ltrig = hb->s_ltrig[o]; r.lendp = hb->s_lendp[o]; r.packs = hb->s_packs[o]; r.aacks = hb->s_aacks[o]; r.pmax = hb->s_pmax[o];
+            r.rsrc = hb->s_rsrc[o]; r.rtrig = hb->s_rtrig[o]; r.rendp = hb->s_rendp[o];
+            rsp_slot_canon(r);
+            hb->s_ltrig[o] = r.ltrig; hb->s_lendp[o] = r.lendp; hb->s_packs[o] = r.packs; hb->s_aacks[o] = r.aacks; hb->s_pmax[o] = r.pmax;
+            hb->s_rsrc[o] = r.rsrc; hb->s_rtrig[o] = r.rtrig; hb->s_rendp[o] = r.rendp;
         }
     return SMR_OK;
 }
@@ -926,6 +932,245 @@ int smr_rsp_exec_poll(smr_rsp_replica *e, uint32_t *group_host, uint32_t *slot_h
             group_host[n] = (uint32_t)g; slot_host[n] = slot; val_host[n] = val[(size_t)(slot & v.Wmask) * G + g];
         }
     *n_out = n;
+    return SMR_OK;
+}
+
+/* ---- save / load of one replica's state on the device (rsp_snapshot.h: the image and its two kernels) --------------------------
+ * The crash-restart loop of summerset_server/src/main.rs:124-167 brings a replica back from its snapshot file and WAL
+ * (rspaxos/snapshot.rs, rspaxos/recovery.rs); a batched replica object is saved and brought back whole, between two handler
+ * calls, by one kernel each, while the other replicas of its cluster go on. */
+}  // extern "C"
+
+struct smr_rsp_snapshot {
+    uint32_t G = 0;
+    uint8_t R = 0, me = 0, ft = 0;
+    uint8_t *dev = nullptr;
+    uint64_t cap_s = 0, cap_x = 0;                               // records the device buffer's sections have room for
+    bool filled = false, hdr_known = false;                      // a save / import has run; `hdr` is the image's header
+    RspSnapHdr hdr;
+};
+
+namespace smr {
+static RspSnapGeom rspsnap_geom_of(const smr_rsp_snapshot *s) { return rspsnap_geom(s->G, s->R); }
+static int rspsnap_alloc(smr_rsp_snapshot *s, uint64_t cap_s, uint64_t cap_x) {
+    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
+    s->cap_s = cap_s; s->cap_x = cap_x;
+    const RspSnapImg S{nullptr, cap_s, cap_x};
+    hipError_t e = hipMalloc((void **)&s->dev, rspsnap_dev_bytes(rspsnap_geom_of(s), S));
+    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("rspaxos snapshot: hipMalloc: ") + hipGetErrorString(e)); }
+    return SMR_OK;
+}
+// room for the worst case of a replica with e's window: every ring row live, a full execution list.  A save can then never find
+// the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica with a
+// larger window is saved into it.
+static int rspsnap_room(smr_rsp_snapshot *s, const smr_rsp_replica *e) {
+    const uint64_t n = (uint64_t)s->G * e->cfg.window;
+    if (s->dev && n <= s->cap_s && n <= s->cap_x) return SMR_OK;
+    s->filled = false; s->hdr_known = false;                     // (what it held goes with the old buffer)
+    return rspsnap_alloc(s, n > s->cap_s ? n : s->cap_s, n > s->cap_x ? n : s->cap_x);
+}
+// the image's header on the host (synchronises once after a save)
+static int rspsnap_header(smr_rsp_snapshot *s) {
+    if (!s->filled) return fail(SMR_ERR_STATE, "rspaxos snapshot: nothing saved or imported yet");
+    if (s->hdr_known) return SMR_OK;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(RspSnapHdr), hipMemcpyDeviceToHost));
+    // (cannot happen: the kernel's counts are bounded by the window the room was made for)
+    if (s->hdr.n_slots > s->cap_s || s->hdr.n_exec > s->cap_x) {
+        s->filled = false;
+        return fail(SMR_ERR_STATE, "rspaxos snapshot: the saved state exceeds the snapshot's room");
+    }
+    s->hdr_known = true;
+    return SMR_OK;
+}
+static bool rspsnap_like(const smr_rsp_snapshot *s, const smr_rsp_replica *e) {
+    return s->G == e->cfg.n_groups && s->R == e->cfg.population && s->me == e->cfg.me && s->ft == e->cfg.fault_tolerance;
+}
+static bool rspsnap_hdr_like(const RspSnapHdr &h, const smr_rsp_snapshot *s) {
+    return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.fault_tolerance == s->ft;
+}
+static const char *const RSPSNAP_OTHER = "another n_groups / population / replica id / fault_tolerance";
+
+// the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
+static int rspsnap_setup(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, bool load, RspSnapArgs &A) {
+    if (!reps || !snaps) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    if (n == 0 || n > SMR_MAX_REPLICAS) return fail(SMR_ERR_ARG, "rspaxos snapshot: 1 .. 8 replicas");
+    memset(&A, 0, sizeof(A));
+    for (uint32_t k = 0; k < n; k++) {
+        smr_rsp_replica *e = reps[k];
+        smr_rsp_snapshot *s = snaps[k];
+        if (!e || !s) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+        for (uint32_t j = 0; j < k; j++)
+            if (reps[j] == e || snaps[j] == s) return fail(SMR_ERR_ARG, "rspaxos snapshot: a replica or a snapshot is listed twice");
+        if (e->v.G != reps[0]->v.G || e->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, "rspaxos snapshot: the replicas differ in groups / population");
+        if (!rspsnap_like(s, e)) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: made for ") + RSPSNAP_OTHER);
+    }
+    for (uint32_t k = 0; k < n; k++) {
+        smr_rsp_replica *e = reps[k];
+        smr_rsp_snapshot *s = snaps[k];
+        if (load) {
+            if (int rc = rspsnap_header(s)) return rc;
+            const RspSnapHdr &h = s->hdr;
+            if (!rspsnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: the image is of ") + RSPSNAP_OTHER);
+            // a slot is held iff slot + W >= len: in another ring the cells around the saved span would count as held or lost
+            if (h.window != e->cfg.window)
+                return fail(SMR_ERR_ARG, "rspaxos snapshot: an image of window " + std::to_string(h.window) + " does not load into window " + std::to_string(e->cfg.window));
+        } else if (int rc = rspsnap_room(s, e)) return rc;               // (only a failed hipMalloc: the snapshots that grew before it are
+                                                                         //  then empty, SMR_ERR_STATE on use, and none holds a partial image)
+    }
+    A.geo = rspsnap_geom(reps[0]->v.G, reps[0]->v.R);
+    for (uint32_t k = 0; k < n; k++) { A.v[k] = reps[k]->v; A.img[k] = snaps[k]->dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
+    return SMR_OK;
+}
+}  // namespace smr
+
+extern "C" {
+
+int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    smr_rsp_snapshot *s = new smr_rsp_snapshot();
+    s->G = like->cfg.n_groups; s->R = like->cfg.population; s->me = like->cfg.me; s->ft = like->cfg.fault_tolerance;
+    memset(&s->hdr, 0, sizeof(s->hdr));
+    if (int rc = rspsnap_room(s, like)) { delete s; return rc; }
+    *out = s;
+    return SMR_OK;
+}
+
+void smr_rsp_snapshot_destroy(smr_rsp_snapshot *s) {
+    if (!s) return;
+    if (s->dev) { (void)hipDeviceSynchronize(); (void)hipFree(s->dev); }
+    delete s;
+}
+
+int smr_rsp_cluster_save_state(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, void *stream) {
+    RspSnapArgs A;
+    if (int rc = rspsnap_setup(n, reps, snaps, false, A)) return rc;
+    hipLaunchKernelGGL(rsp_snap_pack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < n; k++) { snaps[k]->filled = true; snaps[k]->hdr_known = false; }
+    return SMR_OK;
+}
+
+int smr_rsp_cluster_load_state(uint32_t n, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *snaps, void *stream) {
+    RspSnapArgs A;                                               // (a snapshot's header is read back and cached on first use)
+    if (int rc = rspsnap_setup(n, reps, const_cast<smr_rsp_snapshot *const *>(snaps), true, A)) return rc;
+    hipLaunchKernelGGL(rsp_snap_unpack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_rsp_save_state(smr_rsp_replica *e, smr_rsp_snapshot *s, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    return smr_rsp_cluster_save_state(1, &e, &s, stream);
+}
+
+int smr_rsp_load_state(smr_rsp_replica *e, const smr_rsp_snapshot *s, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    return smr_rsp_cluster_load_state(1, &e, &s, stream);
+}
+
+int smr_rsp_debug_arena_view(smr_rsp_replica *e, void **base_dev, uint64_t *n_bytes) {
+    if (!e || !base_dev || !n_bytes) return fail(SMR_ERR_ARG, "rspaxos: null argument");
+    *base_dev = e->arena.base; *n_bytes = e->arena.size;
+    return SMR_OK;
+}
+
+int smr_rsp_snapshot_info_get(const smr_rsp_snapshot *cs, smr_rsp_snapshot_info *out) {
+    if (!cs || !out) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    smr_rsp_snapshot *s = const_cast<smr_rsp_snapshot *>(cs);
+    if (int rc = rspsnap_header(s)) return rc;
+    const RspSnapHdr &h = s->hdr;
+    memset(out, 0, sizeof(*out));
+    out->bytes = h.bytes; out->n_slots = h.n_slots; out->n_exec = h.n_exec;
+    out->n_groups = h.n_groups; out->window = h.window; out->max_live = h.max_live; out->max_exec = h.max_exec;
+    out->population = h.population; out->replica_id = h.me; out->fault_tolerance = h.fault_tolerance;
+    return SMR_OK;
+}
+
+int64_t smr_rsp_snapshot_export(const smr_rsp_snapshot *cs, uint8_t *host, uint64_t cap) {
+    if (!cs || !host) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    smr_rsp_snapshot *s = const_cast<smr_rsp_snapshot *>(cs);
+    if (int rc = rspsnap_header(s)) return rc;
+    const RspSnapHdr &h = s->hdr;
+    if (cap < h.bytes) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
+    const RspSnapGeom q = rspsnap_geom_of(s);
+    const RspSnapImg S{s->dev, s->cap_s, s->cap_x};
+    uint8_t *p = host;
+    SMR_HIP_TRY(hipMemcpy(p, s->dev, q.fixed, hipMemcpyDeviceToHost)); p += q.fixed;
+    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(p, s->dev + q.fixed, h.n_slots * sizeof(RspSnapSlot), hipMemcpyDeviceToHost));
+    p += h.n_slots * sizeof(RspSnapSlot);
+    if (h.n_exec) SMR_HIP_TRY(hipMemcpy(p, s->dev + rspsnap_off_exec(q, S), h.n_exec * 4, hipMemcpyDeviceToHost));
+    memset(p + h.n_exec * 4, 0, rspsnap_a8(h.n_exec * 4) - h.n_exec * 4);
+    return (int64_t)h.bytes;
+}
+
+int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t len) {
+    if (!s || !host) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    if (len < sizeof(RspSnapHdr)) return fail(SMR_ERR_ARG, "rspaxos snapshot: image shorter than its header");
+    RspSnapHdr h;
+    memcpy(&h, host, sizeof(h));
+    if (h.magic != RSPSNAP_MAGIC) return fail(SMR_ERR_ARG, "rspaxos snapshot: not a snapshot image (magic)");
+    if (h.version != RSPSNAP_VERSION)
+        return fail(SMR_ERR_ARG, "rspaxos snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(RSPSNAP_VERSION));
+    if (h.me >= h.population) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image's replica id is not below its population");
+    if (!rspsnap_hdr_like(h, s) || h.reserved0 || h.reserved1 || h.reserved2) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: the image is of ") + RSPSNAP_OTHER);
+    const uint32_t W = h.window;
+    if (W < 8 || (W & (W - 1)) || W > RSPSNAP_MAX_WINDOW) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image's window is not a power of two in 8 .. 2^20");
+    const RspSnapGeom q = rspsnap_geom_of(s);
+    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed) return fail(SMR_ERR_ARG, "rspaxos snapshot: truncated image");
+    const uint64_t room = h.bytes - q.fixed;                      // the record sections; each count bounded before it is multiplied
+    if (h.n_slots > room / sizeof(RspSnapSlot) || h.n_exec > room / 4 || rspsnap_bytes(q, h.n_slots, h.n_exec) != h.bytes)
+        return fail(SMR_ERR_ARG, "rspaxos snapshot: the header's counts do not add up to the image's size");
+    // the body against the header: counts and maxima recomputed from the scalars, ids in range
+    const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: malformed image: ") + what); };
+    const auto u32at = [](const uint8_t *p, uint64_t i) { uint32_t x; memcpy(&x, p + 4 * i, 4); return x; };
+    uint64_t n_s = 0, n_x = 0;
+    uint32_t max_live = 0, max_exec = 0;
+    for (uint32_t g = 0; g < s->G; g++) {
+        const uint32_t n = rsp_live_n(u32at(host + q.o_len, g), W), nx = u32at(host + q.o_xn, g);
+        if (n > h.max_live) return bad("a group's live span above the header's max_live");
+        if (nx > W || nx > h.max_exec) return bad("a group's execution list above the window or the header's max_exec");
+        const uint8_t ld = host[q.o_leader + g];
+        if (ld != RSP_NO_REP && ld >= s->R) return bad("leader not below the population");
+        n_s += n; n_x += nx; max_live = n > max_live ? n : max_live; max_exec = nx > max_exec ? nx : max_exec;
+    }
+    if (n_s != h.n_slots || n_x != h.n_exec || max_live != h.max_live || max_exec != h.max_exec) return bad("the header's counts and maxima contradict the body");
+    const uint64_t g = s->G;
+    const uint64_t pads[7][2] = {{q.o_leader, g}, {q.o_len, 4 * g}, {q.o_cbar, 4 * g}, {q.o_ebar, 4 * g}, {q.o_snap, 4 * g}, {q.o_peb, 4 * g * s->R}, {q.o_xn, 4 * g}};
+    for (const auto &pd : pads)
+        for (uint64_t p = pd[0] + pd[1]; p < pd[0] + rspsnap_a8(pd[1]); p++) if (host[p]) return bad("padding is not zero");
+    const uint8_t *p = host + q.fixed;
+    for (uint64_t k = 0; k < h.n_slots; k++, p += sizeof(RspSnapSlot)) {
+        RspSnapSlot r, c;
+        memcpy(&r, p, sizeof(r));
+        c = r;
+        rsp_slot_canon(c);
+        if (r.zero || r.status > RST_EXECUTED || (r.flags & ~(RFL_LBK | RFL_RBK | RFL_EXT))) return bad("instance record");
+        if (((r.mask | r.vmask | c.packs | c.aacks) >> s->R) || ((r.flags & RFL_RBK) && r.rsrc >= s->R)) return bad("an instance names replicas beyond the population");
+        if (memcmp(&r, &c, sizeof(r))) return bad("bookkeeping fields of an instance without that bookkeeping");
+    }
+    {                                                            // exec entries, in the image's order (tile, list position, group): a slot of the log
+        uint64_t k = 0;
+        for (uint32_t t0 = 0; t0 < s->G; t0 += 64) {
+            uint32_t rows = 0;
+            for (uint32_t gg = t0; gg < t0 + 64 && gg < s->G; gg++) { const uint32_t nx = u32at(host + q.o_xn, gg); rows = nx > rows ? nx : rows; }
+            for (uint32_t row = 0; row < rows; row++)
+                for (uint32_t gg = t0; gg < t0 + 64 && gg < s->G; gg++)
+                    if (u32at(host + q.o_xn, gg) > row && u32at(p, k++) >= u32at(host + q.o_len, gg)) return bad("an executed slot at or above the group's len");
+        }
+    }
+    for (uint64_t k = h.n_exec * 4; k < rspsnap_a8(h.n_exec * 4); k++) if (p[k]) return bad("padding is not zero");
+    if (h.n_slots > s->cap_s || h.n_exec > s->cap_x)
+        if (int rc = rspsnap_alloc(s, h.n_slots > s->cap_s ? h.n_slots : s->cap_s, h.n_exec > s->cap_x ? h.n_exec : s->cap_x)) return rc;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    s->filled = false;
+    const RspSnapImg S{s->dev, s->cap_s, s->cap_x};
+    p = host;
+    SMR_HIP_TRY(hipMemcpy(s->dev, p, q.fixed, hipMemcpyHostToDevice)); p += q.fixed;
+    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(s->dev + q.fixed, p, h.n_slots * sizeof(RspSnapSlot), hipMemcpyHostToDevice));
+    p += h.n_slots * sizeof(RspSnapSlot);
+    if (h.n_exec) SMR_HIP_TRY(hipMemcpy(s->dev + rspsnap_off_exec(q, S), p, h.n_exec * 4, hipMemcpyHostToDevice));
+    s->hdr = h; s->filled = true; s->hdr_known = true;
     return SMR_OK;
 }
 

@@ -49,6 +49,8 @@ struct PsPlane {
     uint8_t *base0;        // that plane's bytes.  NULL / unused for every other plane
 };
 // where shard k of cell i (= row * G + g) of plane p is read from
+// (ps_snapshot.h's byte kernel knows this rule too: it reads the shards whose alias bit is clear from `bytes` directly and skips
+// the aliased ones.  A change to what an alias means changes both.)
 __device__ __forceinline__ const uint8_t *ps_rd(const PsPlane &p, size_t i, uint32_t k) {
     return (p.alias && ((p.alias[i] >> k) & 1u)) ? p.base0 : p.bytes;
 }
@@ -908,6 +910,8 @@ static bool ps_build_table(int n, int d, std::vector<uint8_t> &tab) {
 
 }  // namespace smr
 
+#include "ps_snapshot.h"
+
 using namespace smr;
 
 struct smr_rsp_pstore {
@@ -1439,6 +1443,209 @@ int smr_rsp_pstore_debug_delivered(smr_rsp_pstore *s, uint64_t *out_host) {
     unsigned long long c[5];
     SMR_HIP_TRY(ctr_read(s->v.counters, 5, c));
     *out_host = c[4];
+    return SMR_OK;
+}
+
+/* ---- save / load of a store's state on the device (ps_snapshot.h: the image and its kernels) ------------------------------------
+ * What rspaxos/snapshot.rs + recovery.rs (craft/snapshot.rs) bring back of `inst.reqs_cw` / `inst.voted.1` / a log entry's
+ * codeword: here the shard bytes themselves, between two calls on the store, two launches each way. */
+}  // extern "C"
+
+struct smr_rsp_pstore_snapshot {
+    uint32_t G = 0, W = 0;
+    uint8_t n = 0, d = 0, planes = 0, craft = 0;
+    uint8_t *dev = nullptr;                                      // the image, dense: header .. shard bytes
+    uint64_t *d_off = nullptr;                                   // [planes][W][G] where a cell's stored shards begin (scratch of the two launches)
+    uint64_t cap_bytes = 0;                                      // room of the shard section
+    bool filled = false, hdr_known = false;
+    PsSnapHdr hdr;
+};
+
+namespace smr {
+static PsSnapGeom pssnap_geom_of(const smr_rsp_pstore_snapshot *s) { return pssnap_geom(s->G, s->W, s->planes); }
+static int pssnap_alloc(smr_rsp_pstore_snapshot *s, uint64_t cap_bytes) {
+    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
+    s->cap_bytes = cap_bytes;
+    hipError_t e = hipMalloc((void **)&s->dev, pssnap_geom_of(s).fixed + cap_bytes + 16);
+    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("pstore snapshot: hipMalloc: ") + hipGetErrorString(e)); }
+    return SMR_OK;
+}
+// room for the worst case of store `st`: every cell holding every shard at max_data_len -- the planes' own size.  A save can then
+// never find the snapshot too small, so it only enqueues.  Grows (host-known sizes) when a store with a larger max_data_len is saved.
+static int pssnap_room(smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
+    const uint64_t need = (uint64_t)st->planes * st->plane_bytes;
+    if (s->dev && need <= s->cap_bytes) return SMR_OK;
+    s->filled = false; s->hdr_known = false;
+    return pssnap_alloc(s, need > s->cap_bytes ? need : s->cap_bytes);
+}
+static int pssnap_header(smr_rsp_pstore_snapshot *s) {
+    if (!s->filled) return fail(SMR_ERR_STATE, "pstore snapshot: nothing saved or imported yet");
+    if (s->hdr_known) return SMR_OK;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(PsSnapHdr), hipMemcpyDeviceToHost));
+    if (s->hdr.shard_bytes > s->cap_bytes) {                     // (cannot happen: bounded by the planes the room was made for)
+        s->filled = false;
+        return fail(SMR_ERR_STATE, "pstore snapshot: the saved state exceeds the snapshot's room");
+    }
+    s->hdr_known = true;
+    return SMR_OK;
+}
+static bool pssnap_like(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
+    return s->G == st->v.G && s->W == st->v.W && s->n == st->v.n && s->d == st->v.d && s->planes == st->planes && (s->craft != 0) == st->craft_store;
+}
+static bool pssnap_hdr_like(const PsSnapHdr &h, const smr_rsp_pstore_snapshot *s) {
+    return h.n_groups == s->G && h.window == s->W && h.n_shards == s->n && h.n_data_shards == s->d && h.planes == s->planes && h.craft == s->craft;
+}
+static const char *const PSSNAP_OTHER = "another n_groups / n_shards / n_data_shards / window / kind (RSPaxos or CRaft store)";
+static PsSnapArgs pssnap_args(const smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *s) {
+    PsSnapArgs A;
+    memset(&A, 0, sizeof(A));
+    A.v = st->v; A.img = s->dev; A.cell_off = s->d_off; A.cap_bytes = s->cap_bytes; A.craft = s->craft; A.geo = pssnap_geom_of(s);
+    return A;
+}
+static uint32_t pssnap_byte_blocks(const PsSnapArgs &A) {
+    const uint64_t items = (uint64_t)A.geo.planes * A.geo.cells * A.v.n, want = (items + 3) / 4;
+    return (uint32_t)(want < PSSNAP_BYTE_BLOCKS ? (want ? want : 1) : PSSNAP_BYTE_BLOCKS);
+}
+}  // namespace smr
+
+extern "C" {
+
+int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    smr_rsp_pstore_snapshot *s = new smr_rsp_pstore_snapshot();
+    s->G = like->v.G; s->W = like->v.W; s->n = (uint8_t)like->v.n; s->d = (uint8_t)like->v.d; s->planes = (uint8_t)like->planes;
+    s->craft = like->craft_store ? 1 : 0;
+    memset(&s->hdr, 0, sizeof(s->hdr));
+    hipError_t e = hipMalloc((void **)&s->d_off, (size_t)s->planes * s->G * s->W * 8 + 8);
+    if (e != hipSuccess) { delete s; return fail(SMR_ERR_DEVICE, std::string("pstore snapshot: hipMalloc: ") + hipGetErrorString(e)); }
+    if (int rc = pssnap_room(s, like)) { (void)hipFree(s->d_off); delete s; return rc; }
+    *out = s;
+    return SMR_OK;
+}
+
+void smr_rsp_pstore_snapshot_destroy(smr_rsp_pstore_snapshot *s) {
+    if (!s) return;
+    if (s->dev || s->d_off) (void)hipDeviceSynchronize();
+    if (s->dev) (void)hipFree(s->dev);
+    if (s->d_off) (void)hipFree(s->d_off);
+    delete s;
+}
+
+int smr_rsp_pstore_save(smr_rsp_pstore *st, smr_rsp_pstore_snapshot *s, void *stream) {
+    if (!st || !s) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    if (!pssnap_like(s, st)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: made for ") + PSSNAP_OTHER);
+    if (int rc = pssnap_room(s, st)) return rc;
+    const PsSnapArgs A = pssnap_args(st, s);
+    hipLaunchKernelGGL(ps_snap_head<true>, dim3(A.geo.nblock), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(ps_snap_bytes<true>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    s->filled = true; s->hdr_known = false;
+    return SMR_OK;
+}
+
+int smr_rsp_pstore_load(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *cs, void *stream) {
+    if (!st || !cs) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
+    if (!pssnap_like(s, st)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: made for ") + PSSNAP_OTHER);
+    if (int rc = pssnap_header(s)) return rc;
+    const PsSnapHdr &h = s->hdr;
+    if (!pssnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: the image is of ") + PSSNAP_OTHER);
+    if (h.max_dlen > st->max_data_len)
+        return fail(SMR_ERR_ARG, "pstore snapshot: a payload of " + std::to_string(h.max_dlen) + " bytes does not fit max_data_len " + std::to_string(st->max_data_len));
+    const PsSnapArgs A = pssnap_args(st, s);
+    hipLaunchKernelGGL(ps_snap_head<false>, dim3(A.geo.nblock), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(ps_snap_bytes<false>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_rsp_pstore_snapshot_info_get(const smr_rsp_pstore_snapshot *cs, smr_rsp_pstore_snapshot_info *out) {
+    if (!cs || !out) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
+    if (int rc = pssnap_header(s)) return rc;
+    const PsSnapHdr &h = s->hdr;
+    memset(out, 0, sizeof(*out));
+    out->bytes = h.bytes; out->n_cells = h.n_cells; out->n_shards_stored = h.n_shards_stored; out->shard_bytes = h.shard_bytes;
+    out->n_groups = h.n_groups; out->window = h.window; out->max_dlen = h.max_dlen;
+    out->n_shards = h.n_shards; out->n_data_shards = h.n_data_shards; out->planes = h.planes; out->craft = h.craft;
+    return SMR_OK;
+}
+
+int64_t smr_rsp_pstore_snapshot_export(const smr_rsp_pstore_snapshot *cs, uint8_t *host, uint64_t cap) {
+    if (!cs || !host) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
+    if (int rc = pssnap_header(s)) return rc;
+    if (cap < s->hdr.bytes) return fail(SMR_ERR_ARG, "pstore snapshot: the image takes " + std::to_string(s->hdr.bytes) + " bytes");
+    SMR_HIP_TRY(hipMemcpy(host, s->dev, s->hdr.bytes, hipMemcpyDeviceToHost));
+    return (int64_t)s->hdr.bytes;
+}
+
+int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *host, uint64_t len) {
+    if (!s || !host) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    if (len < sizeof(PsSnapHdr)) return fail(SMR_ERR_ARG, "pstore snapshot: image shorter than its header");
+    PsSnapHdr h;
+    memcpy(&h, host, sizeof(h));
+    if (h.magic != PSSNAP_MAGIC) return fail(SMR_ERR_ARG, "pstore snapshot: not a store image (magic)");
+    if (h.version != PSSNAP_VERSION)
+        return fail(SMR_ERR_ARG, "pstore snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(PSSNAP_VERSION));
+    if (!pssnap_hdr_like(h, s) || h.reserved) return fail(SMR_ERR_ARG, std::string("pstore snapshot: the image is of ") + PSSNAP_OTHER);
+    const PsSnapGeom q = pssnap_geom_of(s);
+    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed || h.bytes - q.fixed != h.shard_bytes || (h.shard_bytes & 15))
+        return fail(SMR_ERR_ARG, "pstore snapshot: truncated image, or its sizes do not add up");
+    const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("pstore snapshot: malformed image: ") + what); };
+    const auto u32at = [&](uint64_t off, uint64_t i) { uint32_t x; memcpy(&x, host + off + 4 * i, 4); return x; };
+    for (uint32_t p = 0; p < q.planes; p++) {
+        for (uint64_t b = q.o_tok[p] + 4 * q.cells; b < q.o_dlen[p]; b++) if (host[b]) return bad("padding is not zero");
+        for (uint64_t b = q.o_dlen[p] + 4 * q.cells; b < q.o_avail[p]; b++) if (host[b]) return bad("padding is not zero");
+        for (uint64_t b = q.o_avail[p] + q.cells; b < q.o_avail[p] + pssnap_a8(q.cells); b++) if (host[b]) return bad("padding is not zero");
+    }
+    for (uint64_t b = (q.planes == 2 ? q.o_alias + q.cells : q.hdr_end); b < q.fixed; b++) if (host[b]) return bad("padding is not zero");
+    // the shard section against the headers, in the image's order: tile, plane, ring row, group, shard
+    uint64_t off = 0, n_cells = 0, n_stored = 0;
+    uint32_t max_dlen = 0;
+    for (uint32_t t0 = 0; t0 < s->G; t0 += 64)
+        for (uint32_t p = 0; p < q.planes; p++)
+            for (uint32_t r = 0; r < s->W; r++)
+                for (uint32_t g = t0; g < t0 + 64 && g < s->G; g++) {
+                    const uint64_t i = (uint64_t)r * s->G + g;
+                    const uint32_t tok = u32at(q.o_tok[p], i), dlen = u32at(q.o_dlen[p], i), avail = host[q.o_avail[p] + i];
+                    const uint32_t alias = p == 1 ? host[q.o_alias + i] : 0u;
+                    if (tok == PS_NULL) {
+                        if (dlen || avail || alias) return bad("a cell without a token holds something");
+                        continue;
+                    }
+                    if ((avail >> s->n) || (alias & ~avail) || (p == 1 && (alias & ~(uint32_t)host[q.o_avail[0] + i]))) return bad("shard or alias bits");
+                    // an alias says "this vote's shard is the REQS row's": same token, same length (ps_plan_cell)
+                    if (alias && (u32at(q.o_tok[0], i) != tok || u32at(q.o_dlen[0], i) != dlen)) return bad("an alias into a REQS cell of another token or length");
+                    n_cells++; max_dlen = dlen > max_dlen ? dlen : max_dlen;
+                    const uint32_t st = pssnap_stored(avail, alias), sl = pssnap_shard_len(dlen, s->d);
+                    const uint64_t sl16 = pssnap_a16(sl);
+                    for (uint32_t k = 0; k < s->n; k++) {
+                        if (!((st >> k) & 1u)) continue;
+                        if (sl16 > h.shard_bytes - off) return bad("the headers ask for more shard bytes than the image holds");
+                        for (uint64_t b = sl; b < sl16; b++) if (host[q.fixed + off + b]) return bad("padding is not zero");
+                        off += sl16; n_stored++;
+                    }
+                }
+    if (off != h.shard_bytes || n_cells != h.n_cells || n_stored != h.n_shards_stored || max_dlen != h.max_dlen)
+        return bad("the header's counts contradict the cell headers");
+    if (!s->dev || h.shard_bytes > s->cap_bytes)
+        if (int rc = pssnap_alloc(s, h.shard_bytes > s->cap_bytes ? h.shard_bytes : s->cap_bytes)) return rc;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    s->filled = false;
+    SMR_HIP_TRY(hipMemcpy(s->dev, host, h.bytes, hipMemcpyHostToDevice));
+    s->hdr = h; s->filled = true; s->hdr_known = true;
+    return SMR_OK;
+}
+
+/* debug / measurement only: the three device allocations that hold the store (meta, REQS plane, VOTED plane; a CRaft store's
+ * third is a stub), i.e. what a wholesale copy of the store would move */
+int smr_rsp_pstore_debug_allocs(smr_rsp_pstore *s, void **base_dev3, uint64_t *n_bytes3) {
+    if (!s || !base_dev3 || !n_bytes3) return fail(SMR_ERR_ARG, "pstore: null argument");
+    const size_t cells = (size_t)s->v.W * s->v.G;
+    base_dev3[0] = s->meta; n_bytes3[0] = (uint64_t)((char *)s->v.dlv + cells - (char *)s->meta);
+    for (int p = 0; p < 2; p++) { base_dev3[1 + p] = s->plane_alloc[p]; n_bytes3[1 + p] = p < s->planes ? s->plane_bytes : 0; }
     return SMR_OK;
 }
 

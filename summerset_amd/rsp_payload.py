@@ -31,6 +31,58 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+class PayloadStoreSnapshot:
+    """One payload store's state between two calls on it, held on the device (`smr_rsp_pstore_snapshot`): cell headers, the VOTED
+    plane's alias bytes, every present shard that is no alias, the counters -- for an `RSPaxosPayloadStore` or a `CRaftPayloadStore`.
+    `export()` gives the canonical image as bytes, equal for two stores of the same content whatever their `max_data_len`."""
+
+    def __init__(self, like):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        check(self._L.smr_rsp_pstore_snapshot_create(like._h, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def create_like(cls, like):
+        """room for the worst case of store `like` (every cell holding every shard at max_data_len)"""
+        return cls(like)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.smr_rsp_pstore_snapshot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def save(self, store, stream=None):
+        check(self._L.smr_rsp_pstore_save(store._h, self._h, stream_ptr(stream)))
+        return self
+
+    def load(self, store, stream=None):
+        check(self._L.smr_rsp_pstore_load(store._h, self._h, stream_ptr(stream)))
+
+    def info(self):
+        """sizes of what was saved (synchronises): bytes, n_cells, n_shards_stored, shard_bytes, n_groups, window, max_dlen,
+        n_shards, n_data_shards, planes, craft"""
+        st = _lib.PstoreSnapshotInfo()
+        check(self._L.smr_rsp_pstore_snapshot_info_get(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+    def export(self):
+        n = self.info()["bytes"]
+        buf = (C.c_uint8 * n)()
+        got = self._L.smr_rsp_pstore_snapshot_export(self._h, buf, n)
+        if got < 0:
+            check(int(got))
+        return C.string_at(buf, got)
+
+    def import_(self, data):
+        data = bytes(data)
+        check(self._L.smr_rsp_pstore_snapshot_import(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
+        return self
+
+
 class RSPaxosPayloadStore:
     _CREATE = "smr_rsp_pstore_create"
 
@@ -168,6 +220,17 @@ class RSPaxosPayloadStore:
         check(self._L.smr_rsp_pstore_counters(self._h, c.ctypes.data_as(C.c_void_p)))
         return dict(copied=int(c[0]), rebuilt=int(c[1]), unsatisfied=int(c[2]), rekeyed=int(c[3]))
 
+    def save(self, snap=None, stream=None):
+        """my headers, alias bytes, present shards and counters into a device-resident snapshot (a new one, or `snap` again),
+        between two calls on the store; two launches on `stream`, nothing is read back"""
+        snap = PayloadStoreSnapshot(self) if snap is None else snap
+        return snap.save(self, stream)
+
+    def load(self, snap, stream=None):
+        """overwrite my state with a snapshot's (`smr_rsp_pstore_load`): same n_groups, shards, data shards, window and kind;
+        max_data_len at least the snapshot's max_dlen"""
+        snap.load(self, stream)
+
     def delivered(self):
         """of `counters()["copied"]`: shards a sender's `put_follow_all` wrote here from its put launch (no copy out of its row)"""
         c = np.zeros(1, np.uint64)
@@ -253,6 +316,16 @@ class RSPaxosReplicaWithPayload:
         """`cluster`: the R objects of this kind, by replica id"""
         self.cluster = list(cluster)
         self.shared = cluster[0].shared                                   # (who answered the last Reconstruct: see reconstruct_reply)
+
+    def save_state(self, snaps=None, stream=None):
+        """the replica's state and its store's, both halves on one stream, between two handler calls: (RSPaxosSnapshot,
+        PayloadStoreSnapshot) -- new ones, or `snaps` filled again.  (A staging store holds only messages in flight: not state.)"""
+        rs, ps = (None, None) if snaps is None else snaps
+        return self.replica.save_state(rs, stream=stream), self.store.save(ps, stream=stream)
+
+    def load_state(self, snaps, stream=None):
+        self.replica.load_state(snaps[0], stream=stream)
+        self.store.load(snaps[1], stream=stream)
 
     def req_batch(self, val, data=None, lens=None, stream=None, out=None):
         acc = self.replica.req_batch(val, stream=stream, out=out)

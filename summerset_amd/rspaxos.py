@@ -23,6 +23,82 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+class RSPaxosSnapshot:
+    """One replica object's state between two handler calls, held on the device (`smr_rsp_snapshot`): what
+    `RSPaxosReplicaGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
+    two replicas that hold the same logical state -- and `import_` takes one back."""
+
+    def __init__(self, like):
+        self._L = _lib.load()
+        h = C.c_void_p()
+        check(self._L.smr_rsp_snapshot_create(like._h, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def create_like(cls, like):
+        """room for the worst case of replica `like` (every ring row live, a full execution list)"""
+        return cls(like)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.smr_rsp_snapshot_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def save(self, rep, stream=None):
+        """`rep.save_state(self)`"""
+        check(self._L.smr_rsp_save_state(rep._h, self._h, stream_ptr(stream)))
+        return self
+
+    def load(self, rep, stream=None):
+        """`rep.load_state(self)`"""
+        check(self._L.smr_rsp_load_state(rep._h, self._h, stream_ptr(stream)))
+
+    def info(self):
+        """sizes of what was saved (synchronises): bytes, n_slots, n_exec, n_groups, window, max_live, max_exec, population,
+        replica_id, fault_tolerance"""
+        st = _lib.RspSnapshotInfo()
+        check(self._L.smr_rsp_snapshot_info_get(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
+
+    def export(self):
+        n = self.info()["bytes"]
+        buf = (C.c_uint8 * n)()
+        got = self._L.smr_rsp_snapshot_export(self._h, buf, n)
+        if got < 0:
+            check(int(got))
+        return C.string_at(buf, got)
+
+    def import_(self, data):
+        """take an exported image (of a replica like the one this snapshot was made for; any window)"""
+        data = bytes(data)
+        check(self._L.smr_rsp_snapshot_import(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
+        return self
+
+
+def _handles(xs):
+    return (C.c_void_p * len(xs))(*[x._h for x in xs])
+
+
+def save_cluster_state(reps, snaps=None, stream=None):
+    """`reps[k].save_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch
+    (`smr_rsp_cluster_save_state`); returns the snapshots (new ones without `snaps`)"""
+    snaps = [RSPaxosSnapshot(r) for r in reps] if snaps is None else list(snaps)
+    if len(snaps) != len(reps):
+        raise ValueError("save_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_rsp_cluster_save_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_state(reps, snaps, stream=None):
+    """`reps[k].load_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch (`smr_rsp_cluster_load_state`)"""
+    if len(snaps) != len(reps):
+        raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_rsp_cluster_load_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+
+
 class RSPaxosReplicaGroup:
     def __init__(self, n_groups, population=5, me=0, window=32, fault_tolerance=0):
         self.G, self.R, self.me, self.W = int(n_groups), int(population), int(me), int(window)
@@ -150,6 +226,17 @@ class RSPaxosReplicaGroup:
             o, hb = self._hb(flags.device, "", False)
         check(self._L.smr_rsp_bcast_heartbeat(self._h, _ptr(flags), C.byref(hb), stream_ptr(stream)))
         return dict(ballot=o["ballot"], commit_bar=o["commit"], exec_bar=o["exec"], snap_bar=o["snap"])
+
+    def save_state(self, snap=None, stream=None):
+        """my whole logical state into a device-resident snapshot (a new one, or `snap` again), between two handler calls; one
+        kernel on `stream`, nothing is read back"""
+        snap = RSPaxosSnapshot(self) if snap is None else snap
+        return snap.save(self, stream)
+
+    def load_state(self, snap, stream=None):
+        """overwrite my whole logical state with a snapshot's (`smr_rsp_load_state`): same n_groups, population, replica id,
+        fault_tolerance and window"""
+        snap.load(self, stream)
 
     def dump(self):
         G, R, W = self.G, self.R, self.W
