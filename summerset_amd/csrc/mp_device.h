@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mp_types.h"
+#include "snapshot_common.h"
 
 // phase stamps inside a handler (experiments only: a -DSMR_JOB_STAMPS build, tools/dbg_stamps.py)
 #ifdef SMR_JOB_STAMPS
@@ -41,10 +42,7 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t x) {
     for (int off = 32; off > 0; off >>= 1) { uint32_t y = __shfl_xor(x, off); x = y < x ? y : x; }
     return x;
 }
-__device__ __forceinline__ uint32_t wave_max(uint32_t x) {
-    for (int off = 32; off > 0; off >>= 1) { uint32_t y = __shfl_xor(x, off); x = y > x ? y : x; }
-    return x;
-}
+// (the maximum is snapshot_common.h's snap_wave_max: the library's one definition)
 
 // Lane context: the group's scalar state of one replica cached in registers.
 struct Lane {
@@ -499,7 +497,7 @@ struct Lane {
                 const uint32_t st = m_st(v.s_meta()[ix(s)]);
                 if (below ? st < bound : st > bound) { found = s + 1; break; }
             }
-        if (coop()) found = wave_max(found);
+        if (coop()) found = snap_wave_max(found);
         return found ? found - 1 : none;
     }
 

@@ -3120,27 +3120,22 @@ int smr_mp_spread_tick(smr_mp_spread *s, const smr_mp_tick_in *in, int heartbeat
 struct smr_mp_snapshot {
     uint32_t G = 0;
     uint8_t R = 0, commit_extra = 0, live = 0;
-    uint8_t *dev = nullptr;
+    SnapBuf buf;
     uint64_t cap_slots = 0, cap_ob = 0, cap_cl = 0;              // records the device buffer's three sections have room for
-    bool filled = false, hdr_known = false;                      // a save / import has run; `hdr` is the image's header
-    SnapHdr hdr;
+    SnapHdr hdr;                                                 // the image's header, once buf.hdr_known
     uint32_t lead_hint = 0;                                      // (scheduling only: not part of the image)
 };
 
+static const char *const MPSNAP = "mp snapshot: ";
 static SnapImg snap_img(const smr_mp_snapshot *s) {
     SnapImg S;
-    S.base = s->dev; S.cap_slots = s->cap_slots; S.cap_ob = s->cap_ob; S.cap_cl = s->cap_cl;
+    S.base = s->buf.dev; S.cap_slots = s->cap_slots; S.cap_ob = s->cap_ob; S.cap_cl = s->cap_cl;
     S.geo = snap_geom(s->G, s->R, s->live); S.commit_extra = s->commit_extra;
     return S;
 }
 static int snap_alloc(smr_mp_snapshot *s, uint64_t cap_slots, uint64_t cap_ob, uint64_t cap_cl) {
-    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
     s->cap_slots = cap_slots; s->cap_ob = cap_ob; s->cap_cl = cap_cl;
-    const SnapImg S = snap_img(s);
-    const uint64_t bytes = snap_off_clist(S) + cap_cl * 8;
-    hipError_t e = hipMalloc((void **)&s->dev, bytes);
-    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("mp snapshot: hipMalloc: ") + hipGetErrorString(e)); }
-    return SMR_OK;
+    return snap_buf_alloc(s->buf, snap_off_clist(snap_img(s)) + cap_cl * 8, MPSNAP);
 }
 // room for the worst case of a cluster with c's window, outbox_cap and commit_list_cap: every ring row live, every outbox
 // full.  A save can then never find the snapshot too small, so it stays a call that only enqueues and whose result needs no
@@ -3151,24 +3146,19 @@ static int snap_room(smr_mp_snapshot *s, const smr_mp_cluster *c) {
     const SnapGeom q = snap_geom(s->G, s->R, s->live);
     const uint64_t GL = (uint64_t)s->G * q.L;
     const uint64_t ns = GL * c->cfg.window, no = GL * c->cfg.outbox_cap, nc = (uint64_t)q.L * c->cfg.commit_list_cap;
-    if (s->dev && ns <= s->cap_slots && no <= s->cap_ob && nc <= s->cap_cl) return SMR_OK;
-    s->filled = false; s->hdr_known = false;                     // (what it held goes with the old buffer)
+    if (s->buf.dev && ns <= s->cap_slots && no <= s->cap_ob && nc <= s->cap_cl) return SMR_OK;
+    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
     return snap_alloc(s, ns > s->cap_slots ? ns : s->cap_slots, no > s->cap_ob ? no : s->cap_ob, nc > s->cap_cl ? nc : s->cap_cl);
 }
 // the image's header on the host (synchronises once after a save)
 static int snap_header(smr_mp_snapshot *s) {
-    if (!s->filled) return fail(SMR_ERR_STATE, "mp snapshot: nothing saved or imported yet");
-    if (s->hdr_known) return SMR_OK;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(SnapHdr), hipMemcpyDeviceToHost));
-    const SnapHdr &h = s->hdr;
-    // (cannot happen: the kernel clamps a group's counts to the window and outbox_cap the room was made for)
-    if (h.n_slots > s->cap_slots || h.n_outbox > s->cap_ob || h.n_commits > s->cap_cl) {
-        s->filled = false;
-        return fail(SMR_ERR_STATE, "mp snapshot: the saved state exceeds the snapshot's room");
-    }
-    s->hdr_known = true;
-    return SMR_OK;
+    return snap_buf_header(s->buf, s->hdr, MPSNAP, [s](const SnapHdr &h) { return h.n_slots <= s->cap_slots && h.n_outbox <= s->cap_ob && h.n_commits <= s->cap_cl; });
+}
+// the image of header h between the device buffer (sections at their capacities) and packed host bytes
+static int snap_copy(const smr_mp_snapshot *s, uint8_t *host, const SnapHdr &h, bool to_host) {
+    const SnapImg S = snap_img(s);
+    const uint64_t ns = h.n_slots * sizeof(SnapSlot), no = h.n_outbox * sizeof(SnapMsg), nc = h.n_commits * 8;
+    return snap_copy_sections(s->buf.dev, host, S.geo.fixed, to_host, {{S.geo.fixed, ns, ns}, {snap_off_msgs(S), no, no}, {snap_off_clist(S), nc, nc}});
 }
 static bool snap_like(const smr_mp_snapshot *s, const smr_mp_cluster *c) {
     return s->G == c->cfg.n_groups && s->R == c->cfg.population && s->commit_extra == c->cfg.commit_extra && s->live == (uint8_t)c->hp.live;
@@ -3187,7 +3177,7 @@ int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out) {
 
 void smr_mp_snapshot_destroy(smr_mp_snapshot *s) {
     if (!s) return;
-    if (s->dev) { (void)hipDeviceSynchronize(); (void)hipFree(s->dev); }
+    snap_buf_free(s->buf);
     delete s;
 }
 
@@ -3206,9 +3196,9 @@ int smr_mp_save_state(smr_mp_cluster *c, smr_mp_snapshot *s, void *stream) {
         SMR_HIP_TRY(hipGetLastError());
     }
     const SnapImg S = snap_img(s);
-    hipLaunchKernelGGL(mp_snap_pack, dim3(S.geo.nblock), dim3(256), 0, st, c->dp, c->par, S);
+    hipLaunchKernelGGL(mp_snap_pack, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S);
     SMR_HIP_TRY(hipGetLastError());
-    s->filled = true; s->hdr_known = false;
+    s->buf.filled = true; s->buf.hdr_known = false;
     s->lead_hint = c->lead_hint;
     return SMR_OK;
 }
@@ -3231,7 +3221,7 @@ int smr_mp_load_state(smr_mp_cluster *c, const smr_mp_snapshot *cs, void *stream
     c->rest_pending = false;                                     // whatever the cluster had pending belongs to the state that goes
     c->lead_hint = s->lead_hint < c->cfg.population ? s->lead_hint : 0u;
     const SnapImg S = snap_img(s);
-    hipLaunchKernelGGL(mp_snap_unpack, dim3(S.geo.nblock), dim3(256), 0, (hipStream_t)stream, c->dp, c->par, S);
+    hipLaunchKernelGGL(mp_snap_unpack, dim3(S.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, c->dp, c->par, S);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
 }
@@ -3254,15 +3244,9 @@ int64_t smr_mp_snapshot_export(const smr_mp_snapshot *cs, uint8_t *host, uint64_
     if (int rc = snap_header(s)) return rc;
     const SnapHdr &h = s->hdr;
     if (cap < h.bytes) return fail(SMR_ERR_ARG, "mp snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    const SnapImg S = snap_img(s);
-    const SnapGeom &q = S.geo;
-    uint8_t *p = host;
-    SMR_HIP_TRY(hipMemcpy(p, s->dev, q.fixed, hipMemcpyDeviceToHost)); p += q.fixed;
-    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(p, s->dev + q.fixed, h.n_slots * sizeof(SnapSlot), hipMemcpyDeviceToHost));
-    p += h.n_slots * sizeof(SnapSlot);
-    if (h.n_outbox) SMR_HIP_TRY(hipMemcpy(p, s->dev + snap_off_msgs(S), h.n_outbox * sizeof(SnapMsg), hipMemcpyDeviceToHost));
-    p += h.n_outbox * sizeof(SnapMsg);
-    if (h.n_commits) SMR_HIP_TRY(hipMemcpy(p, s->dev + snap_off_clist(S), h.n_commits * 8, hipMemcpyDeviceToHost));
+    if (int rc = snap_copy(s, host, h, true)) return rc;
+    const SnapGeom q = snap_geom(s->G, s->R, s->live);
+    uint8_t *p = host + h.bytes - h.n_commits * 8;
     // the list's order across groups is the order the wavefronts' appends happened to land in (smr_mp_poll_commits: unspecified):
     // canonical is a replica's groups ascending, a group's entries in the order they came
     std::vector<uint64_t> e;
@@ -3282,22 +3266,19 @@ int64_t smr_mp_snapshot_export(const smr_mp_snapshot *cs, uint8_t *host, uint64_
 
 int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
-    if (len < sizeof(SnapHdr)) return fail(SMR_ERR_ARG, "mp snapshot: image shorter than its header");
     SnapHdr h;
-    memcpy(&h, host, sizeof(h));
-    if (h.magic != SNAP_MAGIC) return fail(SMR_ERR_ARG, "mp snapshot: not a snapshot image (magic)");
-    if (h.version != SNAP_VERSION) return fail(SMR_ERR_ARG, "mp snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(SNAP_VERSION));
+    if (int rc = snap_import_prologue(host, len, SNAP_MAGIC, SNAP_VERSION, MPSNAP, h)) return rc;
     if (h.n_groups != s->G || h.population != s->R || h.commit_extra != s->commit_extra || h.live_mask != s->live || h.reserved0 || h.reserved1)
         return fail(SMR_ERR_ARG, "mp snapshot: the image is of another n_groups / population / commit_extra / live mask");
     const SnapGeom q = snap_geom(s->G, s->R, s->live);
-    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed) return fail(SMR_ERR_ARG, "mp snapshot: truncated image");
+    if (snap_truncated(len, q.fixed, h.bytes)) return fail(SMR_ERR_ARG, "mp snapshot: truncated image");
     const uint64_t room = h.bytes - q.fixed;                      // the three record sections; each count bounded before it is multiplied
     if (h.n_slots > room / sizeof(SnapSlot) || h.n_outbox > room / sizeof(SnapMsg) || h.n_commits > room / 8 ||
         h.n_slots * sizeof(SnapSlot) + h.n_outbox * sizeof(SnapMsg) + h.n_commits * 8 != room)
         return fail(SMR_ERR_ARG, "mp snapshot: the header's counts do not add up to the image's size");
     // the body against the header: counts and maxima recomputed from the scalars, the records' enumerated fields in range
     const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("mp snapshot: malformed image: ") + what); };
-    for (uint64_t p = s->G; p < snap_a8(s->G); p++) if (host[q.off_ovf + p]) return bad("padding is not zero");
+    if (!snap_pad_is_zero(host, q.off_ovf, s->G)) return bad("padding is not zero");
     uint64_t n_slots = 0, n_outbox = 0, n_commits = 0;
     uint32_t max_live = 0, max_outbox = 0, max_commits = 0;
     for (uint32_t i = 0; i < q.L; i++) {
@@ -3315,7 +3296,7 @@ int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len
             n_slots += ln - st; n_outbox += nob;
             max_live = ln - st > max_live ? ln - st : max_live; max_outbox = nob > max_outbox ? nob : max_outbox;
         }
-        for (uint64_t p = q.o_leader + s->G; p < q.scal_stride; p++) if (b[p]) return bad("padding is not zero");
+        if (!snap_pad_is_zero(b, 0, q.o_leader + s->G)) return bad("padding is not zero");
         SnapRep rp;
         memcpy(&rp, host + q.off_rep + (size_t)i * sizeof(SnapRep), sizeof(rp));
         if (rp.clist_carried > rp.clist_total || rp.clist_total > 0xFFFFFFFFull) return bad("commit list counts");
@@ -3345,16 +3326,9 @@ int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len
         if (int rc = snap_alloc(s, h.n_slots > s->cap_slots ? h.n_slots : s->cap_slots, h.n_outbox > s->cap_ob ? h.n_outbox : s->cap_ob,
                                 h.n_commits > s->cap_cl ? h.n_commits : s->cap_cl)) return rc;
     SMR_HIP_TRY(hipDeviceSynchronize());
-    s->filled = false;
-    const SnapImg S = snap_img(s);
-    p = host;
-    SMR_HIP_TRY(hipMemcpy(s->dev, p, q.fixed, hipMemcpyHostToDevice)); p += q.fixed;
-    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(s->dev + q.fixed, p, h.n_slots * sizeof(SnapSlot), hipMemcpyHostToDevice));
-    p += h.n_slots * sizeof(SnapSlot);
-    if (h.n_outbox) SMR_HIP_TRY(hipMemcpy(s->dev + snap_off_msgs(S), p, h.n_outbox * sizeof(SnapMsg), hipMemcpyHostToDevice));
-    p += h.n_outbox * sizeof(SnapMsg);
-    if (h.n_commits) SMR_HIP_TRY(hipMemcpy(s->dev + snap_off_clist(S), p, h.n_commits * 8, hipMemcpyHostToDevice));
-    s->hdr = h; s->filled = true; s->hdr_known = true; s->lead_hint = 0;
+    s->buf.filled = false;
+    if (int rc = snap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
+    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true; s->lead_hint = 0;
     return SMR_OK;
 }
 

@@ -24,7 +24,7 @@
 // On the device the three record sections sit at fixed capacities behind the fixed part; export closes the gaps.
 #pragma once
 #include "mp_device.h"
-#include "smr_common.h"
+#include "snapshot_common.h"
 
 namespace smr {
 
@@ -103,20 +103,16 @@ SMR_HD uint32_t mp_slot_meta(const SnapSlot &c, bool &voted_side, bool &lx, bool
 
 // ---- where things are in an image ---------------------------------------------------------------------------------------
 struct SnapGeom {
-    uint32_t G, R, live, L, ntile, tpw, nwave, nblock;
+    uint32_t G, R, live, L;
+    SnapTiles tiles;
     uint64_t off_ovf, off_rep, off_scal, scal_stride, fixed;
     uint64_t o_bps, o_bpd, o_bms, o_start, o_len, o_abar, o_cbar, o_ebar, o_snap, o_nob, o_peb, o_leader;
 };
-constexpr uint32_t SNAP_MAX_WAVES = 1024;          // wavefronts of a launch; each takes a contiguous piece of the group tiles
-SMR_HD uint64_t snap_a8(uint64_t x) { return (x + 7) & ~(uint64_t)7; }
 SMR_HD SnapGeom snap_geom(uint32_t G, uint32_t R, uint32_t live) {
     SnapGeom q;
     q.G = G; q.R = R; q.live = live; q.L = 0;
     for (uint32_t r = 0; r < R; r++) q.L += (live >> r) & 1u;
-    q.ntile = (G + 63) / 64;
-    q.tpw = (q.ntile + SNAP_MAX_WAVES - 1) / SNAP_MAX_WAVES;
-    q.nwave = (q.ntile + q.tpw - 1) / q.tpw;
-    q.nblock = (q.nwave + 3) / 4;
+    q.tiles = snap_tiles(G);
     const uint64_t g = G;
     q.off_ovf = sizeof(SnapHdr);
     q.off_rep = q.off_ovf + snap_a8(g);
@@ -155,16 +151,8 @@ SMR_HD SnapScal snap_scal(uint8_t *base, const SnapGeom &q, uint32_t i) {
 }
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
-// Lane = group, a wavefront = a contiguous piece of the 64-group tiles with all their live replicas, 4 wavefronts a block.  A
-// record's place follows from the counts of everything in front of it: the block sums the groups in front of its own tiles
-// (every block reads those counts itself: 12 B per replica and group out of the L2, no block waits for another), the
-// wavefront adds the tiles of its block in front of its own, and inside a tile a row's records go to the lanes that hold one,
-// packed (ballot + prefix count).
-
-__device__ __forceinline__ uint64_t snap_wave_sum(uint64_t x) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
+// A wavefront's tiles carry all their live replicas.  Tiles, bases and placement are snapshot_common.h's; a
+// group's counts cost the bases 12 B per replica out of the L2.
 
 // live slots and pending outbox entries of replica r (the i-th live one) of group g: the cluster's own (PACK) or the image's
 template <bool PACK>
@@ -183,50 +171,52 @@ __device__ __forceinline__ void snap_count(const MpParams &P, int par, const Sna
     if (no > P.cap) no = P.cap;
 }
 
-// sums and maxima over the groups [0, g_wave0) of all live replicas; g_block0 <= g_wave0 is the same for the whole block
+// slot and outbox records of all live replicas in front of a wavefront, and their maxima.  snap_bases' two stages written out,
+// replica by replica: with the replicas as the inner loop of snap_bases' per-group functor, save and load of the headline shape
+// (65 536 groups x 5 replicas) took 16 % and 22 % longer on the MI355X (profiles/snapshot_refactor_ab.log) -- each replica's
+// pass streams through three arrays, and the simple loop over groups is what the compiler keeps several loads in flight for
 template <bool PACK>
-__device__ __forceinline__ void snap_bases(const MpParams &P, int par, const SnapImg &S, uint32_t g_block0, uint32_t g_wave0, uint64_t &bs,
-                                           uint64_t &bo, uint32_t &ms, uint32_t &mo) {
+__device__ __forceinline__ void mp_snap_bases(const MpParams &P, int par, const SnapImg &S, const SnapWave &w, uint64_t (&base)[2], uint32_t (&mx)[2]) {
     __shared__ uint64_t sh_s[4], sh_o[4];
     __shared__ uint32_t sh_ms[4], sh_mo[4];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const uint32_t wv = threadIdx.x >> 6;
     uint64_t s = 0, o = 0;
     uint32_t xs = 0, xo = 0;
     for (uint32_t r = 0, i = 0; r < P.R; r++) {
         if (!((S.geo.live >> r) & 1u)) continue;
-        for (uint32_t g = threadIdx.x; g < g_block0; g += 256) {
+        for (uint32_t g = threadIdx.x; g < w.gb0; g += 256) {
             uint32_t ns, no;
             snap_count<PACK>(P, par, S, r, i, g, ns, no);
             s += ns; o += no; xs = ns > xs ? ns : xs; xo = no > xo ? no : xo;
         }
         i++;
     }
-    s = snap_wave_sum(s); o = snap_wave_sum(o); xs = wave_max(xs); xo = wave_max(xo);
-    if (lane == 0) { sh_s[w] = s; sh_o[w] = o; sh_ms[w] = xs; sh_mo[w] = xo; }
+    s = snap_wave_sum(s); o = snap_wave_sum(o); xs = snap_wave_max(xs); xo = snap_wave_max(xo);
+    if (w.lane == 0) { sh_s[wv] = s; sh_o[wv] = o; sh_ms[wv] = xs; sh_mo[wv] = xo; }
     __syncthreads();
-    bs = sh_s[0] + sh_s[1] + sh_s[2] + sh_s[3];
-    bo = sh_o[0] + sh_o[1] + sh_o[2] + sh_o[3];
-    ms = sh_ms[0]; mo = sh_mo[0];
-    for (int k = 1; k < 4; k++) { ms = sh_ms[k] > ms ? sh_ms[k] : ms; mo = sh_mo[k] > mo ? sh_mo[k] : mo; }
+    base[0] = sh_s[0] + sh_s[1] + sh_s[2] + sh_s[3];
+    base[1] = sh_o[0] + sh_o[1] + sh_o[2] + sh_o[3];
+    mx[0] = sh_ms[0]; mx[1] = sh_mo[0];
+    for (int k = 1; k < 4; k++) { mx[0] = sh_ms[k] > mx[0] ? sh_ms[k] : mx[0]; mx[1] = sh_mo[k] > mx[1] ? sh_mo[k] : mx[1]; }
     s = 0; o = 0; xs = 0; xo = 0;
     for (uint32_t r = 0, i = 0; r < P.R; r++) {
         if (!((S.geo.live >> r) & 1u)) continue;
-        for (uint32_t g = g_block0 + lane; g < g_wave0; g += 64) {
+        for (uint32_t g = w.gb0 + w.lane; g < w.gw0; g += 64) {
             uint32_t ns, no;
             snap_count<PACK>(P, par, S, r, i, g, ns, no);
             s += ns; o += no; xs = ns > xs ? ns : xs; xo = no > xo ? no : xo;
         }
         i++;
     }
-    bs += snap_wave_sum(s); bo += snap_wave_sum(o);
-    xs = wave_max(xs); xo = wave_max(xo);
-    ms = xs > ms ? xs : ms; mo = xo > mo ? xo : mo;
+    base[0] += snap_wave_sum(s); base[1] += snap_wave_sum(o);
+    xs = snap_wave_max(xs); xo = snap_wave_max(xo);
+    mx[0] = xs > mx[0] ? xs : mx[0]; mx[1] = xo > mx[1] ? xo : mx[1];
 }
 
-// one (tile, replica): scalars, then the slot rows, then the outbox rows.  bs / bo: record index of the unit's first slot /
+// one (tile, replica): scalars, then the slot rows, then the outbox rows.  base: record index of the unit's first slot /
 // outbox record on entry, of the next unit's on return
-__device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const SnapImg &S, uint32_t r, uint32_t i, uint32_t tile, uint64_t &bs,
-                                               uint64_t &bo, uint32_t &ms, uint32_t &mo) {
+__device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const SnapImg &S, uint32_t r, uint32_t i, uint32_t tile,
+                                               uint64_t (&base)[2], uint32_t (&mx)[2]) {
     const SnapGeom &Q = S.geo;
     const uint32_t lane = threadIdx.x & 63u, g = tile * 64 + lane;
     const bool in = g < P.G;
@@ -246,51 +236,36 @@ __device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const
     }
     uint32_t n = in ? len - start : 0u;
     if (n > P.W) n = P.W;
-    const uint32_t maxn = wave_max(n), maxo = wave_max(nob);
-    ms = maxn > ms ? maxn : ms; mo = maxo > mo ? maxo : mo;
     SnapSlot *const recs = (SnapSlot *)(S.base + Q.fixed);
-    for (uint32_t k = 0; k < maxn; k++) {
-        const bool act = k < n;
-        const unsigned long long mask = __ballot(act);
-        if (act) {
-            const uint32_t slot = start + k;
-            const size_t t = tix(P.W, slot & P.Wmask, g);
-            const uint32_t val = v.s_val()[t];
-            uint32_t m = v.s_meta()[t];
-            uint64_t bal = v.s_bal()[t];
-            mp_slot_stored(slot, brun, leader, r, cbar, bms, val, bal, m);
-            const bool vs = mp_meta_voted_side(m), lx = mp_meta_lbkx(m), rx = mp_meta_rbkx(m);
-            const SnapSlot c = mp_slot_canon(m, bal, val, vs ? v.s_vbal()[t] : 0ull, vs ? v.s_vval()[t] : 0u, lx ? v.s_pmax()[t] : 0ull,
-                                             lx ? v.s_ltrig()[t] : 0u, lx ? v.s_lendp()[t] : 0u, rx ? v.s_rtrig()[t] : 0u,
-                                             rx ? v.s_rendp()[t] : 0u);
-            const uint64_t pos = bs + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (pos < S.cap_slots) recs[pos] = c;
-        }
-        bs += (uint64_t)__popcll(mask);
-    }
+    const uint32_t maxn = snap_place(n, base[0], S.cap_slots, lane, [&](uint32_t k, uint64_t pos) {
+        const uint32_t slot = start + k;
+        const size_t t = tix(P.W, slot & P.Wmask, g);
+        const uint32_t val = v.s_val()[t];
+        uint32_t m = v.s_meta()[t];
+        uint64_t bal = v.s_bal()[t];
+        mp_slot_stored(slot, brun, leader, r, cbar, bms, val, bal, m);
+        const bool vs = mp_meta_voted_side(m), lx = mp_meta_lbkx(m), rx = mp_meta_rbkx(m);
+        recs[pos] = mp_slot_canon(m, bal, val, vs ? v.s_vbal()[t] : 0ull, vs ? v.s_vval()[t] : 0u, lx ? v.s_pmax()[t] : 0ull,
+                                  lx ? v.s_ltrig()[t] : 0u, lx ? v.s_lendp()[t] : 0u, rx ? v.s_rtrig()[t] : 0u, rx ? v.s_rendp()[t] : 0u);
+    });
     SnapMsg *const msgs = (SnapMsg *)(S.base + snap_off_msgs(S));
     const uint32_t reg = (in && nob) ? v.ob_reg(par)[g] : 0u;       // a pure append run stores no ob_slot / ob_bal (Lane::ob_end_run)
     const uint64_t rbal = reg ? v.ob_rbal(par)[g] : 0ull;
-    for (uint32_t j = 0; j < maxo; j++) {
-        const bool act = j < nob;
-        const unsigned long long mask = __ballot(act);
-        if (act) {
-            const size_t o = tix(P.cap, j, g);
-            SnapMsg e;
-            e.slot = reg ? ((OB_ACCEPT << OB_KIND_SH) | ((reg - 1 + j) & OB_SLOT_MASK)) : v.ob_slot(par)[o];
-            e.bal = reg ? rbal : v.ob_bal(par)[o];
-            e.val = v.ob_val(par)[o];
-            e.aux = (e.slot >> OB_KIND_SH) == OB_HEARTBEAT ? v.ob_aux(par)[o] : 0u;
-            e.pad = 0;
-            const uint64_t pos = bo + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (pos < S.cap_ob) msgs[pos] = e;
-        }
-        bo += (uint64_t)__popcll(mask);
-    }
+    const uint32_t maxo = snap_place(nob, base[1], S.cap_ob, lane, [&](uint32_t j, uint64_t pos) {
+        const size_t o = tix(P.cap, j, g);
+        SnapMsg e;
+        e.slot = reg ? ((OB_ACCEPT << OB_KIND_SH) | ((reg - 1 + j) & OB_SLOT_MASK)) : v.ob_slot(par)[o];
+        e.bal = reg ? rbal : v.ob_bal(par)[o];
+        e.val = v.ob_val(par)[o];
+        e.aux = (e.slot >> OB_KIND_SH) == OB_HEARTBEAT ? v.ob_aux(par)[o] : 0u;
+        e.pad = 0;
+        msgs[pos] = e;
+    });
+    mx[0] = maxn > mx[0] ? maxn : mx[0]; mx[1] = maxo > mx[1] ? maxo : mx[1];
 }
 
 __device__ __forceinline__ void snap_unpack_unit(const MpParams &P, int par, const SnapImg &S, uint32_t r, uint32_t i, uint32_t tile,
-                                                 uint64_t &bs, uint64_t &bo) {
+                                                 uint64_t (&base)[2]) {
     const SnapGeom &Q = S.geo;
     const uint32_t lane = threadIdx.x & 63u, g = tile * 64 + lane;
     const bool in = g < P.G;
@@ -314,51 +289,36 @@ __device__ __forceinline__ void snap_unpack_unit(const MpParams &P, int par, con
     }
     uint32_t n = in ? len - start : 0u;
     if (n > P.W) n = P.W;
-    const uint32_t maxn = wave_max(n), maxo = wave_max(nob);
     const SnapSlot *const recs = (const SnapSlot *)(S.base + Q.fixed);
     uint32_t nlb = SNAP_NONE;                                    // first Null at or above exec_bar (MpRep::null_lb), else the log end
-    for (uint32_t k = 0; k < maxn; k++) {
-        const bool act = k < n;
-        const unsigned long long mask = __ballot(act);
-        const uint64_t pos = bs + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-        if (act && pos < S.cap_slots) {
-            const uint32_t slot = start + k;
-            const size_t t = tix(P.W, slot & P.Wmask, g);
-            const SnapSlot c = recs[pos];
-            bool vs, lx, rx;
-            const uint32_t m = mp_slot_meta(c, vs, lx, rx);
-            v.s_bal()[t] = c.bal; v.s_val()[t] = c.reqs; v.s_meta()[t] = m;
-            if (vs) { v.s_vbal()[t] = c.vbal; v.s_vval()[t] = c.vreqs; }
-            if (lx) { v.s_pmax()[t] = c.pmax; v.s_ltrig()[t] = c.ltrig; v.s_lendp()[t] = c.lendp; }
-            if (rx) { v.s_rtrig()[t] = c.rtrig; v.s_rendp()[t] = c.rendp; }
-            if (nlb == SNAP_NONE && slot >= ebar && (m & M_STATUS) == SMR_ST_NULL) nlb = slot;
-        }
-        bs += (uint64_t)__popcll(mask);
-    }
+    snap_place(n, base[0], S.cap_slots, lane, [&](uint32_t k, uint64_t pos) {
+        const uint32_t slot = start + k;
+        const size_t t = tix(P.W, slot & P.Wmask, g);
+        const SnapSlot c = recs[pos];
+        bool vs, lx, rx;
+        const uint32_t m = mp_slot_meta(c, vs, lx, rx);
+        v.s_bal()[t] = c.bal; v.s_val()[t] = c.reqs; v.s_meta()[t] = m;
+        if (vs) { v.s_vbal()[t] = c.vbal; v.s_vval()[t] = c.vreqs; }
+        if (lx) { v.s_pmax()[t] = c.pmax; v.s_ltrig()[t] = c.ltrig; v.s_lendp()[t] = c.lendp; }
+        if (rx) { v.s_rtrig()[t] = c.rtrig; v.s_rendp()[t] = c.rendp; }
+        if (nlb == SNAP_NONE && slot >= ebar && (m & M_STATUS) == SMR_ST_NULL) nlb = slot;
+    });
     if (in) v.null_lb()[g] = nlb == SNAP_NONE ? len : nlb;
     const SnapMsg *const msgs = (const SnapMsg *)(S.base + snap_off_msgs(S));
-    for (uint32_t j = 0; j < maxo; j++) {
-        const bool act = j < nob;
-        const unsigned long long mask = __ballot(act);
-        const uint64_t pos = bo + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-        if (act && pos < S.cap_ob) {
-            const size_t o = tix(P.cap, j, g);
-            const SnapMsg e = msgs[pos];
-            v.ob_slot(par)[o] = e.slot; v.ob_bal(par)[o] = e.bal; v.ob_val(par)[o] = e.val;
-            if ((e.slot >> OB_KIND_SH) == OB_HEARTBEAT) v.ob_aux(par)[o] = e.aux;
-        }
-        bo += (uint64_t)__popcll(mask);
-    }
+    snap_place(nob, base[1], S.cap_ob, lane, [&](uint32_t j, uint64_t pos) {
+        const size_t o = tix(P.cap, j, g);
+        const SnapMsg e = msgs[pos];
+        v.ob_slot(par)[o] = e.slot; v.ob_bal(par)[o] = e.bal; v.ob_val(par)[o] = e.val;
+        if ((e.slot >> OB_KIND_SH) == OB_HEARTBEAT) v.ob_aux(par)[o] = e.aux;
+    });
 }
 
 // counters (block 0) and the committed-slot entries not yet polled (the whole grid), replica after replica
 template <bool PACK>
 __device__ __forceinline__ void snap_lists(const MpParams &P, const SnapImg &S, uint64_t &n_commits, uint32_t &max_commits) {
-    static_assert(SMR_CTR_SHARDS == 256, "one thread of block 0 per counter shard");
     const SnapGeom &Q = S.geo;
     unsigned long long *const cl = (unsigned long long *)(S.base + snap_off_clist(S));
     const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x, nth = (uint64_t)gridDim.x * 256;
-    const uint32_t lane = threadIdx.x & 63u;
     uint64_t off = 0;
     max_commits = 0;
     for (uint32_t r = 0, i = 0; r < P.R; r++) {
@@ -371,23 +331,15 @@ __device__ __forceinline__ void snap_lists(const MpParams &P, const SnapImg &S, 
             carried = total < P.clist_cap ? total : P.clist_cap;
             for (uint64_t k = tid; k < carried; k += nth)
                 if (off + k < S.cap_cl) cl[off + k] = v.clist()[k];
-            if (blockIdx.x == 0 && threadIdx.x < 64) {           // the counters' shards summed (smr_common.h)
-                unsigned long long x[3] = {0, 0, 0};
-                for (uint32_t sh = lane; sh < SMR_CTR_SHARDS; sh += 64)
-                    for (int k = 0; k < 3; k++) x[k] += v.counters()[(size_t)sh * SMR_CTR_STRIDE + k];
-                for (int k = 0; k < 3; k++) x[k] = snap_wave_sum(x[k]);
-                if (lane == 0) { rp->counters[0] = x[0]; rp->counters[1] = x[1]; rp->counters[2] = x[2]; rp->clist_total = total; rp->clist_carried = carried; }
-            }
+            snap_counters_save<3>(v.counters(), rp->counters);
+            if (blockIdx.x == 0 && threadIdx.x == 0) { rp->clist_total = total; rp->clist_carried = carried; }
         } else {
             total = rp->clist_total;
             carried = rp->clist_carried < P.clist_cap ? rp->clist_carried : P.clist_cap;
             for (uint64_t k = tid; k < carried; k += nth)
                 if (off + k < S.cap_cl) v.clist()[k] = cl[off + k];
-            if (blockIdx.x == 0) {                               // the sums into shard 0, the other shards (and the debug words) zero
-                for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++)
-                    v.counters()[(size_t)threadIdx.x * SMR_CTR_STRIDE + k] = (threadIdx.x == 0 && k < 3) ? rp->counters[k] : 0ull;
-                if (threadIdx.x == 0) *v.clist_n() = (unsigned int)total;
-            }
+            snap_counters_load<3>(rp->counters, v.counters());   // (and the shards' debug words zero)
+            if (blockIdx.x == 0 && threadIdx.x == 0) *v.clist_n() = (unsigned int)total;
         }
         off += carried;
         max_commits = carried > max_commits ? (uint32_t)carried : max_commits;
@@ -399,50 +351,43 @@ __device__ __forceinline__ void snap_lists(const MpParams &P, const SnapImg &S, 
 __global__ __launch_bounds__(256) void mp_snap_pack(const MpParams *__restrict__ Pp, int par, const SnapImg S) {
     const MpParams &P = *Pp;
     const SnapGeom &Q = S.geo;
-    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
-    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
-    const uint32_t gb0 = tb0 * 64 < P.G ? tb0 * 64 : P.G, gw0 = t0 * 64 < P.G ? t0 * 64 : P.G;
-    uint64_t bs, bo;
-    uint32_t ms, mo;
-    snap_bases<true>(P, par, S, gb0, gw0, bs, bo, ms, mo);
-    for (uint32_t t = t0; t < t1; t++)
+    const SnapWave w = snap_wave(Q.tiles, P.G);
+    uint64_t base[2];                                            // slot, outbox records in front
+    uint32_t mx[2];
+    mp_snap_bases<true>(P, par, S, w, base, mx);
+    for (uint32_t t = w.t0; t < w.t1; t++)
         for (uint32_t r = 0, i = 0; r < P.R; r++) {
             if (!((Q.live >> r) & 1u)) continue;
-            snap_pack_unit(P, par, S, r, i, t, bs, bo, ms, mo);
+            snap_pack_unit(P, par, S, r, i, t, base, mx);
             i++;
         }
     uint64_t n_commits;
     uint32_t max_commits;
     snap_lists<true>(P, S, n_commits, max_commits);
-    if (t0 < Q.ntile && t1 == Q.ntile && lane == 0) {            // the wavefront of the last tile knows the totals
+    if (w.last && w.lane == 0) {                                 // the wavefront of the last tile knows the totals
         SnapHdr h;
         h.magic = SNAP_MAGIC; h.version = SNAP_VERSION;
         h.n_groups = P.G; h.population = (uint8_t)P.R; h.commit_extra = (uint8_t)S.commit_extra; h.live_mask = (uint8_t)Q.live; h.reserved0 = 0;
-        h.n_slots = bs; h.n_outbox = bo; h.n_commits = n_commits;
-        h.bytes = Q.fixed + bs * sizeof(SnapSlot) + bo * sizeof(SnapMsg) + n_commits * 8;
-        h.max_live = ms; h.max_outbox = mo; h.max_commits = max_commits; h.reserved1 = 0;
+        h.n_slots = base[0]; h.n_outbox = base[1]; h.n_commits = n_commits;
+        h.bytes = Q.fixed + base[0] * sizeof(SnapSlot) + base[1] * sizeof(SnapMsg) + n_commits * 8;
+        h.max_live = mx[0]; h.max_outbox = mx[1]; h.max_commits = max_commits; h.reserved1 = 0;
         *(SnapHdr *)S.base = h;
-        for (uint64_t p = P.G; p < snap_a8(P.G); p++) S.base[Q.off_ovf + p] = 0;             // padding is zero
-        for (uint32_t i = 0; i < Q.L; i++)
-            for (uint64_t p = Q.o_leader + P.G; p < Q.scal_stride; p++) S.base[Q.off_scal + (uint64_t)i * Q.scal_stride + p] = 0;
+        snap_zero_pad(S.base, Q.off_ovf, P.G);                   // padding is zero
+        for (uint32_t i = 0; i < Q.L; i++) snap_zero_pad(S.base, Q.off_scal + (uint64_t)i * Q.scal_stride, Q.o_leader + P.G);
     }
 }
 
 __global__ __launch_bounds__(256) void mp_snap_unpack(const MpParams *__restrict__ Pp, int par, const SnapImg S) {
     const MpParams &P = *Pp;
     const SnapGeom &Q = S.geo;
-    const uint32_t wv = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
-    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
-    const uint32_t gb0 = tb0 * 64 < P.G ? tb0 * 64 : P.G, gw0 = t0 * 64 < P.G ? t0 * 64 : P.G;
-    uint64_t bs, bo;
-    uint32_t ms, mo;
-    snap_bases<false>(P, par, S, gb0, gw0, bs, bo, ms, mo);
-    for (uint32_t t = t0; t < t1; t++)
+    const SnapWave w = snap_wave(Q.tiles, P.G);
+    uint64_t base[2];
+    uint32_t mx[2];
+    mp_snap_bases<false>(P, par, S, w, base, mx);
+    for (uint32_t t = w.t0; t < w.t1; t++)
         for (uint32_t r = 0, i = 0; r < P.R; r++) {
             if (!((Q.live >> r) & 1u)) continue;
-            snap_unpack_unit(P, par, S, r, i, t, bs, bo);
+            snap_unpack_unit(P, par, S, r, i, t, base);
             i++;
         }
     uint64_t n_commits;

@@ -20,21 +20,12 @@
 //                                                    the row).  An aliased shard's bytes are carried once, in the REQS cell.
 // The image is dense: the device buffer holds exactly the exported bytes.
 #pragma once
-#include "smr_common.h"
-
-#ifndef SMR_HD
-#if defined(__HIPCC__)
-#define SMR_HD __host__ __device__ __forceinline__
-#else
-#define SMR_HD inline
-#endif
-#endif
+#include "snapshot_common.h"
 
 namespace smr {
 
 constexpr uint32_t PSSNAP_MAGIC = 0x42505253u;      // "SRPB"
 constexpr uint32_t PSSNAP_VERSION = 1;
-constexpr uint32_t PSSNAP_MAX_WAVES = 1024;          // wavefronts of the header launch; each takes a contiguous piece of the group tiles
 constexpr uint32_t PSSNAP_BYTE_BLOCKS = 2048;        // of the byte launch (a grid-stride loop over (cell, shard), a wavefront each)
 
 struct PsSnapHdr {
@@ -45,8 +36,6 @@ struct PsSnapHdr {
 };
 static_assert(sizeof(PsSnapHdr) == 64, "image header");
 
-SMR_HD uint64_t pssnap_a8(uint64_t x) { return (x + 7) & ~(uint64_t)7; }
-SMR_HD uint64_t pssnap_a16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
 // the one place that knows what a cell contributes to the shard section: its shards that are present and not aliases, each
 // ceil(dlen / d) bytes padded to 16 (shared by the kernels and the import's checks)
 SMR_HD uint32_t pssnap_shard_len(uint32_t dlen, uint32_t d) { return (dlen + d - 1) / d; }
@@ -54,41 +43,37 @@ SMR_HD uint32_t pssnap_stored(uint32_t avail, uint32_t alias) { return avail & ~
 SMR_HD uint64_t pssnap_cell_bytes(uint32_t stored, uint32_t dlen, uint32_t d) {
     uint32_t n = 0;
     for (uint32_t k = 0; k < 8; k++) n += (stored >> k) & 1u;
-    return (uint64_t)n * pssnap_a16(pssnap_shard_len(dlen, d));
+    return (uint64_t)n * snap_a16(pssnap_shard_len(dlen, d));
 }
 
 struct PsSnapGeom {
-    uint32_t G, W, planes, ntile, tpw, nwave, nblock;
+    uint32_t G, W, planes;
+    SnapTiles tiles;
     uint64_t cells, off_ctr, o_tok[2], o_dlen[2], o_avail[2], o_alias, hdr_end, fixed;
 };
 SMR_HD PsSnapGeom pssnap_geom(uint32_t G, uint32_t W, uint32_t planes) {
     PsSnapGeom q;
-    q.G = G; q.W = W; q.planes = planes;
-    q.ntile = (G + 63) / 64;
-    q.tpw = (q.ntile + PSSNAP_MAX_WAVES - 1) / PSSNAP_MAX_WAVES;
-    q.nwave = (q.ntile + q.tpw - 1) / q.tpw;
-    q.nblock = (q.nwave + 3) / 4;
+    q.G = G; q.W = W; q.planes = planes; q.tiles = snap_tiles(G);
     q.cells = (uint64_t)G * W;
     q.off_ctr = sizeof(PsSnapHdr);
     uint64_t off = q.off_ctr + 5 * 8;
     for (uint32_t p = 0; p < 2; p++) {
-        q.o_tok[p] = off; if (p < planes) off += pssnap_a8(4 * q.cells);
-        q.o_dlen[p] = off; if (p < planes) off += pssnap_a8(4 * q.cells);
-        q.o_avail[p] = off; if (p < planes) off += pssnap_a8(q.cells);
+        q.o_tok[p] = off; if (p < planes) off += snap_a8(4 * q.cells);
+        q.o_dlen[p] = off; if (p < planes) off += snap_a8(4 * q.cells);
+        q.o_avail[p] = off; if (p < planes) off += snap_a8(q.cells);
     }
-    q.o_alias = off; if (planes == 2) off += pssnap_a8(q.cells);
+    q.o_alias = off; if (planes == 2) off += snap_a8(q.cells);
     q.hdr_end = off;
-    q.fixed = pssnap_a16(off);
+    q.fixed = snap_a16(off);
     return q;
 }
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // Two launches each way, no host read-back between them.
-//   (1) ps_snap_head: lane = group, a wavefront = a contiguous piece of the 64-group tiles, 4 wavefronts a block, by the scheme of
-//       mp_snapshot.h: the block sums the byte totals of the groups in front of its own tiles itself (no block
-//       waits for another), the wavefront adds the tiles of its block in front of its own; inside a tile, per (plane, row), a
-//       prefix over the 64 lanes gives every cell the offset of its first stored shard (cell_off, a scratch array of the snapshot,
-//       not part of the image).  The same pass moves the cell headers (canonical) and, from the last tile, writes the image header.
+//   (1) ps_snap_head: snapshot_common.h's tiles and bases, summing the groups' byte totals; inside a tile, per
+//       (plane, row), a prefix over the 64 lanes gives every cell the offset of its first stored shard (cell_off, a scratch array
+//       of the snapshot, not part of the image) -- cells differ in size, so this is a scan where the other images count lanes.
+//       The same pass moves the cell headers (canonical) and, from the last tile, writes the image header.
 //   (2) ps_snap_bytes: shaped like ps_bytes_kernel -- one wavefront per (cell, shard), one lane per 16-byte column, 16-byte loads
 //       and stores on both sides; every byte offset is 64-bit.
 struct PsSnapArgs {
@@ -99,15 +84,6 @@ struct PsSnapArgs {
     uint32_t craft;
     PsSnapGeom geo;
 };
-
-__device__ __forceinline__ uint64_t pssnap_wave_sum(uint64_t x) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ uint32_t pssnap_wave_max(uint32_t x) {
-    for (int off = 32; off > 0; off >>= 1) { const uint32_t y = __shfl_xor(x, off); x = y > x ? y : x; }
-    return x;
-}
 
 struct PsSnapCell { uint32_t tok, dlen, avail, alias; };
 // cell i of plane P: the store's own, canonical (PACK), or the image's
@@ -127,50 +103,25 @@ __device__ __forceinline__ PsSnapCell pssnap_cell(const PsSnapArgs &A, size_t i)
     }
     return c;
 }
-struct PsSnapSums { uint64_t bytes, cells, shards; uint32_t max_dlen; };
+// what the launch sums over groups: the shard bytes (a cell's offset), and for a save's header the cells with a token, the shards
+// stored and (mx[]) the longest payload; a load has those in the image and sums the bytes alone
+enum { PS_BYTES = 0, PS_CELLS = 1, PS_SHARDS = 2 };
 template <bool PACK, int P>
-__device__ __forceinline__ void pssnap_add_group(const PsSnapArgs &A, uint32_t g, PsSnapSums &s) {
+__device__ __forceinline__ void pssnap_add_group(const PsSnapArgs &A, uint32_t g, uint64_t (&sum)[PACK ? 3 : 1], uint32_t (&mx)[1]) {
     for (uint32_t r = 0; r < A.geo.W; r++) {
         const PsSnapCell c = pssnap_cell<PACK, P>(A, (size_t)r * A.geo.G + g);
         const uint32_t st = pssnap_stored(c.avail, c.alias);
-        s.bytes += pssnap_cell_bytes(st, c.dlen, A.v.d);
-        s.cells += c.tok != PS_NULL ? 1u : 0u; s.shards += (uint32_t)__popc(st);
-        s.max_dlen = c.dlen > s.max_dlen ? c.dlen : s.max_dlen;
+        sum[PS_BYTES] += pssnap_cell_bytes(st, c.dlen, A.v.d);
+        if constexpr (PACK) {
+            sum[PS_CELLS] += c.tok != PS_NULL ? 1u : 0u; sum[PS_SHARDS] += (uint32_t)__popc(st);
+            mx[0] = c.dlen > mx[0] ? c.dlen : mx[0];
+        }
     }
-}
-template <bool PACK>
-__device__ __forceinline__ void pssnap_add_groups(const PsSnapArgs &A, uint32_t g0, uint32_t g1, uint32_t step, PsSnapSums &s) {
-    for (uint32_t g = g0; g < g1; g += step) {
-        pssnap_add_group<PACK, 0>(A, g, s);
-        if (A.geo.planes == 2) pssnap_add_group<PACK, 1>(A, g, s);
-    }
-}
-__device__ __forceinline__ void pssnap_wave_reduce(PsSnapSums &s) {
-    s.bytes = pssnap_wave_sum(s.bytes); s.cells = pssnap_wave_sum(s.cells); s.shards = pssnap_wave_sum(s.shards); s.max_dlen = pssnap_wave_max(s.max_dlen);
-}
-// sums over the groups [0, g_wave0); g_block0 <= g_wave0 is the same for the whole block
-template <bool PACK>
-__device__ __forceinline__ PsSnapSums pssnap_bases(const PsSnapArgs &A, uint32_t g_block0, uint32_t g_wave0) {
-    __shared__ uint64_t sh_b[4], sh_c[4], sh_s[4];
-    __shared__ uint32_t sh_m[4];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    PsSnapSums s{0, 0, 0, 0};
-    pssnap_add_groups<PACK>(A, threadIdx.x, g_block0, 256, s);
-    pssnap_wave_reduce(s);
-    if (lane == 0) { sh_b[w] = s.bytes; sh_c[w] = s.cells; sh_s[w] = s.shards; sh_m[w] = s.max_dlen; }
-    __syncthreads();
-    PsSnapSums t{sh_b[0] + sh_b[1] + sh_b[2] + sh_b[3], sh_c[0] + sh_c[1] + sh_c[2] + sh_c[3], sh_s[0] + sh_s[1] + sh_s[2] + sh_s[3], sh_m[0]};
-    for (int k = 1; k < 4; k++) t.max_dlen = sh_m[k] > t.max_dlen ? sh_m[k] : t.max_dlen;
-    PsSnapSums u{0, 0, 0, 0};
-    pssnap_add_groups<PACK>(A, g_block0 + lane, g_wave0, 64, u);
-    pssnap_wave_reduce(u);
-    t.bytes += u.bytes; t.cells += u.cells; t.shards += u.shards; t.max_dlen = u.max_dlen > t.max_dlen ? u.max_dlen : t.max_dlen;
-    return t;
 }
 
 // one (plane, row) of a tile: the headers across, the cells' offsets from a prefix over the lanes
 template <bool PACK, int P>
-__device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r, uint32_t g, bool in, uint32_t lane, PsSnapSums &run, PsSnapSums &mine) {
+__device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r, uint32_t g, bool in, uint32_t lane, uint64_t &run_bytes, uint64_t (&mine)[3], uint32_t (&mine_mx)[1]) {
     const PsSnapGeom &Q = A.geo;
     const size_t i = (size_t)r * Q.G + (in ? g : 0u);
     uint64_t c = 0;
@@ -187,72 +138,63 @@ __device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r,
         }
         const uint32_t st = pssnap_stored(x.avail, x.alias);
         c = pssnap_cell_bytes(st, x.dlen, A.v.d);
-        mine.cells += x.tok != PS_NULL ? 1u : 0u; mine.shards += (uint32_t)__popc(st);
-        mine.max_dlen = x.dlen > mine.max_dlen ? x.dlen : mine.max_dlen;
+        if (PACK) {                                              // (the header's counts: a load has them in the image)
+            mine[PS_CELLS] += x.tok != PS_NULL ? 1u : 0u; mine[PS_SHARDS] += (uint32_t)__popc(st);
+            mine_mx[0] = x.dlen > mine_mx[0] ? x.dlen : mine_mx[0];
+        }
     }
     uint64_t incl = c;
     for (uint32_t off = 1; off < 64; off <<= 1) {
         const uint64_t y = __shfl(incl, (int)(lane >= off ? lane - off : lane));
         if (lane >= off) incl += y;
     }
-    if (in) A.cell_off[((size_t)P * Q.W + r) * Q.G + g] = run.bytes + (incl - c);
-    run.bytes += __shfl(incl, 63);
+    if (in) A.cell_off[((size_t)P * Q.W + r) * Q.G + g] = run_bytes + (incl - c);
+    run_bytes += __shfl(incl, 63);
 }
 
 template <bool PACK>
 __global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) {
     const PsSnapGeom &Q = A.geo;
     const PsView &v = A.v;
-    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
-    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
-    const uint32_t gb0 = tb0 * 64 < Q.G ? tb0 * 64 : Q.G, gw0 = t0 * 64 < Q.G ? t0 * 64 : Q.G;
-    PsSnapSums run = pssnap_bases<PACK>(A, gb0, gw0);
-    PsSnapSums mine{0, 0, 0, 0};
-    for (uint32_t t = t0; t < t1; t++) {
-        const uint32_t g = t * 64 + lane;
+    const SnapWave w = snap_wave(Q.tiles, Q.G);
+    constexpr int NS = PACK ? 3 : 1;
+    uint64_t run[NS], mine[3] = {0, 0, 0};                       // in front of this wavefront's tiles; inside them (bytes: in run)
+    uint32_t run_mx[1], mine_mx[1] = {0};
+    snap_bases(
+        [&](uint32_t g, uint64_t (&add)[NS], uint32_t (&m)[1]) {
+            pssnap_add_group<PACK, 0>(A, g, add, m);
+            if (A.geo.planes == 2) pssnap_add_group<PACK, 1>(A, g, add, m);
+        },
+        w.gb0, w.gw0, run, run_mx);
+    for (uint32_t t = w.t0; t < w.t1; t++) {
+        const uint32_t g = t * 64 + w.lane;
         const bool in = g < Q.G;
-        for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 0>(A, r, g, in, lane, run, mine);
+        for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 0>(A, r, g, in, w.lane, run[PS_BYTES], mine, mine_mx);
         if (Q.planes == 2)
-            for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 1>(A, r, g, in, lane, run, mine);
+            for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 1>(A, r, g, in, w.lane, run[PS_BYTES], mine, mine_mx);
     }
-    static_assert(SMR_CTR_SHARDS == 256, "one thread of block 0 per counter shard");
-    if (PACK) {
-        if (blockIdx.x == 0 && threadIdx.x < 64) {               // the counters' shards summed (smr_common.h)
-            unsigned long long x0 = 0, x1 = 0, x2 = 0, x3 = 0, x4 = 0;
-            for (uint32_t sh = lane; sh < SMR_CTR_SHARDS; sh += 64) {
-                const unsigned long long *c = v.counters + (size_t)sh * SMR_CTR_STRIDE;
-                x0 += c[0]; x1 += c[1]; x2 += c[2]; x3 += c[3]; x4 += c[4];
-            }
-            x0 = pssnap_wave_sum(x0); x1 = pssnap_wave_sum(x1); x2 = pssnap_wave_sum(x2); x3 = pssnap_wave_sum(x3); x4 = pssnap_wave_sum(x4);
-            if (lane == 0) {
-                uint64_t *c = (uint64_t *)(A.img + Q.off_ctr);
-                c[0] = x0; c[1] = x1; c[2] = x2; c[3] = x3; c[4] = x4;
-            }
-        }
-        if (t0 < Q.ntile && t1 == Q.ntile) {                     // the wavefront of the last tile knows the totals
-            pssnap_wave_reduce(mine);
-            if (lane == 0) {
+    if constexpr (PACK) {
+        snap_counters_save<5>(v.counters, (uint64_t *)(A.img + Q.off_ctr));
+        if (w.last) {                                            // the wavefront of the last tile knows the totals
+            const uint64_t cells = run[PS_CELLS] + snap_wave_sum(mine[PS_CELLS]), shards = run[PS_SHARDS] + snap_wave_sum(mine[PS_SHARDS]);
+            const uint32_t mdl = snap_wave_max(mine_mx[0]);
+            if (w.lane == 0) {
                 PsSnapHdr h;
                 h.magic = PSSNAP_MAGIC; h.version = PSSNAP_VERSION; h.n_groups = Q.G; h.window = Q.W;
                 h.n_shards = (uint8_t)v.n; h.n_data_shards = (uint8_t)v.d; h.planes = (uint8_t)Q.planes; h.craft = (uint8_t)A.craft;
-                h.max_dlen = mine.max_dlen > run.max_dlen ? mine.max_dlen : run.max_dlen;
-                h.n_cells = run.cells + mine.cells; h.n_shards_stored = run.shards + mine.shards; h.shard_bytes = run.bytes;
-                h.bytes = Q.fixed + run.bytes; h.reserved = 0;
+                h.max_dlen = mdl > run_mx[0] ? mdl : run_mx[0];
+                h.n_cells = cells; h.n_shards_stored = shards; h.shard_bytes = run[PS_BYTES];
+                h.bytes = Q.fixed + run[PS_BYTES]; h.reserved = 0;
                 *(PsSnapHdr *)A.img = h;
                 for (uint32_t p = 0; p < Q.planes; p++) {        // padding is zero
-                    for (uint64_t b = Q.o_tok[p] + 4 * Q.cells; b < Q.o_dlen[p]; b++) A.img[b] = 0;
-                    for (uint64_t b = Q.o_dlen[p] + 4 * Q.cells; b < Q.o_avail[p]; b++) A.img[b] = 0;
-                    for (uint64_t b = Q.o_avail[p] + Q.cells; b < Q.o_avail[p] + pssnap_a8(Q.cells); b++) A.img[b] = 0;
+                    snap_zero_pad(A.img, Q.o_tok[p], 4 * Q.cells); snap_zero_pad(A.img, Q.o_dlen[p], 4 * Q.cells); snap_zero_pad(A.img, Q.o_avail[p], Q.cells);
                 }
-                if (Q.planes == 2)
-                    for (uint64_t b = Q.o_alias + Q.cells; b < Q.hdr_end; b++) A.img[b] = 0;
-                for (uint64_t b = Q.hdr_end; b < Q.fixed; b++) A.img[b] = 0;
+                if (Q.planes == 2) snap_zero_pad(A.img, Q.o_alias, Q.cells);
+                for (uint64_t b = Q.hdr_end; b < Q.fixed; b++) A.img[b] = 0;     // (up to the shard section's multiple of 16)
             }
         }
-    } else if (blockIdx.x == 0) {                                // the sums into shard 0, the other shards zero
-        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++)
-            v.counters[(size_t)threadIdx.x * SMR_CTR_STRIDE + k] = (threadIdx.x == 0 && k < 5) ? ((const uint64_t *)(A.img + Q.off_ctr))[k] : 0ull;
+    } else {
+        snap_counters_load<5>((const uint64_t *)(A.img + Q.off_ctr), v.counters);
     }
 }
 
@@ -276,7 +218,7 @@ __global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) {
         const uint32_t stored = pssnap_stored(avail, alias);
         if (!((stored >> k) & 1u)) continue;
         const uint32_t dlen = ((const uint32_t *)(A.img + (p1 ? Q.o_dlen[1] : Q.o_dlen[0])))[i];
-        const uint32_t sl = pssnap_shard_len(dlen, v.d), sl16 = (uint32_t)pssnap_a16(sl);
+        const uint32_t sl = pssnap_shard_len(dlen, v.d), sl16 = (uint32_t)snap_a16(sl);
         const uint64_t off = A.cell_off[ci64] + (uint64_t)__popc(stored & ((1u << k) - 1u)) * sl16;
         if (sl16 > v.cap_sl || off + sl16 > A.cap_bytes) continue;                    // (refused by the host / cannot happen)
         const uint32_t row = (uint32_t)(i / Q.G), g = (uint32_t)(i - (size_t)row * Q.G);

@@ -1736,45 +1736,40 @@ int smr_raft_cluster_tick(smr_raft_leader *leader, const uint32_t *n_new_dev, ui
 struct smr_raft_snapshot {
     uint32_t G = 0;
     uint8_t R = 0, me = 0, commit_extra = 0, craft = 0, ft = 0, rep_thr = 0;
-    int device = -1;
-    uint8_t *dev = nullptr;
+    SnapBuf buf;
     uint64_t cap_e = 0, cap_rq = 0;                              // records the device buffer's sections have room for
-    bool filled = false, hdr_known = false;                      // a save / import has run; `hdr` is the image's header
-    RaftSnapHdr hdr;
+    RaftSnapHdr hdr;                                             // the image's header, once buf.hdr_known
 };
 
 namespace smr {
+static const char *const RSNAP = "raft snapshot: ";
 static RaftSnapGeom rsnap_geom_of(const smr_raft_snapshot *s) { return rsnap_geom(s->G, s->R, s->craft != 0); }
+static RaftSnapImg rsnap_img(const smr_raft_snapshot *s) { return RaftSnapImg{s->buf.dev, s->cap_e, s->cap_rq}; }
 static int rsnap_alloc(smr_raft_snapshot *s, uint64_t cap_e, uint64_t cap_rq) {
-    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
     s->cap_e = cap_e; s->cap_rq = cap_rq;
-    const RaftSnapImg S{nullptr, cap_e, cap_rq};
-    hipError_t e = hipMalloc((void **)&s->dev, rsnap_dev_bytes(rsnap_geom_of(s), S));
-    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("raft snapshot: hipMalloc: ") + hipGetErrorString(e)); }
-    return SMR_OK;
+    return snap_buf_alloc(s->buf, rsnap_dev_bytes(rsnap_geom_of(s), rsnap_img(s)), RSNAP);
 }
 // room for the worst case of a replica with l's window: every ring row live, a full Reconstruct queue.  A save can then never
 // find the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica
 // with a larger window is saved into it.
 static int rsnap_room(smr_raft_snapshot *s, const smr_raft_leader *l) {
     const uint64_t ne = (uint64_t)s->G * l->cfg.window, nq = s->craft ? (uint64_t)s->G * CRAFT_RQ : 0;
-    if (s->dev && ne <= s->cap_e && nq <= s->cap_rq) return SMR_OK;
-    s->filled = false; s->hdr_known = false;                     // (what it held goes with the old buffer)
+    if (s->buf.dev && ne <= s->cap_e && nq <= s->cap_rq) return SMR_OK;
+    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
     return rsnap_alloc(s, ne > s->cap_e ? ne : s->cap_e, nq > s->cap_rq ? nq : s->cap_rq);
 }
 // the image's header on the host (synchronises once after a save)
 static int rsnap_header(smr_raft_snapshot *s) {
-    if (!s->filled) return fail(SMR_ERR_STATE, "raft snapshot: nothing saved or imported yet");
-    if (s->hdr_known) return SMR_OK;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(RaftSnapHdr), hipMemcpyDeviceToHost));
-    // (cannot happen: the kernel's counts are bounded by the window and queue length the room was made for)
-    if (s->hdr.n_entries > s->cap_e || s->hdr.n_rq > s->cap_rq) {
-        s->filled = false;
-        return fail(SMR_ERR_STATE, "raft snapshot: the saved state exceeds the snapshot's room");
-    }
-    s->hdr_known = true;
-    return SMR_OK;
+    return snap_buf_header(s->buf, s->hdr, RSNAP, [s](const RaftSnapHdr &h) { return h.n_entries <= s->cap_e && h.n_rq <= s->cap_rq; });
+}
+// the image of header h between the device buffer (sections at their capacities) and packed host bytes; plain Raft has the
+// entry terms alone
+static int rsnap_copy(const smr_raft_snapshot *s, uint8_t *host, const RaftSnapHdr &h, bool to_host) {
+    const RaftSnapGeom q = rsnap_geom_of(s);
+    const RaftSnapImg S = rsnap_img(s);
+    const uint64_t rq = s->craft ? h.n_rq * sizeof(RaftSnapRq) : 0, mask = s->craft ? h.n_entries : 0;
+    return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
+                              {{q.fixed, h.n_entries * 8, h.n_entries * 8}, {rsnap_off_rq(q, S), rq, rq}, {rsnap_off_mask(q, S), mask, snap_a8(mask)}});
 }
 static bool rsnap_like(const smr_raft_snapshot *s, const smr_raft_leader *l) {
     return s->G == l->cfg.n_groups && s->R == l->cfg.population && s->me == l->cfg.leader_id && s->commit_extra == l->cfg.commit_extra &&
@@ -1788,21 +1783,17 @@ static const char *const RSNAP_OTHER = "another n_groups / population / replica 
 
 // the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
 static int rsnap_setup(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, bool load, RaftSnapArgs &A) {
-    if (!reps || !snaps) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
-    if (n == 0 || n > RMAX) return fail(SMR_ERR_ARG, "raft snapshot: 1 .. 8 replicas");
+    if (int rc = snap_pairs_check(n, reps, snaps, RSNAP, [&](uint32_t k) {
+            const smr_raft_leader *l = reps[k];
+            const smr_raft_snapshot *s = snaps[k];
+            if (l->v.G != reps[0]->v.G || l->v.R != reps[0]->v.R || l->craft != reps[0]->craft)
+                return fail(SMR_ERR_ARG, "raft snapshot: the replicas differ in groups / population / variant");
+            if (l->device != reps[0]->device || s->buf.device != l->device) return fail(SMR_ERR_ARG, "raft snapshot: a replica or snapshot lives on another device");
+            if (!rsnap_like(s, l)) return fail(SMR_ERR_ARG, std::string("raft snapshot: made for ") + RSNAP_OTHER);
+            if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, "raft snapshot: a replica has no device copy of its view");
+            return (int)SMR_OK;
+        })) return rc;
     memset(&A, 0, sizeof(A));
-    for (uint32_t k = 0; k < n; k++) {
-        smr_raft_leader *l = reps[k];
-        smr_raft_snapshot *s = snaps[k];
-        if (!l || !s) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
-        for (uint32_t j = 0; j < k; j++)
-            if (reps[j] == l || snaps[j] == s) return fail(SMR_ERR_ARG, "raft snapshot: a replica or a snapshot is listed twice");
-        if (l->v.G != reps[0]->v.G || l->v.R != reps[0]->v.R || l->craft != reps[0]->craft)
-            return fail(SMR_ERR_ARG, "raft snapshot: the replicas differ in groups / population / variant");
-        if (l->device != reps[0]->device || s->device != l->device) return fail(SMR_ERR_ARG, "raft snapshot: a replica or snapshot lives on another device");
-        if (!rsnap_like(s, l)) return fail(SMR_ERR_ARG, std::string("raft snapshot: made for ") + RSNAP_OTHER);
-        if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, "raft snapshot: a replica has no device copy of its view");
-    }
     for (uint32_t k = 0; k < n; k++) {
         smr_raft_leader *l = reps[k];
         smr_raft_snapshot *s = snaps[k];
@@ -1816,7 +1807,7 @@ static int rsnap_setup(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapsh
     }
     A.geo = rsnap_geom(reps[0]->v.G, reps[0]->v.R, reps[0]->craft);
     for (uint32_t k = 0; k < n; k++) {
-        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.img[k] = snaps[k]->dev; A.cap_e[k] = snaps[k]->cap_e; A.cap_rq[k] = snaps[k]->cap_rq;
+        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.img[k] = snaps[k]->buf.dev; A.cap_e[k] = snaps[k]->cap_e; A.cap_rq[k] = snaps[k]->cap_rq;
         A.commit_extra[k] = reps[k]->cfg.commit_extra;
     }
     return SMR_OK;
@@ -1830,7 +1821,7 @@ int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **ou
     smr_raft_snapshot *s = new smr_raft_snapshot();
     s->G = like->cfg.n_groups; s->R = like->cfg.population; s->me = like->cfg.leader_id; s->commit_extra = like->cfg.commit_extra;
     s->craft = like->craft ? 1 : 0; s->ft = like->craft ? (uint8_t)like->cv.ft : 0; s->rep_thr = like->craft ? (uint8_t)like->cv.rep_thr : 0;
-    s->device = like->device;
+    s->buf.device = like->device;
     memset(&s->hdr, 0, sizeof(s->hdr));
     if (int rc = rsnap_room(s, like)) { delete s; return rc; }
     *out = s;
@@ -1839,23 +1830,23 @@ int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **ou
 
 void smr_raft_snapshot_destroy(smr_raft_snapshot *s) {
     if (!s) return;
-    if (s->dev) { (void)hipDeviceSynchronize(); (void)hipFree(s->dev); }
+    snap_buf_free(s->buf);
     delete s;
 }
 
 int smr_raft_cluster_save_state(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, void *stream) {
     RaftSnapArgs A;
     if (int rc = rsnap_setup(n, reps, snaps, false, A)) return rc;
-    hipLaunchKernelGGL(raft_snap_pack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(raft_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n; k++) { snaps[k]->filled = true; snaps[k]->hdr_known = false; }
+    for (uint32_t k = 0; k < n; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
     return SMR_OK;
 }
 
 int smr_raft_cluster_load_state(uint32_t n, smr_raft_leader *const *reps, const smr_raft_snapshot *const *snaps, void *stream) {
     RaftSnapArgs A;                                              // (a snapshot's header is read back and cached on first use)
     if (int rc = rsnap_setup(n, reps, const_cast<smr_raft_snapshot *const *>(snaps), true, A)) return rc;
-    hipLaunchKernelGGL(raft_snap_unpack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(raft_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
 }
@@ -1896,35 +1887,20 @@ int64_t smr_raft_snapshot_export(const smr_raft_snapshot *cs, uint8_t *host, uin
     if (int rc = rsnap_header(s)) return rc;
     const RaftSnapHdr &h = s->hdr;
     if (cap < h.bytes) return fail(SMR_ERR_ARG, "raft snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    const RaftSnapGeom q = rsnap_geom_of(s);
-    const RaftSnapImg S{s->dev, s->cap_e, s->cap_rq};
-    uint8_t *p = host;
-    SMR_HIP_TRY(hipMemcpy(p, s->dev, q.fixed, hipMemcpyDeviceToHost)); p += q.fixed;
-    if (h.n_entries) SMR_HIP_TRY(hipMemcpy(p, s->dev + q.fixed, h.n_entries * 8, hipMemcpyDeviceToHost));
-    p += h.n_entries * 8;
-    if (s->craft) {
-        if (h.n_rq) SMR_HIP_TRY(hipMemcpy(p, s->dev + rsnap_off_rq(q, S), h.n_rq * sizeof(RaftSnapRq), hipMemcpyDeviceToHost));
-        p += h.n_rq * sizeof(RaftSnapRq);
-        if (h.n_entries) SMR_HIP_TRY(hipMemcpy(p, s->dev + rsnap_off_mask(q, S), h.n_entries, hipMemcpyDeviceToHost));
-        memset(p + h.n_entries, 0, rsnap_a8(h.n_entries) - h.n_entries);
-    }
+    if (int rc = rsnap_copy(s, host, h, true)) return rc;
     return (int64_t)h.bytes;
 }
 
 int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
-    if (len < sizeof(RaftSnapHdr)) return fail(SMR_ERR_ARG, "raft snapshot: image shorter than its header");
     RaftSnapHdr h;
-    memcpy(&h, host, sizeof(h));
-    if (h.magic != RSNAP_MAGIC) return fail(SMR_ERR_ARG, "raft snapshot: not a snapshot image (magic)");
-    if (h.version != RSNAP_VERSION)
-        return fail(SMR_ERR_ARG, "raft snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(RSNAP_VERSION));
+    if (int rc = snap_import_prologue(host, len, RSNAP_MAGIC, RSNAP_VERSION, RSNAP, h)) return rc;
     if (h.me >= h.population) return fail(SMR_ERR_ARG, "raft snapshot: the image's replica id is not below its population");
     bool res = h.reserved1 != 0;
     for (int k = 0; k < 6; k++) res = res || h.reserved0[k];
     if (!rsnap_hdr_like(h, s) || res) return fail(SMR_ERR_ARG, std::string("raft snapshot: the image is of ") + RSNAP_OTHER);
     const RaftSnapGeom q = rsnap_geom_of(s);
-    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed) return fail(SMR_ERR_ARG, "raft snapshot: truncated image");
+    if (snap_truncated(len, q.fixed, h.bytes)) return fail(SMR_ERR_ARG, "raft snapshot: truncated image");
     const uint64_t room = h.bytes - q.fixed;                      // the record sections; each count bounded before it is multiplied
     if (h.n_entries > room / 8 || h.n_rq > room / sizeof(RaftSnapRq) || (!s->craft && h.n_rq) || rsnap_bytes(q, h.n_entries, h.n_rq) != h.bytes)
         return fail(SMR_ERR_ARG, "raft snapshot: the header's counts do not add up to the image's size");
@@ -1952,8 +1928,7 @@ int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t
             n_rq += nq; max_rq = nq > max_rq ? nq : max_rq;
         }
     }
-    for (uint64_t p = q.scal_end; p < rsnap_a8(q.scal_end); p++) if (b[p]) return bad("padding is not zero");
-    if (s->craft) for (uint64_t p = q.craft_end; p < rsnap_a8(q.craft_end); p++) if (c[p]) return bad("padding is not zero");
+    if (!snap_pad_is_zero(b, 0, q.scal_end) || (s->craft && !snap_pad_is_zero(c, 0, q.craft_end))) return bad("padding is not zero");
     if (n_e != h.n_entries || n_rq != h.n_rq || max_live != h.max_live || max_rq != h.max_rq) return bad("the header's counts and maxima contradict the body");
     const uint8_t *p = host + q.fixed + h.n_entries * 8;
     if (s->craft) {
@@ -1963,23 +1938,14 @@ int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t
             if (e.pad) return bad("Reconstruct queue record");
         }
         for (uint64_t k = 0; k < h.n_entries; k++) if (p[k] >> s->R) return bad("shard bitmap of replicas beyond the population");
-        for (uint64_t k = h.n_entries; k < rsnap_a8(h.n_entries); k++) if (p[k]) return bad("padding is not zero");
+        if (!snap_pad_is_zero(p, 0, h.n_entries)) return bad("padding is not zero");
     }
     if (h.n_entries > s->cap_e || h.n_rq > s->cap_rq)
         if (int rc = rsnap_alloc(s, h.n_entries > s->cap_e ? h.n_entries : s->cap_e, h.n_rq > s->cap_rq ? h.n_rq : s->cap_rq)) return rc;
     SMR_HIP_TRY(hipDeviceSynchronize());
-    s->filled = false;
-    const RaftSnapImg S{s->dev, s->cap_e, s->cap_rq};
-    p = host;
-    SMR_HIP_TRY(hipMemcpy(s->dev, p, q.fixed, hipMemcpyHostToDevice)); p += q.fixed;
-    if (h.n_entries) SMR_HIP_TRY(hipMemcpy(s->dev + q.fixed, p, h.n_entries * 8, hipMemcpyHostToDevice));
-    p += h.n_entries * 8;
-    if (s->craft) {
-        if (h.n_rq) SMR_HIP_TRY(hipMemcpy(s->dev + rsnap_off_rq(q, S), p, h.n_rq * sizeof(RaftSnapRq), hipMemcpyHostToDevice));
-        p += h.n_rq * sizeof(RaftSnapRq);
-        if (h.n_entries) SMR_HIP_TRY(hipMemcpy(s->dev + rsnap_off_mask(q, S), p, h.n_entries, hipMemcpyHostToDevice));
-    }
-    s->hdr = h; s->filled = true; s->hdr_known = true;
+    s->buf.filled = false;
+    if (int rc = rsnap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
+    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
     return SMR_OK;
 }
 

@@ -29,21 +29,12 @@
 // without the window it came from.  On the device the record sections sit at fixed capacities behind the fixed part; export
 // closes the gaps.
 #pragma once
-#include "smr_common.h"
-
-#ifndef SMR_HD
-#if defined(__HIPCC__)
-#define SMR_HD __host__ __device__ __forceinline__
-#else
-#define SMR_HD inline
-#endif
-#endif
+#include "snapshot_common.h"
 
 namespace smr {
 
 constexpr uint32_t RSNAP_MAGIC = 0x53465253u;      // "SRFS"
 constexpr uint32_t RSNAP_VERSION = 1;
-constexpr uint32_t RSNAP_MAX_WAVES = 1024;          // wavefronts of a launch per replica; each takes a contiguous piece of the group tiles
 constexpr uint32_t RSNAP_MAX_LOG = 1u << 20;        // no window is larger
 
 struct RaftSnapHdr {
@@ -72,19 +63,15 @@ SMR_HD uint32_t raft_live_n(uint32_t start, uint32_t rlo, uint32_t len, uint32_t
 
 // ---- where things are in an image ---------------------------------------------------------------------------------------
 struct RaftSnapGeom {
-    uint32_t G, R, craft, ntile, tpw, nwave, nblock;
+    uint32_t G, R, craft;
+    SnapTiles tiles;
     uint64_t off_ctr, off_scal, off_craft, fixed;
     uint64_t o_term, o_len, o_start, o_commit, o_snap, o_rlo, o_nexec, o_ntrunc, o_next, o_try, o_match, o_role, o_leader, o_voted, o_votes, scal_end;
     uint64_t c_hbr, c_hbs, c_lrecon, c_rqn, c_hbrep, c_full, c_alive, c_partial, craft_end;
 };
-SMR_HD uint64_t rsnap_a8(uint64_t x) { return (x + 7) & ~(uint64_t)7; }
 SMR_HD RaftSnapGeom rsnap_geom(uint32_t G, uint32_t R, bool craft) {
     RaftSnapGeom q;
-    q.G = G; q.R = R; q.craft = craft ? 1u : 0u;
-    q.ntile = (G + 63) / 64;
-    q.tpw = (q.ntile + RSNAP_MAX_WAVES - 1) / RSNAP_MAX_WAVES;
-    q.nwave = (q.ntile + q.tpw - 1) / q.tpw;
-    q.nblock = (q.nwave + 3) / 4;
+    q.G = G; q.R = R; q.craft = craft ? 1u : 0u; q.tiles = snap_tiles(G);
     const uint64_t g = G, gr = (uint64_t)G * R;
     q.off_ctr = sizeof(RaftSnapHdr);
     q.off_scal = q.off_ctr + 8 * 8;
@@ -92,10 +79,10 @@ SMR_HD RaftSnapGeom rsnap_geom(uint32_t G, uint32_t R, bool craft) {
     q.o_ntrunc = 32 * g; q.o_next = 36 * g; q.o_try = q.o_next + 4 * gr; q.o_match = q.o_try + 4 * gr;
     q.o_role = q.o_match + 4 * gr; q.o_leader = q.o_role + g; q.o_voted = q.o_leader + g; q.o_votes = q.o_voted + g;
     q.scal_end = q.o_votes + g;
-    q.off_craft = q.off_scal + rsnap_a8(q.scal_end);
+    q.off_craft = q.off_scal + snap_a8(q.scal_end);
     q.c_hbr = 0; q.c_hbs = 8 * gr; q.c_lrecon = 16 * gr; q.c_rqn = q.c_lrecon + 4 * g; q.c_hbrep = q.c_rqn + 4 * g;
     q.c_full = q.c_hbrep + gr; q.c_alive = q.c_full + g; q.c_partial = q.c_alive + g; q.craft_end = q.c_partial + g;
-    q.fixed = q.off_craft + (craft ? rsnap_a8(q.craft_end) : 0);
+    q.fixed = q.off_craft + (craft ? snap_a8(q.craft_end) : 0);
     return q;
 }
 // one replica's image on the device: the fixed part, then room for cap_e entry terms, cap_rq queue records, cap_e masks
@@ -105,9 +92,9 @@ struct RaftSnapImg {
 };
 SMR_HD uint64_t rsnap_off_rq(const RaftSnapGeom &q, const RaftSnapImg &S) { return q.fixed + S.cap_e * 8; }
 SMR_HD uint64_t rsnap_off_mask(const RaftSnapGeom &q, const RaftSnapImg &S) { return rsnap_off_rq(q, S) + S.cap_rq * sizeof(RaftSnapRq); }
-SMR_HD uint64_t rsnap_dev_bytes(const RaftSnapGeom &q, const RaftSnapImg &S) { return rsnap_off_mask(q, S) + (q.craft ? rsnap_a8(S.cap_e) : 0); }
+SMR_HD uint64_t rsnap_dev_bytes(const RaftSnapGeom &q, const RaftSnapImg &S) { return rsnap_off_mask(q, S) + (q.craft ? snap_a8(S.cap_e) : 0); }
 SMR_HD uint64_t rsnap_bytes(const RaftSnapGeom &q, uint64_t n_e, uint64_t n_rq) {
-    return q.fixed + n_e * 8 + (q.craft ? n_rq * sizeof(RaftSnapRq) + rsnap_a8(n_e) : 0);
+    return q.fixed + n_e * 8 + (q.craft ? n_rq * sizeof(RaftSnapRq) + snap_a8(n_e) : 0);
 }
 
 // the scalar arrays inside an image
@@ -136,11 +123,8 @@ SMR_HD RaftSnapScal rsnap_scal(uint8_t *base, const RaftSnapGeom &q) {
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1); the replicas are reached
-// through the device copies of their views, as smr_raft_cluster_replicate's followers are.  Lane = group, a wavefront = a
-// contiguous piece of the 64-group tiles, 4 wavefronts a block.  A record's place follows from the live counts of every group
-// in front of it, by the scheme of mp_snapshot.h: the block sums the groups in front of its own tiles itself
-// (12 to 16 B per group out of the L2: no block waits for another), the wavefront adds the tiles of its block in front of its
-// own, and inside a tile a row's records go to the lanes that hold one, packed (ballot + prefix count).
+// through the device copies of their views, as smr_raft_cluster_replicate's followers are.  Tiles, bases and placement are
+// snapshot_common.h's; a group's counts cost the bases 12 to 16 B out of the L2.
 struct RaftSnapArgs {
     const RaftView *rv[RMAX];
     const CraftView *cv[RMAX];
@@ -150,60 +134,25 @@ struct RaftSnapArgs {
     RaftSnapGeom geo;
 };
 
-__device__ __forceinline__ uint64_t rsnap_wave_sum(uint64_t x) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-__device__ __forceinline__ uint32_t rsnap_wave_max(uint32_t x) {
-    for (int off = 32; off > 0; off >>= 1) { const uint32_t y = __shfl_xor(x, off); x = y > x ? y : x; }
-    return x;
-}
-
-// live entries and queued Reconstruct slots of group g: the replica's own (PACK) or the image's
+// live entries and queued Reconstruct slots in front of a wavefront: the replica's own (PACK) or the image's
 template <bool PACK>
-__device__ __forceinline__ void rsnap_count(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, uint32_t g, uint32_t &ne,
-                                            uint32_t &nq) {
-    if (PACK) {
-        ne = raft_live_n(v.start_slot[g], v.ring_lo[g], v.log_len[g], v.W);
-        nq = craft ? cv.rq_n[g] : 0u;
-    } else {
-        ne = raft_live_n(sc.start[g], sc.rlo[g], sc.len[g], RSNAP_MAX_LOG);
-        if (ne > v.W) ne = v.W;                              // (load has refused such an image: max_live <= window)
-        nq = craft ? sc.rqn[g] : 0u;
-    }
-    if (nq > CRAFT_RQ) nq = CRAFT_RQ;
-}
-
-// sums and maxima over the groups [0, g_wave0); g_block0 <= g_wave0 is the same for the whole block
-template <bool PACK>
-__device__ __forceinline__ void rsnap_bases(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, uint32_t g_block0,
-                                            uint32_t g_wave0, uint64_t &be, uint64_t &bq, uint32_t &me_, uint32_t &mq) {
-    __shared__ uint64_t sh_e[4], sh_q[4];
-    __shared__ uint32_t sh_me[4], sh_mq[4];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint64_t e = 0, q = 0;
-    uint32_t xe = 0, xq = 0;
-    for (uint32_t g = threadIdx.x; g < g_block0; g += 256) {
-        uint32_t ne, nq;
-        rsnap_count<PACK>(v, cv, craft, sc, g, ne, nq);
-        e += ne; q += nq; xe = ne > xe ? ne : xe; xq = nq > xq ? nq : xq;
-    }
-    e = rsnap_wave_sum(e); q = rsnap_wave_sum(q); xe = rsnap_wave_max(xe); xq = rsnap_wave_max(xq);
-    if (lane == 0) { sh_e[w] = e; sh_q[w] = q; sh_me[w] = xe; sh_mq[w] = xq; }
-    __syncthreads();
-    be = sh_e[0] + sh_e[1] + sh_e[2] + sh_e[3];
-    bq = sh_q[0] + sh_q[1] + sh_q[2] + sh_q[3];
-    me_ = sh_me[0]; mq = sh_mq[0];
-    for (int k = 1; k < 4; k++) { me_ = sh_me[k] > me_ ? sh_me[k] : me_; mq = sh_mq[k] > mq ? sh_mq[k] : mq; }
-    e = 0; q = 0; xe = 0; xq = 0;
-    for (uint32_t g = g_block0 + lane; g < g_wave0; g += 64) {
-        uint32_t ne, nq;
-        rsnap_count<PACK>(v, cv, craft, sc, g, ne, nq);
-        e += ne; q += nq; xe = ne > xe ? ne : xe; xq = nq > xq ? nq : xq;
-    }
-    be += rsnap_wave_sum(e); bq += rsnap_wave_sum(q);
-    xe = rsnap_wave_max(xe); xq = rsnap_wave_max(xq);
-    me_ = xe > me_ ? xe : me_; mq = xq > mq ? xq : mq;
+__device__ __forceinline__ void rsnap_bases(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, const SnapWave &w,
+                                            uint64_t (&base)[2], uint32_t (&mx)[2]) {
+    snap_bases(
+        [&](uint32_t g, uint64_t (&add)[2], uint32_t (&m)[2]) {
+            uint32_t ne, nq;
+            if (PACK) {
+                ne = raft_live_n(v.start_slot[g], v.ring_lo[g], v.log_len[g], v.W);
+                nq = craft ? cv.rq_n[g] : 0u;
+            } else {
+                ne = raft_live_n(sc.start[g], sc.rlo[g], sc.len[g], RSNAP_MAX_LOG);
+                if (ne > v.W) ne = v.W;                          // (load has refused such an image: max_live <= window)
+                nq = craft ? sc.rqn[g] : 0u;
+            }
+            if (nq > CRAFT_RQ) nq = CRAFT_RQ;
+            add[0] += ne; add[1] += nq; m[0] = ne > m[0] ? ne : m[0]; m[1] = nq > m[1] ? nq : m[1];
+        },
+        w.gb0, w.gw0, base, mx);
 }
 
 // the replica of this block: views in registers, the image's descriptor
@@ -236,22 +185,18 @@ __global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
     const RaftSnapImg &S = X.S;
     const bool craft = Q.craft != 0;
     const RaftSnapScal sc = rsnap_scal(S.base, Q);
-    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
-    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
-    const uint32_t gb0 = tb0 * 64 < v.G ? tb0 * 64 : v.G, gw0 = t0 * 64 < v.G ? t0 * 64 : v.G;
+    const SnapWave w = snap_wave(Q.tiles, v.G);
     const size_t G = v.G;
-    uint64_t be, bq;
-    uint32_t mx_e, mx_q;
-    rsnap_bases<true>(v, cv, craft, sc, gb0, gw0, be, bq, mx_e, mx_q);
+    uint64_t base[2];                                            // entries, queue records in front
+    uint32_t mx[2];
+    rsnap_bases<true>(v, cv, craft, sc, w, base, mx);
     uint64_t *const terms = (uint64_t *)(S.base + Q.fixed);
     RaftSnapRq *const rqs = (RaftSnapRq *)(S.base + rsnap_off_rq(Q, S));
     uint8_t *const masks = S.base + rsnap_off_mask(Q, S);
-    for (uint32_t t = t0; t < t1; t++) {
-        const uint32_t g = t * 64 + lane;
-        const bool in = g < v.G;
+    for (uint32_t t = w.t0; t < w.t1; t++) {
+        const uint32_t g = t * 64 + w.lane;
         uint32_t n = 0, lo = 0, nq = 0;
-        if (in) {
+        if (g < v.G) {
             const uint32_t len = v.log_len[g], start = v.start_slot[g], rlo = raft_ring_lo(v.ring_lo[g], len, v.W);
             lo = raft_live_lo(start, rlo, len, v.W); n = len > lo ? len - lo : 0u;
             sc.term[g] = v.curr_term[g]; sc.len[g] = len; sc.start[g] = start; sc.commit[g] = v.last_commit[g]; sc.snap[g] = v.last_snap[g];
@@ -273,56 +218,33 @@ __global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
                 }
             }
         }
-        const uint32_t maxn = rsnap_wave_max(n), maxq = rsnap_wave_max(nq);
-        mx_e = maxn > mx_e ? maxn : mx_e; mx_q = maxq > mx_q ? maxq : mx_q;
-        for (uint32_t k = 0; k < maxn; k++) {
-            const bool act = k < n;
-            const unsigned long long mask = __ballot(act);
-            if (act) {
-                const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
-                const uint64_t pos = be + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-                if (pos < S.cap_e) {
-                    terms[pos] = v.entry_term[i];
-                    if (craft) masks[pos] = v.entry_mask[i];
-                }
-            }
-            be += (uint64_t)__popcll(mask);
-        }
-        for (uint32_t j = 0; j < maxq; j++) {
-            const bool act = j < nq;
-            const unsigned long long mask = __ballot(act);
-            if (act) {
-                const size_t i = (size_t)j * G + g;
-                RaftSnapRq e;
-                e.term = cv.rq_term[i]; e.slot = cv.rq_slot[i]; e.pad = 0;
-                const uint64_t pos = bq + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-                if (pos < S.cap_rq) rqs[pos] = e;
-            }
-            bq += (uint64_t)__popcll(mask);
-        }
+        const uint32_t maxn = snap_place(n, base[0], S.cap_e, w.lane, [&](uint32_t k, uint64_t pos) {
+            const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
+            terms[pos] = v.entry_term[i];
+            if (craft) masks[pos] = v.entry_mask[i];
+        });
+        const uint32_t maxq = snap_place(nq, base[1], S.cap_rq, w.lane, [&](uint32_t j, uint64_t pos) {
+            const size_t i = (size_t)j * G + g;
+            RaftSnapRq e;
+            e.term = cv.rq_term[i]; e.slot = cv.rq_slot[i]; e.pad = 0;
+            rqs[pos] = e;
+        });
+        mx[0] = maxn > mx[0] ? maxn : mx[0]; mx[1] = maxq > mx[1] ? maxq : mx[1];
     }
-    if (blockIdx.x == 0 && threadIdx.x < 64) {                   // the counters' shards summed (smr_common.h)
-        unsigned long long x[SMR_CTR_STRIDE];
-        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) x[k] = 0;
-        for (uint32_t sh = lane; sh < SMR_CTR_SHARDS; sh += 64)
-            for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) x[k] += v.counters[(size_t)sh * SMR_CTR_STRIDE + k];
-        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) x[k] = rsnap_wave_sum(x[k]);
-        if (lane == 0)
-            for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) ((uint64_t *)(S.base + Q.off_ctr))[k] = x[k];
-    }
-    if (t0 < Q.ntile && t1 == Q.ntile && lane == 0) {            // the wavefront of the last tile knows the totals
+    snap_counters_save<(int)SMR_CTR_STRIDE>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
+    if (w.last && w.lane == 0) {                                 // the wavefront of the last tile knows the totals
         RaftSnapHdr h;
         h.magic = RSNAP_MAGIC; h.version = RSNAP_VERSION;
         h.n_groups = v.G; h.population = (uint8_t)v.R; h.me = (uint8_t)v.me; h.commit_extra = (uint8_t)X.commit_extra; h.variant = craft ? 1 : 0;
         h.fault_tolerance = craft ? (uint8_t)cv.ft : (uint8_t)0; h.repeat_threshold = craft ? (uint8_t)cv.rep_thr : (uint8_t)0;
         for (int k = 0; k < 6; k++) h.reserved0[k] = 0;
-        h.n_entries = be; h.n_rq = bq; h.bytes = rsnap_bytes(Q, be, bq);
-        h.max_live = mx_e; h.max_rq = mx_q; h.reserved1 = 0;
+        h.n_entries = base[0]; h.n_rq = base[1]; h.bytes = rsnap_bytes(Q, base[0], base[1]);
+        h.max_live = mx[0]; h.max_rq = mx[1]; h.reserved1 = 0;
         *(RaftSnapHdr *)S.base = h;
-        for (uint64_t p = Q.scal_end; p < rsnap_a8(Q.scal_end); p++) S.base[Q.off_scal + p] = 0;       // padding is zero
+        snap_zero_pad(S.base, Q.off_scal, Q.scal_end);           // padding is zero
         if (craft) {
-            for (uint64_t p = Q.craft_end; p < rsnap_a8(Q.craft_end); p++) S.base[Q.off_craft + p] = 0;
-            for (uint64_t p = be; p < rsnap_a8(be); p++) if (p < rsnap_a8(S.cap_e)) masks[p] = 0;
+            snap_zero_pad(S.base, Q.off_craft, Q.craft_end);
+            snap_zero_pad(S.base, rsnap_off_mask(Q, S), base[0] < S.cap_e ? base[0] : S.cap_e);
         }
     }
 }
@@ -338,22 +260,18 @@ __global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) {
     const RaftSnapImg &S = X.S;
     const bool craft = Q.craft != 0;
     const RaftSnapScal sc = rsnap_scal(S.base, Q);
-    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t tb0 = blockIdx.x * 4 * Q.tpw, t0 = wv * Q.tpw;
-    const uint32_t t1 = t0 + Q.tpw < Q.ntile ? t0 + Q.tpw : Q.ntile;
-    const uint32_t gb0 = tb0 * 64 < v.G ? tb0 * 64 : v.G, gw0 = t0 * 64 < v.G ? t0 * 64 : v.G;
+    const SnapWave w = snap_wave(Q.tiles, v.G);
     const size_t G = v.G;
-    uint64_t be, bq;
-    uint32_t mx_e, mx_q;
-    rsnap_bases<false>(v, cv, craft, sc, gb0, gw0, be, bq, mx_e, mx_q);
+    uint64_t base[2];
+    uint32_t mx[2];
+    rsnap_bases<false>(v, cv, craft, sc, w, base, mx);
     const uint64_t *const terms = (const uint64_t *)(S.base + Q.fixed);
     const RaftSnapRq *const rqs = (const RaftSnapRq *)(S.base + rsnap_off_rq(Q, S));
     const uint8_t *const masks = S.base + rsnap_off_mask(Q, S);
-    for (uint32_t t = t0; t < t1; t++) {
-        const uint32_t g = t * 64 + lane;
-        const bool in = g < v.G;
+    for (uint32_t t = w.t0; t < w.t1; t++) {
+        const uint32_t g = t * 64 + w.lane;
         uint32_t n = 0, lo = 0, nq = 0;
-        if (in) {
+        if (g < v.G) {
             const uint32_t len = sc.len[g], start = sc.start[g], rlo = sc.rlo[g];
             lo = raft_live_lo(start, rlo, len, RSNAP_MAX_LOG); n = len > lo ? len - lo : 0u;
             if (n > v.W) { lo += n - v.W; n = v.W; }              // (refused by the host: max_live <= window)
@@ -376,34 +294,18 @@ __global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) {
                 }
             }
         }
-        const uint32_t maxn = rsnap_wave_max(n), maxq = rsnap_wave_max(nq);
-        for (uint32_t k = 0; k < maxn; k++) {
-            const bool act = k < n;
-            const unsigned long long mask = __ballot(act);
-            const uint64_t pos = be + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (act && pos < S.cap_e) {
-                const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
-                v.entry_term[i] = terms[pos];
-                if (craft) v.entry_mask[i] = masks[pos];
-            }
-            be += (uint64_t)__popcll(mask);
-        }
-        for (uint32_t j = 0; j < maxq; j++) {
-            const bool act = j < nq;
-            const unsigned long long mask = __ballot(act);
-            const uint64_t pos = bq + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (act && pos < S.cap_rq) {
-                const size_t i = (size_t)j * G + g;
-                const RaftSnapRq e = rqs[pos];
-                cv.rq_term[i] = e.term; cv.rq_slot[i] = e.slot;
-            }
-            bq += (uint64_t)__popcll(mask);
-        }
+        snap_place(n, base[0], S.cap_e, w.lane, [&](uint32_t k, uint64_t pos) {
+            const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
+            v.entry_term[i] = terms[pos];
+            if (craft) v.entry_mask[i] = masks[pos];
+        });
+        snap_place(nq, base[1], S.cap_rq, w.lane, [&](uint32_t j, uint64_t pos) {
+            const size_t i = (size_t)j * G + g;
+            const RaftSnapRq e = rqs[pos];
+            cv.rq_term[i] = e.term; cv.rq_slot[i] = e.slot;
+        });
     }
-    static_assert(SMR_CTR_SHARDS == 256, "one thread of block 0 per counter shard");
-    if (blockIdx.x == 0)                                         // the sums into shard 0, the other shards zero
-        for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++)
-            v.counters[(size_t)threadIdx.x * SMR_CTR_STRIDE + k] = threadIdx.x == 0 ? ((const uint64_t *)(S.base + Q.off_ctr))[k] : 0ull;
+    snap_counters_load<(int)SMR_CTR_STRIDE>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
 }
 
 }  // namespace smr

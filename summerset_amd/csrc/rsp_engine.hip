@@ -944,44 +944,37 @@ int smr_rsp_exec_poll(smr_rsp_replica *e, uint32_t *group_host, uint32_t *slot_h
 struct smr_rsp_snapshot {
     uint32_t G = 0;
     uint8_t R = 0, me = 0, ft = 0;
-    uint8_t *dev = nullptr;
+    SnapBuf buf;
     uint64_t cap_s = 0, cap_x = 0;                               // records the device buffer's sections have room for
-    bool filled = false, hdr_known = false;                      // a save / import has run; `hdr` is the image's header
-    RspSnapHdr hdr;
+    RspSnapHdr hdr;                                              // the image's header, once buf.hdr_known
 };
 
 namespace smr {
+static const char *const RSPSNAP = "rspaxos snapshot: ";
 static RspSnapGeom rspsnap_geom_of(const smr_rsp_snapshot *s) { return rspsnap_geom(s->G, s->R); }
+static RspSnapImg rspsnap_img(const smr_rsp_snapshot *s) { return RspSnapImg{s->buf.dev, s->cap_s, s->cap_x}; }
 static int rspsnap_alloc(smr_rsp_snapshot *s, uint64_t cap_s, uint64_t cap_x) {
-    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
     s->cap_s = cap_s; s->cap_x = cap_x;
-    const RspSnapImg S{nullptr, cap_s, cap_x};
-    hipError_t e = hipMalloc((void **)&s->dev, rspsnap_dev_bytes(rspsnap_geom_of(s), S));
-    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("rspaxos snapshot: hipMalloc: ") + hipGetErrorString(e)); }
-    return SMR_OK;
+    return snap_buf_alloc(s->buf, rspsnap_dev_bytes(rspsnap_geom_of(s), rspsnap_img(s)), RSPSNAP);
 }
 // room for the worst case of a replica with e's window: every ring row live, a full execution list.  A save can then never find
 // the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica with a
 // larger window is saved into it.
 static int rspsnap_room(smr_rsp_snapshot *s, const smr_rsp_replica *e) {
     const uint64_t n = (uint64_t)s->G * e->cfg.window;
-    if (s->dev && n <= s->cap_s && n <= s->cap_x) return SMR_OK;
-    s->filled = false; s->hdr_known = false;                     // (what it held goes with the old buffer)
+    if (s->buf.dev && n <= s->cap_s && n <= s->cap_x) return SMR_OK;
+    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
     return rspsnap_alloc(s, n > s->cap_s ? n : s->cap_s, n > s->cap_x ? n : s->cap_x);
 }
 // the image's header on the host (synchronises once after a save)
 static int rspsnap_header(smr_rsp_snapshot *s) {
-    if (!s->filled) return fail(SMR_ERR_STATE, "rspaxos snapshot: nothing saved or imported yet");
-    if (s->hdr_known) return SMR_OK;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(RspSnapHdr), hipMemcpyDeviceToHost));
-    // (cannot happen: the kernel's counts are bounded by the window the room was made for)
-    if (s->hdr.n_slots > s->cap_s || s->hdr.n_exec > s->cap_x) {
-        s->filled = false;
-        return fail(SMR_ERR_STATE, "rspaxos snapshot: the saved state exceeds the snapshot's room");
-    }
-    s->hdr_known = true;
-    return SMR_OK;
+    return snap_buf_header(s->buf, s->hdr, RSPSNAP, [s](const RspSnapHdr &h) { return h.n_slots <= s->cap_s && h.n_exec <= s->cap_x; });
+}
+// the image of header h between the device buffer (sections at their capacities) and packed host bytes
+static int rspsnap_copy(const smr_rsp_snapshot *s, uint8_t *host, const RspSnapHdr &h, bool to_host) {
+    const RspSnapGeom q = rspsnap_geom_of(s);
+    return snap_copy_sections(s->buf.dev, host, q.fixed, to_host, {{q.fixed, h.n_slots * sizeof(RspSnapSlot), h.n_slots * sizeof(RspSnapSlot)},
+                                                                  {rspsnap_off_exec(q, rspsnap_img(s)), h.n_exec * 4, snap_a8(h.n_exec * 4)}});
 }
 static bool rspsnap_like(const smr_rsp_snapshot *s, const smr_rsp_replica *e) {
     return s->G == e->cfg.n_groups && s->R == e->cfg.population && s->me == e->cfg.me && s->ft == e->cfg.fault_tolerance;
@@ -993,18 +986,12 @@ static const char *const RSPSNAP_OTHER = "another n_groups / population / replic
 
 // the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
 static int rspsnap_setup(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, bool load, RspSnapArgs &A) {
-    if (!reps || !snaps) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
-    if (n == 0 || n > SMR_MAX_REPLICAS) return fail(SMR_ERR_ARG, "rspaxos snapshot: 1 .. 8 replicas");
+    if (int rc = snap_pairs_check(n, reps, snaps, RSPSNAP, [&](uint32_t k) {
+            if (reps[k]->v.G != reps[0]->v.G || reps[k]->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, "rspaxos snapshot: the replicas differ in groups / population");
+            if (!rspsnap_like(snaps[k], reps[k])) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: made for ") + RSPSNAP_OTHER);
+            return (int)SMR_OK;
+        })) return rc;
     memset(&A, 0, sizeof(A));
-    for (uint32_t k = 0; k < n; k++) {
-        smr_rsp_replica *e = reps[k];
-        smr_rsp_snapshot *s = snaps[k];
-        if (!e || !s) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
-        for (uint32_t j = 0; j < k; j++)
-            if (reps[j] == e || snaps[j] == s) return fail(SMR_ERR_ARG, "rspaxos snapshot: a replica or a snapshot is listed twice");
-        if (e->v.G != reps[0]->v.G || e->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, "rspaxos snapshot: the replicas differ in groups / population");
-        if (!rspsnap_like(s, e)) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: made for ") + RSPSNAP_OTHER);
-    }
     for (uint32_t k = 0; k < n; k++) {
         smr_rsp_replica *e = reps[k];
         smr_rsp_snapshot *s = snaps[k];
@@ -1019,7 +1006,7 @@ static int rspsnap_setup(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snaps
                                                                          //  then empty, SMR_ERR_STATE on use, and none holds a partial image)
     }
     A.geo = rspsnap_geom(reps[0]->v.G, reps[0]->v.R);
-    for (uint32_t k = 0; k < n; k++) { A.v[k] = reps[k]->v; A.img[k] = snaps[k]->dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
+    for (uint32_t k = 0; k < n; k++) { A.v[k] = reps[k]->v; A.img[k] = snaps[k]->buf.dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
     return SMR_OK;
 }
 }  // namespace smr
@@ -1038,23 +1025,23 @@ int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out)
 
 void smr_rsp_snapshot_destroy(smr_rsp_snapshot *s) {
     if (!s) return;
-    if (s->dev) { (void)hipDeviceSynchronize(); (void)hipFree(s->dev); }
+    snap_buf_free(s->buf);
     delete s;
 }
 
 int smr_rsp_cluster_save_state(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, void *stream) {
     RspSnapArgs A;
     if (int rc = rspsnap_setup(n, reps, snaps, false, A)) return rc;
-    hipLaunchKernelGGL(rsp_snap_pack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(rsp_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n; k++) { snaps[k]->filled = true; snaps[k]->hdr_known = false; }
+    for (uint32_t k = 0; k < n; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
     return SMR_OK;
 }
 
 int smr_rsp_cluster_load_state(uint32_t n, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *snaps, void *stream) {
     RspSnapArgs A;                                               // (a snapshot's header is read back and cached on first use)
     if (int rc = rspsnap_setup(n, reps, const_cast<smr_rsp_snapshot *const *>(snaps), true, A)) return rc;
-    hipLaunchKernelGGL(rsp_snap_unpack, dim3(A.geo.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(rsp_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
 }
@@ -1093,31 +1080,20 @@ int64_t smr_rsp_snapshot_export(const smr_rsp_snapshot *cs, uint8_t *host, uint6
     if (int rc = rspsnap_header(s)) return rc;
     const RspSnapHdr &h = s->hdr;
     if (cap < h.bytes) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    const RspSnapGeom q = rspsnap_geom_of(s);
-    const RspSnapImg S{s->dev, s->cap_s, s->cap_x};
-    uint8_t *p = host;
-    SMR_HIP_TRY(hipMemcpy(p, s->dev, q.fixed, hipMemcpyDeviceToHost)); p += q.fixed;
-    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(p, s->dev + q.fixed, h.n_slots * sizeof(RspSnapSlot), hipMemcpyDeviceToHost));
-    p += h.n_slots * sizeof(RspSnapSlot);
-    if (h.n_exec) SMR_HIP_TRY(hipMemcpy(p, s->dev + rspsnap_off_exec(q, S), h.n_exec * 4, hipMemcpyDeviceToHost));
-    memset(p + h.n_exec * 4, 0, rspsnap_a8(h.n_exec * 4) - h.n_exec * 4);
+    if (int rc = rspsnap_copy(s, host, h, true)) return rc;
     return (int64_t)h.bytes;
 }
 
 int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
-    if (len < sizeof(RspSnapHdr)) return fail(SMR_ERR_ARG, "rspaxos snapshot: image shorter than its header");
     RspSnapHdr h;
-    memcpy(&h, host, sizeof(h));
-    if (h.magic != RSPSNAP_MAGIC) return fail(SMR_ERR_ARG, "rspaxos snapshot: not a snapshot image (magic)");
-    if (h.version != RSPSNAP_VERSION)
-        return fail(SMR_ERR_ARG, "rspaxos snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(RSPSNAP_VERSION));
+    if (int rc = snap_import_prologue(host, len, RSPSNAP_MAGIC, RSPSNAP_VERSION, RSPSNAP, h)) return rc;
     if (h.me >= h.population) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image's replica id is not below its population");
     if (!rspsnap_hdr_like(h, s) || h.reserved0 || h.reserved1 || h.reserved2) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: the image is of ") + RSPSNAP_OTHER);
     const uint32_t W = h.window;
     if (W < 8 || (W & (W - 1)) || W > RSPSNAP_MAX_WINDOW) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image's window is not a power of two in 8 .. 2^20");
     const RspSnapGeom q = rspsnap_geom_of(s);
-    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed) return fail(SMR_ERR_ARG, "rspaxos snapshot: truncated image");
+    if (snap_truncated(len, q.fixed, h.bytes)) return fail(SMR_ERR_ARG, "rspaxos snapshot: truncated image");
     const uint64_t room = h.bytes - q.fixed;                      // the record sections; each count bounded before it is multiplied
     if (h.n_slots > room / sizeof(RspSnapSlot) || h.n_exec > room / 4 || rspsnap_bytes(q, h.n_slots, h.n_exec) != h.bytes)
         return fail(SMR_ERR_ARG, "rspaxos snapshot: the header's counts do not add up to the image's size");
@@ -1138,7 +1114,7 @@ int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t l
     const uint64_t g = s->G;
     const uint64_t pads[7][2] = {{q.o_leader, g}, {q.o_len, 4 * g}, {q.o_cbar, 4 * g}, {q.o_ebar, 4 * g}, {q.o_snap, 4 * g}, {q.o_peb, 4 * g * s->R}, {q.o_xn, 4 * g}};
     for (const auto &pd : pads)
-        for (uint64_t p = pd[0] + pd[1]; p < pd[0] + rspsnap_a8(pd[1]); p++) if (host[p]) return bad("padding is not zero");
+        if (!snap_pad_is_zero(host, pd[0], pd[1])) return bad("padding is not zero");
     const uint8_t *p = host + q.fixed;
     for (uint64_t k = 0; k < h.n_slots; k++, p += sizeof(RspSnapSlot)) {
         RspSnapSlot r, c;
@@ -1159,18 +1135,13 @@ int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t l
                     if (u32at(host + q.o_xn, gg) > row && u32at(p, k++) >= u32at(host + q.o_len, gg)) return bad("an executed slot at or above the group's len");
         }
     }
-    for (uint64_t k = h.n_exec * 4; k < rspsnap_a8(h.n_exec * 4); k++) if (p[k]) return bad("padding is not zero");
+    if (!snap_pad_is_zero(p, 0, h.n_exec * 4)) return bad("padding is not zero");
     if (h.n_slots > s->cap_s || h.n_exec > s->cap_x)
         if (int rc = rspsnap_alloc(s, h.n_slots > s->cap_s ? h.n_slots : s->cap_s, h.n_exec > s->cap_x ? h.n_exec : s->cap_x)) return rc;
     SMR_HIP_TRY(hipDeviceSynchronize());
-    s->filled = false;
-    const RspSnapImg S{s->dev, s->cap_s, s->cap_x};
-    p = host;
-    SMR_HIP_TRY(hipMemcpy(s->dev, p, q.fixed, hipMemcpyHostToDevice)); p += q.fixed;
-    if (h.n_slots) SMR_HIP_TRY(hipMemcpy(s->dev + q.fixed, p, h.n_slots * sizeof(RspSnapSlot), hipMemcpyHostToDevice));
-    p += h.n_slots * sizeof(RspSnapSlot);
-    if (h.n_exec) SMR_HIP_TRY(hipMemcpy(s->dev + rspsnap_off_exec(q, S), p, h.n_exec * 4, hipMemcpyHostToDevice));
-    s->hdr = h; s->filled = true; s->hdr_known = true;
+    s->buf.filled = false;
+    if (int rc = rspsnap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
+    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
     return SMR_OK;
 }
 

@@ -1454,41 +1454,29 @@ int smr_rsp_pstore_debug_delivered(smr_rsp_pstore *s, uint64_t *out_host) {
 struct smr_rsp_pstore_snapshot {
     uint32_t G = 0, W = 0;
     uint8_t n = 0, d = 0, planes = 0, craft = 0;
-    uint8_t *dev = nullptr;                                      // the image, dense: header .. shard bytes
+    SnapBuf buf;                                                 // the image, dense: header .. shard bytes
     uint64_t *d_off = nullptr;                                   // [planes][W][G] where a cell's stored shards begin (scratch of the two launches)
     uint64_t cap_bytes = 0;                                      // room of the shard section
-    bool filled = false, hdr_known = false;
-    PsSnapHdr hdr;
+    PsSnapHdr hdr;                                               // the image's header, once buf.hdr_known
 };
 
 namespace smr {
+static const char *const PSSNAP = "pstore snapshot: ";
 static PsSnapGeom pssnap_geom_of(const smr_rsp_pstore_snapshot *s) { return pssnap_geom(s->G, s->W, s->planes); }
 static int pssnap_alloc(smr_rsp_pstore_snapshot *s, uint64_t cap_bytes) {
-    if (s->dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(s->dev); s->dev = nullptr; }
     s->cap_bytes = cap_bytes;
-    hipError_t e = hipMalloc((void **)&s->dev, pssnap_geom_of(s).fixed + cap_bytes + 16);
-    if (e != hipSuccess) { s->dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("pstore snapshot: hipMalloc: ") + hipGetErrorString(e)); }
-    return SMR_OK;
+    return snap_buf_alloc(s->buf, pssnap_geom_of(s).fixed + cap_bytes + 16, PSSNAP);
 }
 // room for the worst case of store `st`: every cell holding every shard at max_data_len -- the planes' own size.  A save can then
 // never find the snapshot too small, so it only enqueues.  Grows (host-known sizes) when a store with a larger max_data_len is saved.
 static int pssnap_room(smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
     const uint64_t need = (uint64_t)st->planes * st->plane_bytes;
-    if (s->dev && need <= s->cap_bytes) return SMR_OK;
-    s->filled = false; s->hdr_known = false;
+    if (s->buf.dev && need <= s->cap_bytes) return SMR_OK;
+    s->buf.filled = false; s->buf.hdr_known = false;
     return pssnap_alloc(s, need > s->cap_bytes ? need : s->cap_bytes);
 }
 static int pssnap_header(smr_rsp_pstore_snapshot *s) {
-    if (!s->filled) return fail(SMR_ERR_STATE, "pstore snapshot: nothing saved or imported yet");
-    if (s->hdr_known) return SMR_OK;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    SMR_HIP_TRY(hipMemcpy(&s->hdr, s->dev, sizeof(PsSnapHdr), hipMemcpyDeviceToHost));
-    if (s->hdr.shard_bytes > s->cap_bytes) {                     // (cannot happen: bounded by the planes the room was made for)
-        s->filled = false;
-        return fail(SMR_ERR_STATE, "pstore snapshot: the saved state exceeds the snapshot's room");
-    }
-    s->hdr_known = true;
-    return SMR_OK;
+    return snap_buf_header(s->buf, s->hdr, PSSNAP, [s](const PsSnapHdr &h) { return h.shard_bytes <= s->cap_bytes; });
 }
 static bool pssnap_like(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
     return s->G == st->v.G && s->W == st->v.W && s->n == st->v.n && s->d == st->v.d && s->planes == st->planes && (s->craft != 0) == st->craft_store;
@@ -1500,7 +1488,7 @@ static const char *const PSSNAP_OTHER = "another n_groups / n_shards / n_data_sh
 static PsSnapArgs pssnap_args(const smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *s) {
     PsSnapArgs A;
     memset(&A, 0, sizeof(A));
-    A.v = st->v; A.img = s->dev; A.cell_off = s->d_off; A.cap_bytes = s->cap_bytes; A.craft = s->craft; A.geo = pssnap_geom_of(s);
+    A.v = st->v; A.img = s->buf.dev; A.cell_off = s->d_off; A.cap_bytes = s->cap_bytes; A.craft = s->craft; A.geo = pssnap_geom_of(s);
     return A;
 }
 static uint32_t pssnap_byte_blocks(const PsSnapArgs &A) {
@@ -1526,8 +1514,8 @@ int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_sn
 
 void smr_rsp_pstore_snapshot_destroy(smr_rsp_pstore_snapshot *s) {
     if (!s) return;
-    if (s->dev || s->d_off) (void)hipDeviceSynchronize();
-    if (s->dev) (void)hipFree(s->dev);
+    if (s->buf.dev || s->d_off) (void)hipDeviceSynchronize();
+    if (s->buf.dev) (void)hipFree(s->buf.dev);
     if (s->d_off) (void)hipFree(s->d_off);
     delete s;
 }
@@ -1537,10 +1525,10 @@ int smr_rsp_pstore_save(smr_rsp_pstore *st, smr_rsp_pstore_snapshot *s, void *st
     if (!pssnap_like(s, st)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: made for ") + PSSNAP_OTHER);
     if (int rc = pssnap_room(s, st)) return rc;
     const PsSnapArgs A = pssnap_args(st, s);
-    hipLaunchKernelGGL(ps_snap_head<true>, dim3(A.geo.nblock), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(ps_snap_head<true>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A);
     hipLaunchKernelGGL(ps_snap_bytes<true>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    s->filled = true; s->hdr_known = false;
+    s->buf.filled = true; s->buf.hdr_known = false;
     return SMR_OK;
 }
 
@@ -1554,7 +1542,7 @@ int smr_rsp_pstore_load(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *cs, v
     if (h.max_dlen > st->max_data_len)
         return fail(SMR_ERR_ARG, "pstore snapshot: a payload of " + std::to_string(h.max_dlen) + " bytes does not fit max_data_len " + std::to_string(st->max_data_len));
     const PsSnapArgs A = pssnap_args(st, s);
-    hipLaunchKernelGGL(ps_snap_head<false>, dim3(A.geo.nblock), dim3(256), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(ps_snap_head<false>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A);
     hipLaunchKernelGGL(ps_snap_bytes<false>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1577,28 +1565,23 @@ int64_t smr_rsp_pstore_snapshot_export(const smr_rsp_pstore_snapshot *cs, uint8_
     smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
     if (int rc = pssnap_header(s)) return rc;
     if (cap < s->hdr.bytes) return fail(SMR_ERR_ARG, "pstore snapshot: the image takes " + std::to_string(s->hdr.bytes) + " bytes");
-    SMR_HIP_TRY(hipMemcpy(host, s->dev, s->hdr.bytes, hipMemcpyDeviceToHost));
+    SMR_HIP_TRY(hipMemcpy(host, s->buf.dev, s->hdr.bytes, hipMemcpyDeviceToHost));     // (the image is dense)
     return (int64_t)s->hdr.bytes;
 }
 
 int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
-    if (len < sizeof(PsSnapHdr)) return fail(SMR_ERR_ARG, "pstore snapshot: image shorter than its header");
     PsSnapHdr h;
-    memcpy(&h, host, sizeof(h));
-    if (h.magic != PSSNAP_MAGIC) return fail(SMR_ERR_ARG, "pstore snapshot: not a store image (magic)");
-    if (h.version != PSSNAP_VERSION)
-        return fail(SMR_ERR_ARG, "pstore snapshot: image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(PSSNAP_VERSION));
+    if (int rc = snap_import_prologue(host, len, PSSNAP_MAGIC, PSSNAP_VERSION, PSSNAP, h, "store")) return rc;
     if (!pssnap_hdr_like(h, s) || h.reserved) return fail(SMR_ERR_ARG, std::string("pstore snapshot: the image is of ") + PSSNAP_OTHER);
     const PsSnapGeom q = pssnap_geom_of(s);
-    if (len < q.fixed || h.bytes > len || h.bytes < q.fixed || h.bytes - q.fixed != h.shard_bytes || (h.shard_bytes & 15))
+    if (snap_truncated(len, q.fixed, h.bytes) || h.bytes - q.fixed != h.shard_bytes || (h.shard_bytes & 15))
         return fail(SMR_ERR_ARG, "pstore snapshot: truncated image, or its sizes do not add up");
     const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("pstore snapshot: malformed image: ") + what); };
     const auto u32at = [&](uint64_t off, uint64_t i) { uint32_t x; memcpy(&x, host + off + 4 * i, 4); return x; };
     for (uint32_t p = 0; p < q.planes; p++) {
-        for (uint64_t b = q.o_tok[p] + 4 * q.cells; b < q.o_dlen[p]; b++) if (host[b]) return bad("padding is not zero");
-        for (uint64_t b = q.o_dlen[p] + 4 * q.cells; b < q.o_avail[p]; b++) if (host[b]) return bad("padding is not zero");
-        for (uint64_t b = q.o_avail[p] + q.cells; b < q.o_avail[p] + pssnap_a8(q.cells); b++) if (host[b]) return bad("padding is not zero");
+        if (!snap_pad_is_zero(host, q.o_tok[p], 4 * q.cells) || !snap_pad_is_zero(host, q.o_dlen[p], 4 * q.cells) || !snap_pad_is_zero(host, q.o_avail[p], q.cells))
+            return bad("padding is not zero");
     }
     for (uint64_t b = (q.planes == 2 ? q.o_alias + q.cells : q.hdr_end); b < q.fixed; b++) if (host[b]) return bad("padding is not zero");
     // the shard section against the headers, in the image's order: tile, plane, ring row, group, shard
@@ -1620,7 +1603,7 @@ int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *ho
                     if (alias && (u32at(q.o_tok[0], i) != tok || u32at(q.o_dlen[0], i) != dlen)) return bad("an alias into a REQS cell of another token or length");
                     n_cells++; max_dlen = dlen > max_dlen ? dlen : max_dlen;
                     const uint32_t st = pssnap_stored(avail, alias), sl = pssnap_shard_len(dlen, s->d);
-                    const uint64_t sl16 = pssnap_a16(sl);
+                    const uint64_t sl16 = snap_a16(sl);
                     for (uint32_t k = 0; k < s->n; k++) {
                         if (!((st >> k) & 1u)) continue;
                         if (sl16 > h.shard_bytes - off) return bad("the headers ask for more shard bytes than the image holds");
@@ -1630,12 +1613,12 @@ int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *ho
                 }
     if (off != h.shard_bytes || n_cells != h.n_cells || n_stored != h.n_shards_stored || max_dlen != h.max_dlen)
         return bad("the header's counts contradict the cell headers");
-    if (!s->dev || h.shard_bytes > s->cap_bytes)
+    if (!s->buf.dev || h.shard_bytes > s->cap_bytes)
         if (int rc = pssnap_alloc(s, h.shard_bytes > s->cap_bytes ? h.shard_bytes : s->cap_bytes)) return rc;
     SMR_HIP_TRY(hipDeviceSynchronize());
-    s->filled = false;
-    SMR_HIP_TRY(hipMemcpy(s->dev, host, h.bytes, hipMemcpyHostToDevice));
-    s->hdr = h; s->filled = true; s->hdr_known = true;
+    s->buf.filled = false;
+    SMR_HIP_TRY(hipMemcpy(s->buf.dev, host, h.bytes, hipMemcpyHostToDevice));
+    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
     return SMR_OK;
 }
 

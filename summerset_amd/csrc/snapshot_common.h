@@ -1,0 +1,236 @@
+// What the four device-resident snapshots (mp_snapshot.h, raft_snapshot.h, rsp_snapshot.h, ps_snapshot.h) have in common: how a
+// launch is cut into tiles, how a record finds its place in an image, the sharded counters, and the host's handling of the device
+// buffer and of an image's outer checks.  The formats and the field moves stay with the engines.
+//
+// The scheme.  Lane = group, a wavefront = a contiguous piece of the 64-group tiles, 4 wavefronts a block.  A record's place in its
+// section follows from the counts of everything in front of it: the block sums the groups in front of its own tiles itself (a few
+// bytes per group out of the L2: no block waits for another), the wavefront adds the tiles of its block in front of its own
+// (snap_bases), and inside a tile a row's records go to the lanes that hold one, packed (snap_place: ballot + prefix count) -- a
+// wavefront's stores of a row are one contiguous piece.  The wavefront of the last tile ends up knowing the totals and writes the
+// header.  On the device the record sections sit at fixed capacities behind the fixed part; export closes the gaps.
+#pragma once
+#include <string.h>
+
+#include <initializer_list>
+
+#include "smr_common.h"
+
+#ifndef SMR_HD
+#if defined(__HIPCC__)
+#define SMR_HD __host__ __device__ __forceinline__
+#else
+#define SMR_HD inline
+#endif
+#endif
+
+namespace smr {
+
+SMR_HD uint64_t snap_a8(uint64_t x) { return (x + 7) & ~(uint64_t)7; }
+SMR_HD uint64_t snap_a16(uint64_t x) { return (x + 15) & ~(uint64_t)15; }
+
+// ---- the tile partition ---------------------------------------------------------------------------------------------------
+constexpr uint32_t SNAP_MAX_WAVES = 1024;          // wavefronts of a launch (per replica); each takes a contiguous piece of the group tiles
+struct SnapTiles { uint32_t ntile, tpw, nwave, nblock; };   // 64-group tiles, tiles per wavefront, wavefronts, blocks of 4 wavefronts
+SMR_HD SnapTiles snap_tiles(uint32_t G) {
+    SnapTiles t;
+    t.ntile = (G + 63) / 64;
+    t.tpw = (t.ntile + SNAP_MAX_WAVES - 1) / SNAP_MAX_WAVES;
+    t.nwave = (t.ntile + t.tpw - 1) / t.tpw;
+    t.nblock = (t.nwave + 3) / 4;
+    return t;
+}
+
+// ---- device ---------------------------------------------------------------------------------------------------------------
+// wave-wide reductions (all 64 lanes must be active)
+__device__ __forceinline__ uint64_t snap_wave_sum(uint64_t x) {
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+__device__ __forceinline__ uint32_t snap_wave_max(uint32_t x) {
+    for (int off = 32; off > 0; off >>= 1) { uint32_t y = __shfl_xor(x, off); x = y > x ? y : x; }
+    return x;
+}
+
+// this wavefront's share of a launch over G groups: its tiles [t0, t1), the first group of its block's tiles and of its own
+// (both clamped to G), and whether it holds the last tile (that wavefront knows the totals)
+struct SnapWave { uint32_t lane, t0, t1, gb0, gw0; bool last; };
+__device__ __forceinline__ SnapWave snap_wave(const SnapTiles &T, uint32_t G) {
+    const uint32_t lane = threadIdx.x & 63u, wv = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t tb0 = blockIdx.x * 4 * T.tpw, t0 = wv * T.tpw;
+    const uint32_t t1 = t0 + T.tpw < T.ntile ? t0 + T.tpw : T.ntile;
+    const uint32_t gb0 = tb0 * 64 < G ? tb0 * 64 : G, gw0 = t0 * 64 < G ? t0 * 64 : G;
+    return SnapWave{lane, t0, t1, gb0, gw0, t0 < T.ntile && t1 == T.ntile};
+}
+
+// sums and maxima over the groups [0, gw0); gb0 <= gw0 is the same for the whole block (256 threads, every one of them calls).
+// count(g, add, mx) adds group g's counts to add[NSUM] and raises mx[NMAX]; the sums are integers, so the order does not matter
+template <int NSUM, int NMAX, class Count>
+__device__ __forceinline__ void snap_bases(const Count &count, uint32_t gb0, uint32_t gw0, uint64_t (&sum)[NSUM], uint32_t (&mx)[NMAX]) {
+    __shared__ uint64_t sh_s[NSUM][4];
+    __shared__ uint32_t sh_m[NMAX][4];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t s[NSUM];
+    uint32_t m[NMAX];
+#pragma unroll
+    for (int k = 0; k < NSUM; k++) s[k] = 0;
+#pragma unroll
+    for (int k = 0; k < NMAX; k++) m[k] = 0;
+    for (uint32_t g = threadIdx.x; g < gb0; g += 256) count(g, s, m);
+#pragma unroll
+    for (int k = 0; k < NSUM; k++) s[k] = snap_wave_sum(s[k]);
+#pragma unroll
+    for (int k = 0; k < NMAX; k++) m[k] = snap_wave_max(m[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NSUM; k++) sh_s[k][w] = s[k];
+#pragma unroll
+        for (int k = 0; k < NMAX; k++) sh_m[k][w] = m[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NSUM; k++) { sum[k] = sh_s[k][0] + sh_s[k][1] + sh_s[k][2] + sh_s[k][3]; s[k] = 0; }
+#pragma unroll
+    for (int k = 0; k < NMAX; k++) {
+        mx[k] = sh_m[k][0];
+#pragma unroll
+        for (int j = 1; j < 4; j++) mx[k] = sh_m[k][j] > mx[k] ? sh_m[k][j] : mx[k];
+        m[k] = 0;
+    }
+    for (uint32_t g = gb0 + lane; g < gw0; g += 64) count(g, s, m);
+#pragma unroll
+    for (int k = 0; k < NSUM; k++) sum[k] += snap_wave_sum(s[k]);
+#pragma unroll
+    for (int k = 0; k < NMAX; k++) { const uint32_t x = snap_wave_max(m[k]); mx[k] = x > mx[k] ? x : mx[k]; }
+}
+
+// the rows of one tile: this lane's group holds n records, `base` is the section index of the tile's first one on entry and of
+// the next tile's on return.  Row k goes to the lanes with k < n, packed; body(k, pos) runs for those of them with pos < cap.
+// Returns the tile's longest row count (the header's max_* fields)
+template <class Body>
+__device__ __forceinline__ uint32_t snap_place(uint32_t n, uint64_t &base, uint64_t cap, uint32_t lane, const Body &body) {
+    const uint32_t rows = snap_wave_max(n);
+    for (uint32_t k = 0; k < rows; k++) {
+        const bool act = k < n;
+        const unsigned long long mask = __ballot(act);
+        const uint64_t pos = base + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+        if (act && pos < cap) body(k, pos);
+        base += (uint64_t)__popcll(mask);
+    }
+    return rows;
+}
+
+// the first N event counters (smr_common.h: SMR_CTR_SHARDS partial sums each).  Save: the shards summed, by wave 0 of block 0;
+// load: the sums into shard 0, the other shards (and the words behind N) zero, by block 0.  Every thread of the launch calls.
+// Ctr: the engine's pointer to its counters (MultiPaxos types it as global address space)
+template <int N, class Ctr>
+__device__ __forceinline__ void snap_counters_save(Ctr counters, uint64_t *dst) {
+    static_assert(N <= (int)SMR_CTR_STRIDE, "counters of one shard");
+    if (blockIdx.x != 0 || threadIdx.x >= 64) return;
+    unsigned long long x[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) x[k] = 0;
+    for (uint32_t sh = threadIdx.x; sh < SMR_CTR_SHARDS; sh += 64) {
+#pragma unroll
+        for (int k = 0; k < N; k++) x[k] += counters[(size_t)sh * SMR_CTR_STRIDE + k];
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) x[k] = snap_wave_sum(x[k]);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; k++) dst[k] = x[k];
+    }
+}
+template <int N, class Ctr>
+__device__ __forceinline__ void snap_counters_load(const uint64_t *src, Ctr counters) {
+    static_assert(SMR_CTR_SHARDS == 256 && N <= (int)SMR_CTR_STRIDE, "one thread of block 0 per counter shard");
+    if (blockIdx.x != 0) return;
+    for (uint32_t k = 0; k < SMR_CTR_STRIDE; k++) counters[(size_t)threadIdx.x * SMR_CTR_STRIDE + k] = (threadIdx.x == 0 && k < N) ? src[k] : 0ull;
+}
+
+// padding is zero: the bytes between the n an array at `off` (a multiple of 8) holds and the next multiple of 8
+__device__ __forceinline__ void snap_zero_pad(uint8_t *base, uint64_t off, uint64_t n) {
+    for (uint64_t p = off + n; p < off + snap_a8(n); p++) base[p] = 0;
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------
+// `what` is the engine's message prefix ("raft snapshot: ", ...): every text below is what the engines said before they shared it.
+
+// a snapshot object's device buffer: `filled` once a save or import has run, `hdr_known` once the image's header is on the host
+struct SnapBuf {
+    int device = -1;                                             // (where the engine keeps track of it)
+    uint8_t *dev = nullptr;
+    bool filled = false, hdr_known = false;
+};
+inline int snap_buf_alloc(SnapBuf &b, uint64_t bytes, const char *what) {
+    if (b.dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(b.dev); b.dev = nullptr; }
+    hipError_t e = hipMalloc((void **)&b.dev, bytes);
+    if (e != hipSuccess) { b.dev = nullptr; return fail(SMR_ERR_DEVICE, std::string(what) + "hipMalloc: " + hipGetErrorString(e)); }
+    return SMR_OK;
+}
+inline void snap_buf_free(SnapBuf &b) {
+    if (b.dev) { (void)hipDeviceSynchronize(); (void)hipFree(b.dev); b.dev = nullptr; }
+}
+// the image's header on the host (synchronises once after a save); fits(hdr): its counts are within the buffer's capacities
+template <class Hdr, class Fits>
+int snap_buf_header(SnapBuf &b, Hdr &hdr, const char *what, const Fits &fits) {
+    if (!b.filled) return fail(SMR_ERR_STATE, std::string(what) + "nothing saved or imported yet");
+    if (b.hdr_known) return SMR_OK;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    SMR_HIP_TRY(hipMemcpy(&hdr, b.dev, sizeof(Hdr), hipMemcpyDeviceToHost));
+    if (!fits(hdr)) {                                            // (cannot happen: the kernels' counts are bounded by what the room was made for)
+        b.filled = false;
+        return fail(SMR_ERR_STATE, std::string(what) + "the saved state exceeds the snapshot's room");
+    }
+    b.hdr_known = true;
+    return SMR_OK;
+}
+
+// a record section: `bytes` at dev_off on the device (capacity-spaced), `pad_to` >= bytes in the packed image, the rest zero.
+// The fixed part and then every section, device to packed host image (export: to_host, the padding written) or back (import)
+struct SnapSection { uint64_t dev_off, bytes, pad_to; };
+inline int snap_copy_sections(uint8_t *dev, uint8_t *host, uint64_t fixed, bool to_host, std::initializer_list<SnapSection> secs) {
+    const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+    SMR_HIP_TRY(hipMemcpy(to_host ? host : dev, to_host ? dev : host, fixed, kind));
+    uint8_t *p = host + fixed;
+    for (const SnapSection &s : secs) {
+        if (s.bytes) SMR_HIP_TRY(hipMemcpy(to_host ? p : dev + s.dev_off, to_host ? dev + s.dev_off : p, s.bytes, kind));
+        if (to_host) memset(p + s.bytes, 0, s.pad_to - s.bytes);
+        p += s.pad_to;
+    }
+    return SMR_OK;
+}
+
+// an import's first checks: length, magic, version; the header copied out.  noun: what the magic message calls the image
+template <class Hdr>
+int snap_import_prologue(const uint8_t *host, uint64_t len, uint32_t magic, uint32_t version, const char *what, Hdr &h, const char *noun = "snapshot") {
+    if (len < sizeof(Hdr)) return fail(SMR_ERR_ARG, std::string(what) + "image shorter than its header");
+    memcpy(&h, host, sizeof(h));
+    if (h.magic != magic) return fail(SMR_ERR_ARG, std::string(what) + "not a " + noun + " image (magic)");
+    if (h.version != version)
+        return fail(SMR_ERR_ARG, std::string(what) + "image format version " + std::to_string(h.version) + ", this library reads " + std::to_string(version));
+    return SMR_OK;
+}
+// len bytes cannot hold an image of `bytes` with a fixed part of `fixed`
+inline bool snap_truncated(uint64_t len, uint64_t fixed, uint64_t bytes) { return len < fixed || bytes > len || bytes < fixed; }
+inline bool snap_pad_is_zero(const uint8_t *host, uint64_t off, uint64_t n) {
+    for (uint64_t p = off + n; p < off + snap_a8(n); p++) if (host[p]) return false;
+    return true;
+}
+
+// the cluster forms' lists: n replicas and their snapshots, nothing null, nothing listed twice; each(k) is the engine's own
+// comparison of pair k (against reps[0], snapshot against replica), run in the same pass so the first fault found is the one
+// the engines reported before they shared this
+template <class Rep, class Snap, class Each>
+int snap_pairs_check(uint32_t n, Rep *const *reps, Snap *const *snaps, const char *what, const Each &each) {
+    if (!reps || !snaps) return fail(SMR_ERR_ARG, std::string(what) + "null argument");
+    if (n == 0 || n > SMR_MAX_REPLICAS) return fail(SMR_ERR_ARG, std::string(what) + "1 .. 8 replicas");
+    for (uint32_t k = 0; k < n; k++) {
+        if (!reps[k] || !snaps[k]) return fail(SMR_ERR_ARG, std::string(what) + "null argument");
+        for (uint32_t j = 0; j < k; j++)
+            if (reps[j] == reps[k] || snaps[j] == snaps[k]) return fail(SMR_ERR_ARG, std::string(what) + "a replica or a snapshot is listed twice");
+        if (int rc = each(k)) return rc;
+    }
+    return SMR_OK;
+}
+
+}  // namespace smr

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .snapshot import DeviceSnapshot
 from ._lib import MpCfg, MpDumpBufs, MpGroupState, MpTickIn, SummersetError, check, stream_ptr
 
 _DUMP_T = {"leader": np.uint8, "bal_prep_sent": np.uint64, "bal_prepared": np.uint64, "bal_max_seen": np.uint64,
@@ -26,48 +27,18 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-class MpSnapshot:
+class MpSnapshot(DeviceSnapshot):
     """A cluster's state between two ticks, held on the device (`smr_mp_snapshot`): what `MultiPaxosCluster.save_state`
     fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any two clusters that hold the
-    same logical state -- and `from_bytes` takes one back."""
-
-    def __init__(self, like):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        check(self._L.smr_mp_snapshot_create(like._h, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.smr_mp_snapshot_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def info(self):
-        """sizes of what was saved (synchronises): bytes, n_slots, n_outbox, n_groups, max_live, max_outbox, population,
-        commit_extra, live_mask"""
-        st = _lib.MpSnapshotInfo()
-        check(self._L.smr_mp_snapshot_info_get(self._h, C.byref(st)))
-        return {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
-
-    def export(self):
-        n = self.info()["bytes"]
-        buf = (C.c_uint8 * n)()
-        got = self._L.smr_mp_snapshot_export(self._h, buf, n)
-        if got < 0:
-            check(int(got))
-        return C.string_at(buf, got)
+    same logical state -- and `from_bytes` takes one back.  `info()`: bytes, n_slots, n_outbox, n_groups, max_live, max_outbox,
+    population, commit_extra, live_mask"""
+    _STEM, _INFO = "smr_mp_snapshot", _lib.MpSnapshotInfo
 
     @classmethod
     def from_bytes(cls, data, like):
         """the snapshot an exported image holds; `like`: a cluster of the image's n_groups, population, commit_extra and
         live mask (its window and capacities do not matter)"""
-        snap = cls(like)
-        data = bytes(data)
-        check(snap._L.smr_mp_snapshot_import(snap._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
-        return snap
+        return cls(like).import_(data)
 
 
 class MultiPaxosCluster:

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .snapshot import DeviceSnapshot
 from ._lib import RaftAppendEntries, RaftAppendReply, RaftCfg, RaftDumpBufs, check, stream_ptr
 
 _T = {"role": np.uint8, "leader": np.uint8, "curr_term": np.uint64, "entry_term": np.uint64}
@@ -21,45 +22,13 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-class RaftSnapshot:
+class RaftSnapshot(DeviceSnapshot):
     """One replica object's state between two handler calls, held on the device (`smr_raft_snapshot`): what
     `RaftLeaderGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
-    two replicas that hold the same logical state -- and `import_` takes one back."""
-
-    def __init__(self, like):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        check(self._L.smr_raft_snapshot_create(like._h, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.smr_raft_snapshot_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def info(self):
-        """sizes of what was saved (synchronises): bytes, n_entries, n_reconstructs, n_groups, max_live, max_reconstructs,
-        population, replica_id, commit_extra, craft, fault_tolerance, repeat_threshold"""
-        st = _lib.RaftSnapshotInfo()
-        check(self._L.smr_raft_snapshot_info_get(self._h, C.byref(st)))
-        return {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
-
-    def export(self):
-        n = self.info()["bytes"]
-        buf = (C.c_uint8 * n)()
-        got = self._L.smr_raft_snapshot_export(self._h, buf, n)
-        if got < 0:
-            check(int(got))
-        return C.string_at(buf, got)
-
-    def import_(self, data):
-        """take an exported image (of a replica like the one this snapshot was made for; its window does not matter)"""
-        data = bytes(data)
-        check(self._L.smr_raft_snapshot_import(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
-        return self
+    two replicas that hold the same logical state -- and `import_` takes one back (of a replica like the one this snapshot was
+    made for; its window does not matter).  `info()`: bytes, n_entries, n_reconstructs, n_groups, max_live, max_reconstructs,
+    population, replica_id, commit_extra, craft, fault_tolerance, repeat_threshold"""
+    _STEM, _INFO = "smr_raft_snapshot", _lib.RaftSnapshotInfo
 
 
 def save_cluster_state(reps, snaps=None, stream=None):

@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, stream_ptr
+from .snapshot import DeviceSnapshot
 
 REQS, VOTED = 0, 1
 NULL = 0xFFFFFFFF
@@ -31,29 +32,13 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-class PayloadStoreSnapshot:
+class PayloadStoreSnapshot(DeviceSnapshot):
     """One payload store's state between two calls on it, held on the device (`smr_rsp_pstore_snapshot`): cell headers, the VOTED
     plane's alias bytes, every present shard that is no alias, the counters -- for an `RSPaxosPayloadStore` or a `CRaftPayloadStore`.
-    `export()` gives the canonical image as bytes, equal for two stores of the same content whatever their `max_data_len`."""
-
-    def __init__(self, like):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        check(self._L.smr_rsp_pstore_snapshot_create(like._h, C.byref(h)))
-        self._h = h
-
-    @classmethod
-    def create_like(cls, like):
-        """room for the worst case of store `like` (every cell holding every shard at max_data_len)"""
-        return cls(like)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.smr_rsp_pstore_snapshot_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
+    `export()` gives the canonical image as bytes, equal for two stores of the same content whatever their `max_data_len`.
+    `create_like`: room for every cell holding every shard at max_data_len.  `info()`: bytes, n_cells, n_shards_stored,
+    shard_bytes, n_groups, window, max_dlen, n_shards, n_data_shards, planes, craft"""
+    _STEM, _INFO = "smr_rsp_pstore_snapshot", _lib.PstoreSnapshotInfo
 
     def save(self, store, stream=None):
         check(self._L.smr_rsp_pstore_save(store._h, self._h, stream_ptr(stream)))
@@ -61,26 +46,6 @@ class PayloadStoreSnapshot:
 
     def load(self, store, stream=None):
         check(self._L.smr_rsp_pstore_load(store._h, self._h, stream_ptr(stream)))
-
-    def info(self):
-        """sizes of what was saved (synchronises): bytes, n_cells, n_shards_stored, shard_bytes, n_groups, window, max_dlen,
-        n_shards, n_data_shards, planes, craft"""
-        st = _lib.PstoreSnapshotInfo()
-        check(self._L.smr_rsp_pstore_snapshot_info_get(self._h, C.byref(st)))
-        return {n: int(getattr(st, n)) for n, _ in st._fields_}
-
-    def export(self):
-        n = self.info()["bytes"]
-        buf = (C.c_uint8 * n)()
-        got = self._L.smr_rsp_pstore_snapshot_export(self._h, buf, n)
-        if got < 0:
-            check(int(got))
-        return C.string_at(buf, got)
-
-    def import_(self, data):
-        data = bytes(data)
-        check(self._L.smr_rsp_pstore_snapshot_import(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
-        return self
 
 
 class RSPaxosPayloadStore:

@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .snapshot import DeviceSnapshot
 from ._lib import RspAccepts, RspCfg, RspDumpBufs, RspHeartbeat, RspPrepareReply, RspShards, check, stream_ptr
 
 NULL, NO_REP = 0xFFFFFFFF, 0xFF
@@ -23,29 +24,13 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-class RSPaxosSnapshot:
+class RSPaxosSnapshot(DeviceSnapshot):
     """One replica object's state between two handler calls, held on the device (`smr_rsp_snapshot`): what
     `RSPaxosReplicaGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
-    two replicas that hold the same logical state -- and `import_` takes one back."""
-
-    def __init__(self, like):
-        self._L = _lib.load()
-        h = C.c_void_p()
-        check(self._L.smr_rsp_snapshot_create(like._h, C.byref(h)))
-        self._h = h
-
-    @classmethod
-    def create_like(cls, like):
-        """room for the worst case of replica `like` (every ring row live, a full execution list)"""
-        return cls(like)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.smr_rsp_snapshot_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
+    two replicas that hold the same logical state -- and `import_` takes one back (of a replica like the one this snapshot was
+    made for; any window).  `create_like`: room for every ring row live and a full execution list.  `info()`: bytes, n_slots,
+    n_exec, n_groups, window, max_live, max_exec, population, replica_id, fault_tolerance"""
+    _STEM, _INFO = "smr_rsp_snapshot", _lib.RspSnapshotInfo
 
     def save(self, rep, stream=None):
         """`rep.save_state(self)`"""
@@ -55,27 +40,6 @@ class RSPaxosSnapshot:
     def load(self, rep, stream=None):
         """`rep.load_state(self)`"""
         check(self._L.smr_rsp_load_state(rep._h, self._h, stream_ptr(stream)))
-
-    def info(self):
-        """sizes of what was saved (synchronises): bytes, n_slots, n_exec, n_groups, window, max_live, max_exec, population,
-        replica_id, fault_tolerance"""
-        st = _lib.RspSnapshotInfo()
-        check(self._L.smr_rsp_snapshot_info_get(self._h, C.byref(st)))
-        return {n: int(getattr(st, n)) for n, _ in st._fields_ if n != "reserved"}
-
-    def export(self):
-        n = self.info()["bytes"]
-        buf = (C.c_uint8 * n)()
-        got = self._L.smr_rsp_snapshot_export(self._h, buf, n)
-        if got < 0:
-            check(int(got))
-        return C.string_at(buf, got)
-
-    def import_(self, data):
-        """take an exported image (of a replica like the one this snapshot was made for; any window)"""
-        data = bytes(data)
-        check(self._L.smr_rsp_snapshot_import(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
-        return self
 
 
 def _handles(xs):

@@ -1149,3 +1149,40 @@ def store_past_4gib(dev, oracle, n=3, d=2, G=4096, W=8, L=88000):
             cw[d:] = oracle.rs_encode(d, n - d, bts)
             assert np.array_equal(row[:, g, :sl], cw), (w, g)
     _close([b, snap])
+
+
+def store_more_tiles_than_wavefronts(dev, oracle, n=3, d=2, G=66000, W=8, L=16):
+    """device only: 66 000 groups are 1 032 tiles for the header kernel's 1 024 wavefronts, so every wavefront takes two tiles
+    (the last ones one or none) and a cell's offset is a sum over tiles of its own wavefront, of its block and of the blocks in
+    front.  One put per ring row of 16-byte payloads (66 000 x 8 x 3 shards of 8 bytes, 16 in the image: 25 MB); the store is
+    saved, loaded into a second one, the two are equal, and sampled shards on both sides of tile, wavefront and block edges are the
+    oracle's encoder's; the image's size is arithmetic"""
+    import torch
+    from summerset_amd import RSPaxosPayloadStore
+    assert (G + 63) // 64 > 1024
+    sl = (L + d - 1) // d
+    a, b = RSPaxosPayloadStore(G, n, W, L, num_data_shards=d), RSPaxosPayloadStore(G, n, W, L + 100, num_data_shards=d)
+    gen = torch.Generator(device=dev); gen.manual_seed(13)
+    data = torch.randint(0, 256, (G, L), dtype=torch.uint8, device=dev, generator=gen)
+    ones = torch.ones(G, dtype=torch.int32, device=dev)
+    for slot in range(W):
+        a_slot = torch.zeros((W, G), dtype=torch.int32, device=dev); a_slot[0] = slot
+        a_val = torch.zeros((W, G), dtype=torch.int32, device=dev); a_val[0] = torch.arange(G, dtype=torch.int32, device=dev) + 1 + slot * G
+        a.put(dict(a_n=ones, a_slot=a_slot, a_val=a_val), data.roll(slot, 1))
+    snap = a.save()
+    info = snap.info()
+    total = G * W * n * a16(sl)
+    assert info["shard_bytes"] == total and info["n_shards_stored"] == G * W * n and info["n_cells"] == G * W and info["max_dlen"] == L, info
+    assert info["bytes"] == StoreLayout(G, W, 2).fixed + total
+    b.load(snap)
+    stores_equal(b, a, "more tiles than wavefronts")
+    host = data.cpu().numpy()
+    for w in (0, W - 1):
+        row = b.read_row(w, 0)
+        for g in (0, 63, 64, 127, 128, 511, 512, G // 2, 65535, 65536, G - 17, G - 16, G - 1):   # tiles, wavefronts (128 groups), blocks (512)
+            bts = np.roll(host[g], w)
+            cw = np.zeros((n, sl), np.uint8)
+            cw[:d].reshape(-1)[:L] = bts
+            cw[d:] = oracle.rs_encode(d, n - d, bts)
+            assert np.array_equal(row[:, g, :sl], cw), (w, g)
+    _close([a, b, snap])

@@ -119,3 +119,8 @@ def test_craft_store_shadow_at_every_tick(cuda, oracle, R):
 def test_store_offsets_past_4_gib(cuda, oracle):
     import rsp_snapshot_cases as c
     c.store_past_4gib(cuda, oracle)
+
+
+def test_store_more_tiles_than_wavefronts(cuda, oracle):
+    import rsp_snapshot_cases as c
+    c.store_more_tiles_than_wavefronts(cuda, oracle)
