@@ -966,6 +966,66 @@ int smr_ep_exec_dump(smr_ep_replica *e, uint32_t *exec_bars, uint64_t *kv, uint6
  * the call only counts and leaves the list in place. */
 int smr_ep_exec_poll(smr_ep_replica *e, uint32_t *group_host, uint8_t *row_host, uint32_t *col_host, uint64_t cap, uint64_t *n_out);
 
+/* ---- save / load of one replica object's state on the device (the image: DESIGN.md 2) -----------------------
+ * The reference brings a replica back from its snapshot file and WAL (epaxos/snapshot.rs, epaxos/recovery.rs) in the
+ * crash-restart loop of summerset_server/src/main.rs:124-167; a batched replica object is saved into a canonical,
+ * device-resident image and loaded back whole, between two handler calls, by one kernel each: a checkpoint, the restart of one
+ * replica while the others of its cluster go on, the way back after smr_ep_spread_abort_tick.
+ * The image carries what the four dumps report and nothing of the arena's layout: per group len and commit_bars per row,
+ * rewritten, the per-key highest columns and, with execute, exec_bars, the executor's commit-bar copies, digest and the KV tokens
+ * as 64-bit values; every LIVE cell -- [len > window ? len - window : 0, len) of its row, the span smr_ep_dump gives -- as a
+ * 64-byte record (ballot, seq, deps, Status, key, bookkeeping and ack masks; with recovery exp_prepare_max_bal,
+ * avoid_fast_path, exp_prepare_acks and the has-entry bits); the stored PreAcceptReplies of my row's live cells (every row's
+ * with recovery, and then the exp_prepare_voteds entries too), each only where a handler can reach it; the submissions
+ * smr_ep_exec_poll would hand over, as (row, column); the 7 (+ 8 with execute) counters summed over their shards -- the
+ * "column >= 2^28" count among them, so a loaded replica goes on answering SMR_ERR_STATE where the saved one did.  Not carried:
+ * ring cells outside the live span (load leaves them alone; the dumps give null cells there), the executor's graph arrays
+ * (dead between two calls), the wire call's scratch, anything of an smr_ep_cluster or smr_ep_spread object.
+ * Save and load are stream-ordered and defined BETWEEN two handler calls / ticks of the replica.  A caller inside an open
+ * smr_ep_spread tick calls smr_ep_spread_abort_tick first: host staging inside a tick is not state.
+ *   smr_ep_snapshot_create    room for the worst case of `like` (every ring cell live, the submission list full), so a save
+ *                             never finds the snapshot too small; a replica with a larger window saved into it later makes it
+ *                             grow in that save call (sizes the host knows: no read-back);
+ *   smr_ep_save_state         one kernel on `stream`, enqueues only.  The snapshot must have been made for the replica's
+ *                             n_groups, population, me, optimized_quorum, execute, recovery and n_keys (SMR_ERR_ARG);
+ *   smr_ep_load_state         the inverse, one kernel: overwrites the replica's whole logical state -- a replica seated in an
+ *                             smr_ep_cluster's shared per-key table loads into its slots of that table.  Needs those seven
+ *                             AND the window to agree -- else SMR_ERR_ARG and the replica is untouched (a cell is held iff
+ *                             column + window >= len; in another ring the cells around the saved span would count as held or
+ *                             as lost).  Synchronises once per save to read the header;
+ *   smr_ep_snapshot_info_get  synchronises;
+ *   smr_ep_snapshot_export / _import   the image as host bytes (little-endian).  The format is canonical: two replicas whose
+ *                             dumps agree export the same bytes, whichever calls ran their ticks (handler by handler,
+ *                             smr_ep_cluster_tick in any mode, seated in a cluster's table or not).  Import checks the FORMAT
+ *                             -- length, magic, version, the header against the snapshot, counts against the live spans,
+ *                             Status <= 5, key < n_keys or SMR_EP_NO_KEY, masks within the population, zero padding
+ *                             (SMR_ERR_ARG) -- and never reads past len.  Export returns the bytes written, < 0 on error
+ *                             (SMR_ERR_ARG: cap below info.bytes);
+ *   smr_ep_cluster_save_state / _load_state   n <= 8 distinct replicas that share n_groups / population / n_keys / execute /
+ *                             recovery, each with its own snapshot, in ONE launch: the images and states of the n single
+ *                             calls.  The views travel in the launch's arguments: the call allocates and copies nothing. */
+typedef struct smr_ep_snapshot smr_ep_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint64_t n_cells;               /* live cells over all rows and groups */
+    uint64_t n_exec;                /* unpolled submissions over all groups */
+    uint32_t n_groups, window, n_keys, max_live, max_exec;   /* the longest live span of a row / submission list of a group */
+    uint8_t population, me, optimized_quorum, execute, recovery, reserved[3];
+} smr_ep_snapshot_info;
+int smr_ep_snapshot_create(const smr_ep_replica *like, smr_ep_snapshot **out);
+void smr_ep_snapshot_destroy(smr_ep_snapshot *s);
+int smr_ep_save_state(smr_ep_replica *e, smr_ep_snapshot *s, void *stream);
+int smr_ep_load_state(smr_ep_replica *e, const smr_ep_snapshot *s, void *stream);
+int smr_ep_snapshot_info_get(const smr_ep_snapshot *s, smr_ep_snapshot_info *out);
+int64_t smr_ep_snapshot_export(const smr_ep_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_ep_snapshot_import(smr_ep_snapshot *s, const uint8_t *host, uint64_t len);
+int smr_ep_cluster_save_state(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, void *stream);
+int smr_ep_cluster_load_state(uint32_t n, smr_ep_replica *const *reps, const smr_ep_snapshot *const *snaps, void *stream);
+/* debug / measurement only: the device allocation that holds the replica's arrays (ring cells dead or alive, the reply tables,
+ * the executor's graph arrays, counter shards), i.e. what a wholesale copy of the replica's state would move --
+ * tools/time_ep_snapshot.py times that copy beside smr_ep_cluster_save_state.  The layout inside is the library's own. */
+int smr_ep_debug_arena_view(smr_ep_replica *e, void **base_dev, uint64_t *n_bytes);
+
 /* ------------------------------------------------------------------------
  * RSPaxos replica: G groups, one replica id per object, one call = one handler
  * of RSPaxosReplica per group (+ the WAL / command completions it triggers, LS-1 rule 0).

@@ -12,7 +12,7 @@ from .rscoding import RSCodewordBatch, rs_matrix, rs_shard_len  # noqa: F401
 from .multipaxos import MpSnapshot, MultiPaxosCluster  # noqa: F401
 from .quorumread import KvStateMachine, QuorumReadGroup, StringKvStateMachine  # noqa: F401
 from .raft import CRaftLeaderGroup, RaftLeaderGroup, RaftSnapshot, load_cluster_state, save_cluster_state  # noqa: F401
-from .epaxos import EPaxosReplicaGroup  # noqa: F401
+from .epaxos import EPaxosReplicaGroup, EPaxosSnapshot  # noqa: F401
 from .rspaxos import RSPaxosReplicaGroup, RSPaxosSnapshot  # noqa: F401
 from .rsp_payload import CRaftPayloadStore, PayloadStoreSnapshot, RSPaxosPayloadStore, RSPaxosReplicaWithPayload  # noqa: F401
 from .repnothing import RepNothingReplica  # noqa: F401

@@ -73,6 +73,12 @@ class RspSnapshotInfo(C.Structure):
                 ("fault_tolerance", C.c_uint8), ("reserved", C.c_uint8 * 5)]
 
 
+class EpSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_cells", C.c_uint64), ("n_exec", C.c_uint64), ("n_groups", C.c_uint32), ("window", C.c_uint32),
+                ("n_keys", C.c_uint32), ("max_live", C.c_uint32), ("max_exec", C.c_uint32), ("population", C.c_uint8), ("me", C.c_uint8),
+                ("optimized_quorum", C.c_uint8), ("execute", C.c_uint8), ("recovery", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 class PstoreSnapshotInfo(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("n_cells", C.c_uint64), ("n_shards_stored", C.c_uint64), ("shard_bytes", C.c_uint64),
                 ("n_groups", C.c_uint32), ("window", C.c_uint32), ("max_dlen", C.c_uint32), ("n_shards", C.c_uint8),
@@ -367,6 +373,16 @@ SYMBOLS = [
     ("smr_ep_dump", _i, [_vp, C.POINTER(EpDumpBufs)]),
     ("smr_ep_exec_dump", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("smr_ep_exec_poll", _i, [_vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    ("smr_ep_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_ep_snapshot_destroy", None, [_vp]),
+    ("smr_ep_save_state", _i, [_vp, _vp, _vp]),
+    ("smr_ep_load_state", _i, [_vp, _vp, _vp]),
+    ("smr_ep_snapshot_info_get", _i, [_vp, C.POINTER(EpSnapshotInfo)]),
+    ("smr_ep_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_ep_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_ep_cluster_save_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_ep_cluster_load_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_ep_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_rsp_replica_create", _i, [C.POINTER(RspCfg), C.POINTER(_vp)]),
     ("smr_rsp_replica_destroy", None, [_vp]),
     ("smr_rsp_cluster_create", _i, [_vp, _u32, _vp]),

@@ -558,6 +558,10 @@ struct EpExec {
                                          // (unused: components > 1 node), attempts, abandoned attempts
 };
 
+}  // namespace smr
+#include "ep_snapshot.h"   // save / load of a replica's state: the canonical image, its two kernels, the live-span rule the dumps share
+namespace smr {
+
 template <int NR, bool CACHE = false>
 struct EpExecLaneT {
     const EpView &v;
@@ -3093,13 +3097,8 @@ int smr_ep_xp_dump(smr_ep_replica *e, uint8_t *acks, uint64_t *max_bal, uint8_t 
         for (size_t w = 0; w < W; w++)
             for (size_t g = 0; g < G; g++) {
                 const size_t o = (row * W + w) * G + g;
-                const uint32_t end = len[row * G + g], lo = end > W ? end - (uint32_t)W : 0;
-                bool live = false;
-                if (end > lo) {
-                    uint32_t cc = (lo & ~(uint32_t)(W - 1)) | (uint32_t)w;
-                    if (cc < lo) cc += (uint32_t)W;
-                    live = cc < end;
-                }
+                uint32_t cc;
+                const bool live = ep_live_col(len[row * G + g], (uint32_t)W, (uint32_t)w, cc);   // (ep_snapshot.h: the live span)
                 const bool lb = live && (bk[o] & 1);
                 avoid[o] = live ? av[o] : 0; acks[o] = lb ? a[o] : 0; max_bal[o] = lb ? mx[o] : 0; has[o] = lb ? h[o] : 0;
                 for (size_t p = 0; p < R; p++) {
@@ -3160,14 +3159,8 @@ int smr_ep_dump(smr_ep_replica *e, const smr_ep_dump_bufs *hb) {
         for (size_t w = 0; w < W; w++)
             for (size_t g = 0; g < G; g++) {
                 const size_t o = (row * W + w) * G + g;
-                const uint32_t end = hb->len[row * G + g], lo = end > W ? end - (uint32_t)W : 0;
-                // the column this cell holds, if any
-                bool live = false;
-                if (end > lo) {
-                    uint32_t cc = (lo & ~(uint32_t)(W - 1)) | (uint32_t)w;
-                    if (cc < lo) cc += (uint32_t)W;
-                    live = cc < end;
-                }
+                uint32_t cc;                                                     // the column this cell holds, if any
+                const bool live = ep_live_col(hb->len[row * G + g], (uint32_t)W, (uint32_t)w, cc);   // (ep_snapshot.h: the live span)
                 hb->bal[o] = live ? bal[o] : 0; hb->seq[o] = live ? seq[o] : 0; hb->status[o] = live ? st[o] : 0;
                 hb->key[o] = live ? key[o] : 0xFF; hb->pa_acks[o] = live ? pa[o] : 0; hb->acc_acks[o] = live ? ac[o] : 0;
                 hb->bk[o] = live ? bk[o] : 0;
@@ -3220,9 +3213,8 @@ int smr_ep_exec_poll(smr_ep_replica *e, uint32_t *group_host, uint8_t *row_host,
         for (uint32_t k = 0; k < n_sub[g]; k++, n++) {
             if (n >= cap || !group_host || !row_host || !col_host) continue;
             const uint32_t ring = order[(size_t)k * G + g], row = ring >> wshift, w = ring & v.Wmask;
-            const uint32_t end = len[row * G + g], lo = end > v.W ? end - v.W : 0u;
-            uint32_t col = (lo & ~v.Wmask) | w;                              // the column of that residue among the last W
-            if (col < lo) col += v.W;
+            uint32_t col;                                                    // the column of that residue among the last W
+            (void)ep_live_col(len[row * G + g], v.W, w, col);
             group_host[n] = (uint32_t)g; row_host[n] = (uint8_t)row; col_host[n] = col;
         }
     *n_out = n;
@@ -3526,5 +3518,249 @@ int smr_ep_cluster_tick(smr_ep_cluster *c, const uint8_t *const *keys_dev, const
     return SMR_OK;
 }
 
+
+}  // extern "C"
+
+/* ---- save / load of one replica's state on the device (ep_snapshot.h: the image and its two kernels) ----------------------------
+ * A batched replica object is saved and brought back whole, between two handler calls, by one kernel each, while the other
+ * replicas of its cluster go on: a checkpoint, the restart of one replica, the way back from an aborted L2 tick. */
+struct smr_ep_snapshot {
+    uint32_t G = 0, K = 0;
+    uint8_t R = 0, me = 0, oq = 0, execute = 0, recovery = 0;
+    SnapBuf buf;
+    uint64_t cap_c = 0, cap_r = 0, cap_x = 0;                    // records the device buffer's sections have room for
+    EpSnapHdr hdr;                                               // the image's header, once buf.hdr_known
+};
+
+namespace smr {
+static const char *const EPSNAP = "epaxos snapshot: ";
+static EpSnapGeom epsnap_geom_of(const smr_ep_snapshot *s) { return epsnap_geom(s->G, s->R, s->K, s->execute, s->recovery); }
+static EpSnapImg epsnap_img(const smr_ep_snapshot *s) { return EpSnapImg{s->buf.dev, s->cap_c, s->cap_r, s->cap_x}; }
+static int epsnap_alloc(smr_ep_snapshot *s, uint64_t cap_c, uint64_t cap_r, uint64_t cap_x) {
+    s->cap_c = cap_c; s->cap_r = cap_r; s->cap_x = cap_x;
+    return snap_buf_alloc(s->buf, epsnap_dev_bytes(epsnap_geom_of(s), epsnap_img(s)), EPSNAP);
+}
+// room for the worst case of a replica with window W: every ring cell live, the submission list full.  A save can then never find
+// the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica with a
+// larger window is saved into it.
+static int epsnap_room_for(smr_ep_snapshot *s, uint64_t W) {
+    const uint64_t c = (uint64_t)s->G * s->R * W, r = (uint64_t)s->G * (s->recovery ? s->R : 1) * W, x = s->execute ? 2 * c : 0;
+    if (s->buf.dev && c <= s->cap_c && r <= s->cap_r && x <= s->cap_x) return SMR_OK;
+    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
+    return epsnap_alloc(s, std::max(c, s->cap_c), std::max(r, s->cap_r), std::max(x, s->cap_x));
+}
+// the image's header on the host (synchronises once after a save)
+static int epsnap_header(smr_ep_snapshot *s) {
+    return snap_buf_header(s->buf, s->hdr, EPSNAP,
+                           [s](const EpSnapHdr &h) { return h.n_cells <= s->cap_c && h.n_replies <= s->cap_r && h.n_exec <= s->cap_x; });
+}
+// the image of header h between the device buffer (sections at their capacities) and packed host bytes
+static int epsnap_copy(const smr_ep_snapshot *s, uint8_t *host, const EpSnapHdr &h, bool to_host) {
+    const EpSnapGeom q = epsnap_geom_of(s);
+    const uint64_t bc = h.n_cells * sizeof(EpSnapCell), br = (uint64_t)h.n_replies * q.r_stride, bx = h.n_exec * sizeof(EpSnapExec);
+    return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
+                              {{q.fixed, bc, bc}, {epsnap_off_rep(q, epsnap_img(s)), br, br}, {epsnap_off_exec(q, epsnap_img(s)), bx, bx}});
+}
+static bool epsnap_like(const smr_ep_snapshot *s, const smr_ep_cfg &c) {
+    return s->G == c.n_groups && s->R == c.population && s->me == c.me && s->oq == (c.optimized_quorum ? 1 : 0) && s->execute == c.execute &&
+           s->recovery == c.recovery && s->K == c.n_keys;
+}
+static bool epsnap_hdr_like(const EpSnapHdr &h, const smr_ep_snapshot *s) {
+    return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.optimized_quorum == s->oq && h.execute == s->execute &&
+           h.recovery == s->recovery && h.n_keys == s->K;
+}
+static const char *const EPSNAP_OTHER = "another n_groups / population / replica id / optimized_quorum / execute / recovery / n_keys";
+
+// the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
+static int epsnap_setup(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, bool load, EpSnapArgs &A) {
+    if (int rc = snap_pairs_check(n, reps, snaps, EPSNAP, [&](uint32_t k) {
+            const smr_ep_cfg &c = reps[k]->cfg, &c0 = reps[0]->cfg;
+            if (c.n_groups != c0.n_groups || c.population != c0.population || c.n_keys != c0.n_keys || c.execute != c0.execute || c.recovery != c0.recovery)
+                return fail(SMR_ERR_ARG, "epaxos snapshot: the replicas differ in groups / population / n_keys / execute / recovery");
+            if (!epsnap_like(snaps[k], c)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: made for ") + EPSNAP_OTHER);
+            return (int)SMR_OK;
+        })) return rc;
+    memset(&A, 0, sizeof(A));
+    for (uint32_t k = 0; k < n; k++) {
+        smr_ep_replica *e = reps[k];
+        smr_ep_snapshot *s = snaps[k];
+        if (load) {
+            if (int rc = epsnap_header(s)) return rc;
+            const EpSnapHdr &h = s->hdr;
+            if (!epsnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: the image is of ") + EPSNAP_OTHER);
+            // a cell is held iff column + W >= len: in another ring the cells around the saved span would count as held or lost
+            if (h.window != e->cfg.window)
+                return fail(SMR_ERR_ARG, "epaxos snapshot: an image of window " + std::to_string(h.window) + " does not load into window " + std::to_string(e->cfg.window));
+        } else if (int rc = epsnap_room_for(s, e->cfg.window)) return rc;   // (only a failed hipMalloc: the snapshots that grew before it are
+                                                                            //  then empty, SMR_ERR_STATE on use, and none holds a partial image)
+    }
+    const smr_ep_cfg &c0 = reps[0]->cfg;
+    A.geo = epsnap_geom(c0.n_groups, c0.population, c0.n_keys, c0.execute, c0.recovery);
+    for (uint32_t k = 0; k < n; k++) {
+        A.v[k] = reps[k]->v; A.x[k] = reps[k]->x; A.img[k] = snaps[k]->buf.dev;
+        A.cap_c[k] = snaps[k]->cap_c; A.cap_r[k] = snaps[k]->cap_r; A.cap_x[k] = snaps[k]->cap_x; A.oq[k] = snaps[k]->oq;
+    }
+    return SMR_OK;
+}
+}  // namespace smr
+
+extern "C" {
+
+int smr_ep_snapshot_create(const smr_ep_replica *like, smr_ep_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
+    smr_ep_snapshot *s = new smr_ep_snapshot();
+    const smr_ep_cfg &c = like->cfg;
+    s->G = c.n_groups; s->K = c.n_keys; s->R = c.population; s->me = c.me; s->oq = c.optimized_quorum ? 1 : 0; s->execute = c.execute; s->recovery = c.recovery;
+    memset(&s->hdr, 0, sizeof(s->hdr));
+    if (int rc = epsnap_room_for(s, c.window)) { delete s; return rc; }
+    *out = s;
+    return SMR_OK;
+}
+
+void smr_ep_snapshot_destroy(smr_ep_snapshot *s) {
+    if (!s) return;
+    snap_buf_free(s->buf);
+    delete s;
+}
+
+int smr_ep_cluster_save_state(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, void *stream) {
+    EpSnapArgs A;
+    if (int rc = epsnap_setup(n, reps, snaps, false, A)) return rc;
+    hipLaunchKernelGGL(ep_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < n; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    return SMR_OK;
+}
+
+int smr_ep_cluster_load_state(uint32_t n, smr_ep_replica *const *reps, const smr_ep_snapshot *const *snaps, void *stream) {
+    EpSnapArgs A;                                                // (a snapshot's header is read back and cached on first use)
+    if (int rc = epsnap_setup(n, reps, const_cast<smr_ep_snapshot *const *>(snaps), true, A)) return rc;
+    hipLaunchKernelGGL(ep_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_ep_save_state(smr_ep_replica *e, smr_ep_snapshot *s, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
+    return smr_ep_cluster_save_state(1, &e, &s, stream);
+}
+
+int smr_ep_load_state(smr_ep_replica *e, const smr_ep_snapshot *s, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
+    return smr_ep_cluster_load_state(1, &e, &s, stream);
+}
+
+int smr_ep_debug_arena_view(smr_ep_replica *e, void **base_dev, uint64_t *n_bytes) {
+    if (!e || !base_dev || !n_bytes) return fail(SMR_ERR_ARG, "epaxos: null argument");
+    *base_dev = e->arena.base; *n_bytes = e->arena.size;
+    return SMR_OK;
+}
+
+int smr_ep_snapshot_info_get(const smr_ep_snapshot *cs, smr_ep_snapshot_info *out) {
+    if (!cs || !out) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
+    smr_ep_snapshot *s = const_cast<smr_ep_snapshot *>(cs);
+    if (int rc = epsnap_header(s)) return rc;
+    const EpSnapHdr &h = s->hdr;
+    memset(out, 0, sizeof(*out));
+    out->bytes = h.bytes; out->n_cells = h.n_cells; out->n_exec = h.n_exec;
+    out->n_groups = h.n_groups; out->window = h.window; out->n_keys = h.n_keys; out->max_live = h.max_live; out->max_exec = h.max_exec;
+    out->population = h.population; out->me = h.me; out->optimized_quorum = h.optimized_quorum; out->execute = h.execute; out->recovery = h.recovery;
+    return SMR_OK;
+}
+
+int64_t smr_ep_snapshot_export(const smr_ep_snapshot *cs, uint8_t *host, uint64_t cap) {
+    if (!cs || !host) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
+    smr_ep_snapshot *s = const_cast<smr_ep_snapshot *>(cs);
+    if (int rc = epsnap_header(s)) return rc;
+    const EpSnapHdr &h = s->hdr;
+    if (cap < h.bytes) return fail(SMR_ERR_ARG, "epaxos snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
+    if (int rc = epsnap_copy(s, host, h, true)) return rc;
+    return (int64_t)h.bytes;
+}
+
+int smr_ep_snapshot_import(smr_ep_snapshot *s, const uint8_t *host, uint64_t len) {
+    if (!s || !host) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
+    EpSnapHdr h;
+    if (int rc = snap_import_prologue(host, len, EPSNAP_MAGIC, EPSNAP_VERSION, EPSNAP, h)) return rc;
+    if (!epsnap_hdr_like(h, s) || h.reserved0[0] || h.reserved0[1] || h.reserved0[2])
+        return fail(SMR_ERR_ARG, std::string("epaxos snapshot: the image is of ") + EPSNAP_OTHER);
+    const uint32_t W = h.window, R = s->R, G = s->G, K = s->K;
+    if (W < 8 || (W & (W - 1)) || W > EPSNAP_MAX_WINDOW) return fail(SMR_ERR_ARG, "epaxos snapshot: the image's window is not a power of two in 8 .. 2^15");
+    const EpSnapGeom q = epsnap_geom_of(s);
+    if (snap_truncated(len, q.fixed, h.bytes)) return fail(SMR_ERR_ARG, "epaxos snapshot: truncated image");
+    const uint64_t room = h.bytes - q.fixed;                      // the record sections; each count bounded before it is multiplied
+    if (h.n_cells > room / sizeof(EpSnapCell) || h.n_replies > room / q.r_stride || h.n_exec > room / sizeof(EpSnapExec) ||
+        epsnap_bytes(q, h.n_cells, h.n_replies, h.n_exec) != h.bytes)
+        return fail(SMR_ERR_ARG, "epaxos snapshot: the header's counts do not add up to the image's size");
+    // the body against the header: counts and maxima recomputed from the scalars, ids in range
+    const auto bad = [](const char *what) { return fail(SMR_ERR_ARG, std::string("epaxos snapshot: malformed image: ") + what); };
+    const auto u32at = [](const uint8_t *p, uint64_t i) { uint32_t x; memcpy(&x, p + 4 * i, 4); return x; };
+    const uint32_t xcap = 2u * R * W;
+    uint64_t n_c = 0, n_r = 0, n_x = 0;
+    uint32_t max_live = 0, max_exec = 0;
+    for (uint32_t g = 0; g < G; g++) {
+        for (uint32_t r = 0; r < R; r++) {
+            const uint32_t n = ep_live_n(u32at(host + q.o_len, (uint64_t)r * G + g), W);
+            if (n > h.max_live) return bad("a row's live span above the header's max_live");
+            n_c += n; if (s->recovery || r == s->me) n_r += n;
+            max_live = n > max_live ? n : max_live;
+        }
+        if (host[q.o_rew + g] > 1) return bad("rewritten is neither 0 nor 1");
+        const uint32_t nx = s->execute ? u32at(host + q.o_nsub, g) : 0u;
+        if (nx > xcap || nx > h.max_exec) return bad("a group's submission list above its capacity or the header's max_exec");
+        n_x += nx; max_exec = nx > max_exec ? nx : max_exec;
+    }
+    if (n_c != h.n_cells || n_r != h.n_replies || n_x != h.n_exec || max_live != h.max_live || max_exec != h.max_exec)
+        return bad("the header's counts and maxima contradict the body (the live spans do not sum to n_cells)");
+    {
+        const uint64_t g = G, rg = 4 * g * R;
+        if (!snap_pad_is_zero(host, q.o_len, rg) || !snap_pad_is_zero(host, q.o_cb, rg) || !snap_pad_is_zero(host, q.o_rew, g) ||
+            !snap_pad_is_zero(host, q.o_hc, rg * K) ||
+            (s->execute && (!snap_pad_is_zero(host, q.o_eb, rg) || !snap_pad_is_zero(host, q.o_pcb, rg) || !snap_pad_is_zero(host, q.o_nsub, 4 * g))))
+            return bad("padding is not zero");
+        for (uint64_t p = q.o_end; p < q.fixed; p++) if (host[p]) return bad("padding is not zero");
+    }
+    const uint8_t *p = host + q.fixed;
+    for (uint64_t k = 0; k < h.n_cells; k++, p += sizeof(EpSnapCell)) {
+        EpSnapCell c;
+        memcpy(&c, p, sizeof(c));
+        if (c.status > EST_EXECUTED) return bad("an instance's status above Executed");
+        if (c.key != EP_NO_KEY && c.key >= K) return bad("an instance's key neither below n_keys nor none");
+        for (uint32_t i = R; i < 8; i++) if (c.deps[i] != EP_NONE) return bad("a dependency at or above the population");
+        if ((c.pa_acks | c.acc_acks | c.xp_acks | c.xp_has) >> R) return bad("an instance names replicas beyond the population");
+        if (!s->recovery && (c.xp_max || c.avoid || c.xp_acks || c.xp_has)) return bad("explicit-prepare fields without recovery");
+        if (!(c.bk & 1) && (c.xp_max || c.xp_acks || c.xp_has)) return bad("explicit-prepare bookkeeping of an instance without leader bookkeeping");
+    }
+    for (uint64_t k = 0; k < h.n_replies; k++, p += q.r_stride) {
+        if (s->recovery)
+            for (uint32_t i = 0; i < R; i++) {
+                if (p[q.r_xs + i] > EST_EXECUTED) return bad("a voted entry's status above Executed");
+                if (p[q.r_xk + i] != EP_NO_KEY && p[q.r_xk + i] >= K) return bad("a voted entry's key neither below n_keys nor none");
+            }
+        for (uint32_t i = q.r_end; i < q.r_stride; i++) if (p[i]) return bad("padding is not zero");
+    }
+    if (s->execute) {                                            // exec entries, in the image's order (tile, list position, group): a cell of a row
+        uint64_t k = 0;
+        for (uint32_t t0 = 0; t0 < G; t0 += 64) {
+            uint32_t rows = 0;
+            for (uint32_t gg = t0; gg < t0 + 64 && gg < G; gg++) { const uint32_t nx = u32at(host + q.o_nsub, gg); rows = nx > rows ? nx : rows; }
+            for (uint32_t row = 0; row < rows; row++)
+                for (uint32_t gg = t0; gg < t0 + 64 && gg < G; gg++) {
+                    if (u32at(host + q.o_nsub, gg) <= row) continue;
+                    const uint32_t col = u32at(p, 2 * k), er = u32at(p, 2 * k + 1);
+                    k++;
+                    if (er >= R || col >= u32at(host + q.o_len, (uint64_t)er * G + gg)) return bad("a submission outside its row");
+                }
+        }
+    }
+    const uint64_t c = std::max<uint64_t>(h.n_cells, s->cap_c), r = std::max<uint64_t>(h.n_replies, s->cap_r), x = std::max<uint64_t>(h.n_exec, s->cap_x);
+    if (c != s->cap_c || r != s->cap_r || x != s->cap_x)
+        if (int rc = epsnap_alloc(s, c, r, x)) return rc;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    s->buf.filled = false;
+    if (int rc = epsnap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
+    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
+    return SMR_OK;
+}
 
 }  // extern "C"

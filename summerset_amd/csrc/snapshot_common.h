@@ -1,4 +1,4 @@
-// What the four device-resident snapshots (mp_snapshot.h, raft_snapshot.h, rsp_snapshot.h, ps_snapshot.h) have in common: how a
+// What the five device-resident snapshots (mp_snapshot.h, raft_snapshot.h, rsp_snapshot.h, ps_snapshot.h, ep_snapshot.h) have in common: how a
 // launch is cut into tiles, how a record finds its place in an image, the sharded counters, and the host's handling of the device
 // buffer and of an image's outer checks.  The formats and the field moves stay with the engines.
 //

@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .snapshot import DeviceSnapshot
 from ._lib import EpCfg, EpDumpBufs, EpExpPrepare, EpExpPrepareReply, EpMsg, check, stream_ptr
 
 NONE, NO_KEY = 0xFFFFFFFF, 0xFF
@@ -25,6 +26,45 @@ NONE, NO_KEY = 0xFFFFFFFF, 0xFF
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+class EPaxosSnapshot(DeviceSnapshot):
+    """One replica object's state between two handler calls, held on the device (`smr_ep_snapshot`): what
+    `EPaxosReplicaGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
+    two replicas whose dumps agree -- and `import_` takes one back (of a replica like the one this snapshot was made for; any
+    window).  `create_like`: room for every ring cell live and a full submission list.  `info()`: bytes, n_cells, n_exec,
+    n_groups, window, n_keys, max_live, max_exec, population, me, optimized_quorum, execute, recovery"""
+    _STEM, _INFO = "smr_ep_snapshot", _lib.EpSnapshotInfo
+
+    def save(self, replica, stream=None):
+        """`replica.save_state(self)`"""
+        check(self._L.smr_ep_save_state(replica._h, self._h, stream_ptr(stream)))
+        return self
+
+    def load(self, replica, stream=None):
+        """`replica.load_state(self)`"""
+        check(self._L.smr_ep_load_state(replica._h, self._h, stream_ptr(stream)))
+
+
+def _handles(xs):
+    return (C.c_void_p * len(xs))(*[x._h for x in xs])
+
+
+def save_cluster_state(reps, snaps=None, stream=None):
+    """`reps[k].save_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch
+    (`smr_ep_cluster_save_state`); returns the snapshots (new ones without `snaps`)"""
+    snaps = [EPaxosSnapshot(r) for r in reps] if snaps is None else list(snaps)
+    if len(snaps) != len(reps):
+        raise ValueError("save_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_ep_cluster_save_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_state(reps, snaps, stream=None):
+    """`reps[k].load_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch (`smr_ep_cluster_load_state`)"""
+    if len(snaps) != len(reps):
+        raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_ep_cluster_load_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
 
 
 class EPaxosReplicaGroup:
@@ -95,6 +135,17 @@ class EPaxosReplicaGroup:
         check(self._L.smr_ep_handle_accept_replies_at(self._h, _ptr(row), _ptr(col), _ptr(ballot), _ptr(flags), _ptr(order),
                                                       _ptr(r["committed"]), stream_ptr(stream)))
         return r
+
+    def save_state(self, snap=None, stream=None):
+        """my whole logical state into a device-resident snapshot (a new one, or `snap` again), between two handler calls; one
+        kernel on `stream`, nothing is read back"""
+        snap = EPaxosSnapshot(self) if snap is None else snap
+        return snap.save(self, stream)
+
+    def load_state(self, snap, stream=None):
+        """overwrite my whole logical state with a snapshot's (`smr_ep_load_state`): same n_groups, population, replica id,
+        optimized_quorum, execute, recovery, n_keys and window"""
+        snap.load(self, stream)
 
     # ---- explicit prepare (recovery=True) ----
     def heartbeat_timeout(self, src, exploded=None, stream=None):

@@ -1,7 +1,7 @@
 """The one host-side handle of a device-resident snapshot (`smr_*_snapshot`, csrc/snapshot_common.h).
 
-`MpSnapshot`, `RaftSnapshot`, `RSPaxosSnapshot` and `PayloadStoreSnapshot` name their C symbols and their info struct; what a
-snapshot object does on the host -- make, close, ask its sizes, export, import -- is the same for all four and lives here.
+`MpSnapshot`, `RaftSnapshot`, `RSPaxosSnapshot`, `PayloadStoreSnapshot` and `EPaxosSnapshot` name their C symbols and their info
+struct; what a snapshot object does on the host -- make, close, ask its sizes, export, import -- is the same for all five and lives here.
 """
 import ctypes as C
 
