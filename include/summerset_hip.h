@@ -469,6 +469,13 @@ int smr_mp_debug_generic_units(smr_mp_cluster *c, uint8_t rep, uint64_t *out);
  * measured a wash -- DESIGN.md 10) */
 int smr_mp_debug_folded_batches(smr_mp_cluster *c, uint8_t rep, uint64_t *out);
 
+/* debug: what the side launch of smr_mp_run_ticks (straggler list on) did with its listed groups, in group-ticks since the
+ * cluster was created (or loaded): out[0] = ticks of a listed group taken by the block-cooperative steady step (prepared
+ * leader, followers following, nothing in flight: one round of loads, one barrier -- DESIGN.md 4), out[1] = ticks that went
+ * through the round bodies (leader changes, redirects, back-pressure, frozen groups; all of them with SMR_MP_SIDE_STEADY=0
+ * in the environment at smr_mp_cluster_create).  A performance, not a correctness, figure.  Synchronises the device. */
+int smr_mp_debug_side_steps(smr_mp_cluster *c, uint64_t out[2]);
+
 /* the straggler list (smr_mp_cfg.straggler_ticks): out[0] = its capacity in groups (0: list off), out[1] = the number of
  * groups the LAST mark pass (of smr_mp_tick / of a smr_mp_run_ticks batch) wanted on it.  out[1] > out[0]: the list was
  * full and the groups beyond it stayed with the bulk kernels (same results, slower tick).  Synchronises the device. */

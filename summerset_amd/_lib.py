@@ -274,6 +274,7 @@ SYMBOLS = [
     ("smr_mp_counters", _i, [_vp, _u8, C.POINTER(_u64 * 3)]),
     ("smr_mp_debug_generic_units", _i, [_vp, _u8, C.POINTER(_u64)]),
     ("smr_mp_debug_folded_batches", _i, [_vp, _u8, C.POINTER(_u64)]),
+    ("smr_mp_debug_side_steps", _i, [_vp, C.POINTER(_u64 * 2)]),
     ("smr_mp_debug_stamps", _i, [_vp, _vp]),
     ("smr_comm_unique_id", _i, [_vp, _u64]),
     ("smr_comm_init_rank", _i, [_vp, _u64, _u32, _u32, C.POINTER(_vp)]),

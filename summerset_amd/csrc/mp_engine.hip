@@ -1498,37 +1498,164 @@ __global__ __launch_bounds__(512, STRAG_MINW) void mp_straggler_tick(const MpPar
 #ifndef STRAG_BATCH_MINW
 #define STRAG_BATCH_MINW STRAG_MINW
 #endif
-__global__ __launch_bounds__(512, STRAG_BATCH_MINW) void mp_straggler_batch(const MpParams *__restrict__ Pp, int lpar, const MpTickBatch B) {
+#ifdef STRAG_PACK
+#define SIDE_K STRAG_PACK
+#else
+#define SIDE_K STRAG_BATCH_K
+#endif
+static_assert(SIDE_K >= 1 && SIDE_K <= 32, "listed groups per block: a bit each in the tick's `done` mask");
+constexpr uint32_t SIDE_REC = 6;   // words of LDS per (listed lane, replica): leader, ok, log_len, ballot lo / hi, pad
+
+// A listed group's QUIET tick -- prepared leader, followers following it with their logs at its log end, nothing in flight -- as
+// ONE step of the block (wavefront w = replica w, all 64 lanes on group g in uniform mode).  Through the round bodies such a tick
+// is four generic jobs per replica with a barrier between them, each of which reloads the replica's scalars and then walks
+// overflow flag -> inputs -> outbox count -> ob_reg -> entries in dependent round trips, and the followers' job (r2_generic's
+// first choice) ends their run and stores ballot and meta per message.  Here every wavefront makes one round of independent
+// loads, the replicas' parts of the predicate meet in a few words of LDS, and the tick is the three fast paths the bulk kernels
+// take for the same state: the leader's r1_coop_append, the followers' "regular outbox" append of r2_body (token only, run
+// extended, one ack-bits word; the tokens come from req_val, which is what the leader puts into ob_val), one barrier, then
+// r3_accept_replies / r3_publish_hb on the Lane that is still in registers.  R4 stays with the caller (r4_body, as before).
+// false = not that state: nothing was stored, the caller runs the round bodies for this group and tick.
+// The predicate implies exactly the fast paths' own preconditions:
+//   * no HearTimeout for the group this tick, group not frozen, r1_done clear;
+//   * no client batches, or n_req <= 64 of them addressed to the leader l every replica names;
+//   * l: r1_coop_append's conditions, with an empty outbox of this parity (so the outbox is a pure run through ob_reg);
+//   * every follower: leader == l, bal_max_seen == l's bal_prepared, accept_bar == log_len == l's log_len, room in its window for
+//     n_req slots, an empty outbox of this parity;
+//   * PrepareReplies: a count still standing at the start of a tick was consumed by the R3 of the tick that sent it (r2_body
+//     clears it first thing); the followers' step clears it the same way.
+__device__ __forceinline__ bool side_steady_tick(const MpParams &P, int par, const MpTickIn &in, const uint32_t g, const uint32_t w,
+                                                 uint32_t *__restrict__ sh) {
+    const bool rep = w < P.R;
+    Lane J(P, rep ? w : 0, g, par);
+    J.set_uniform();
+    const RepView &v = J.v;
+    // the one round of loads: nothing below is waited for before all of them are out
+    const uint32_t to = in.timeout_rep ? in.timeout_rep[g] : NO_REP;
+    const uint32_t tgt = in.req_target ? in.req_target[g] : NO_REP;
+    uint32_t n = in.req_target ? in.req_cnt[g] : 0u;
+    const uint32_t tok = (in.req_target && J.cl < in.S) ? in.req_val[(size_t)J.cl * P.G + g] : 0u;
+    const uint32_t frozen = P.overflow[g], r1d = P.r1_done[g];
+    uint32_t c_par = 0, pr_mine = 0;
+    if (rep) {
+        J.load();
+        c_par = v.ob_cnt(par)[g];
+        pr_mine = v.pr_cnt()[g];
+    }
+    if (n > in.S) n = in.S;
+    if (tgt >= P.R) n = 0;
+    const bool lead = rep && J.is_leader();
+    bool ok = rep && to == NO_REP && !frozen && r1d == 0 && c_par == 0 && J.leader < P.R && (n == 0 || tgt == J.leader) && n <= 64u;
+    if (lead)
+        ok = ok && J.bpd != 0 && J.bpd == J.bms && P.thresh > 1 && J.nlb >= J.len && J.abar == J.len && n <= P.cap &&
+             (J.len - J.start) + n + P.win_reserve <= P.W;
+    else
+        ok = ok && J.abar == J.len && (J.len - J.start) + n <= P.W;
+    if (rep && J.wr) {
+        const uint64_t bal = lead ? J.bpd : J.bms;
+        uint32_t *const my = sh + w * SIDE_REC;
+        my[0] = J.leader; my[1] = ok ? 1u : 0u; my[2] = J.len; my[3] = (uint32_t)bal; my[4] = (uint32_t)(bal >> 32);
+    }
+    __syncthreads();
+    const uint32_t l = sh[0];
+    bool all = l < P.R;
+    if (all) {
+        const uint32_t *const lr = sh + l * SIDE_REC;
+        for (uint32_t q = 0; q < P.R; q++) {
+            const uint32_t *const qr = sh + q * SIDE_REC;
+            all = all && qr[1] != 0 && qr[0] == l && qr[2] == lr[2] && qr[3] == lr[3] && qr[4] == lr[4];
+        }
+    }
+    if (!all) return false;                                      // (block-uniform: every wavefront read the same words)
+    if (rep) {
+        if (lead) {
+            if (n) {
+                if (par == 0) { J.obn0 = 0; J.obl0 = true; } else { J.obn1 = 0; J.obl1 = true; }   // (the count just loaded)
+                (void)r1_coop_append(J, par, in.req_val, n);     // its conditions are the predicate's
+            }
+        } else {
+            if (pr_mine && J.wr) v.pr_cnt()[g] = 0;
+            if (n) {
+                // mp_round_deliver's regular-outbox fast path, lane k = message k: Accepts at my bal_max_seen for slots len, len + 1, ...
+                const RepView snd{P.rep[0], (size_t)l * P.rep_stride};
+                const uint32_t r = J.me, k = J.cl;
+                if (k < n) {
+                    v.s_val()[tix(P.W, (J.len + k) & P.Wmask, g)] = tok;   // neither ballot nor meta: the run (mp_device.h: end_run)
+                    ACK_STORE(snd.ack(), k, 1);
+                }
+                if (J.wr) ack_bits_base(snd.ack(), P.cap, P.G)[tix(MAXR, r, g)] = ack_range_bits(0, n);
+                if (J.nlb == J.len) J.nlb = J.len + n;           // still no Null below the log end
+                if (J.brun == 0xFFFFFFFFu || J.brun > J.len) J.brun = J.len;   // appended at bal_max_seen
+                J.len += n; J.abar = J.len;
+            }
+        }
+    }
+    __syncthreads();                                             // the followers' answers before the leader's tally; and nobody writes the
+                                                                 // next tick's records while a wavefront still reads this tick's
+    if (rep) {
+        if (lead && n) { if (P.R <= 5) r3_accept_replies<5>(J, in.ackctl, n); else r3_accept_replies<MAXR>(J, in.ackctl, n); }
+        if (in.heartbeat) r3_publish_hb(J);
+        J.store();
+        flush_job(J);
+    }
+    return true;
+}
+
+// Round 7: most of a listed group's ticks are QUIET -- mp_mark_batch lists a group for the whole batch, its change takes one or two
+// of the batch's ticks -- and a quiet tick through the cooperative round bodies is still ~30 dependent round trips (each round
+// reloads the replica's scalars and walks flag -> inputs -> count -> ob_reg -> entries) behind three barriers.  With `steady`
+// (smr_mp_cluster.side_steady; SMR_MP_SIDE_STEADY=0 in the environment turns it off) every listed group first tries
+// side_steady_tick, per tick: one round of loads, the predicate through LDS, the bulk kernels' three fast paths, two barriers.
+// A tick the predicate refuses runs the round bodies exactly as before; R4 is r4_body for both.  Counters 5 / 6 of replica 0:
+// group-ticks through the step / through the round bodies (smr_mp_debug_side_steps).
+__global__ __launch_bounds__(512, STRAG_BATCH_MINW) void mp_straggler_batch(const MpParams *__restrict__ Pp, int lpar, const MpTickBatch B, int steady) {
+    __shared__ uint32_t sh_side[SIDE_K * MAXR * SIDE_REC];
     const MpParams &P = *Pp;
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     uint32_t n = P.slow_n[lpar];
     if (n > P.slow_cap) n = P.slow_cap;
+    uint32_t n_step = 0, n_round = 0;
 #ifdef STRAG_PACK                                                 // (experiments: STRAG_PACK listed groups side by side in a block from the first one on)
     for (uint32_t idx0 = blockIdx.x * STRAG_PACK; idx0 < n; idx0 += gridDim.x * STRAG_PACK) {
         const uint32_t idx = idx0 + lane;
-        const bool mine = w < P.R && lane < STRAG_PACK && idx < n;
 #else
     for (uint32_t idx0 = blockIdx.x; idx0 < n; idx0 += gridDim.x * STRAG_BATCH_K) {  // uniform per block
         const uint32_t idx = idx0 + lane * gridDim.x;
-        const bool mine = w < P.R && lane < STRAG_BATCH_K && idx < n;
 #endif
-        const uint32_t g = mine ? P.slow_list[idx] : P.G;
+        const bool listed = lane < SIDE_K && idx < n;               // (the same lanes in every wavefront)
+        const bool mine = w < P.R && listed;
+        const uint32_t g = listed ? P.slow_list[idx] : P.G;
         const uint32_t r = w < P.R ? w : 0;
+        const uint32_t nk = (uint32_t)__popcll(__ballot(listed));   // listed lanes are 0 .. nk - 1
         for (uint32_t t = 0; t < B.n; t++) {
             const MpTickIn &in = B.t[t];
             const int par = B.par0 ^ (int)(t & 1u);
-            if (in.timeout_rep || in.req_target)
-                r1_body(P, par, in.timeout_rep, in.timeout_src, in.req_target, in.req_cnt, in.req_val, in.S, g, mine && !P.overflow[g], r, STRAG_COOP);
-            __syncthreads();
-            r2_body<0>(P, par, g, mine && !P.overflow[g], r, STRAG_COOP);
-            __syncthreads();
-            r3_body(P, par, in.ackctl, in.heartbeat, g, mine && !P.overflow[g], r, STRAG_COOP);
-            __syncthreads();
+            uint32_t done = 0;                                       // bit k: lane k's group took the steady step this tick (block-uniform)
+            if (steady)
+                for (uint32_t k = 0; k < nk; k++)                    // one listed group at a time, all wavefronts at once
+                    if (side_steady_tick(P, par, in, __shfl(g, (int)k), w, sh_side + k * (MAXR * SIDE_REC))) done |= 1u << k;
+            n_step += (uint32_t)__popc(done); n_round += nk - (uint32_t)__popc(done);
+            if (done != (nk >= 32u ? ~0u : (1u << nk) - 1u)) {
+                const bool rest = mine && !((done >> (lane & 31u)) & 1u);
+                if (in.timeout_rep || in.req_target)
+                    r1_body(P, par, in.timeout_rep, in.timeout_src, in.req_target, in.req_cnt, in.req_val, in.S, g, rest && !P.overflow[g], r, STRAG_COOP);
+                __syncthreads();
+                r2_body<0>(P, par, g, rest && !P.overflow[g], r, STRAG_COOP);
+                __syncthreads();
+                r3_body(P, par, in.ackctl, in.heartbeat, g, rest && !P.overflow[g], r, STRAG_COOP);
+                __syncthreads();
+            } else if (in.heartbeat) {
+                __syncthreads();                                     // the records the step published before R4 reads them
+            }
             if (in.heartbeat) {
                 r4_body(P, par, g, mine && !P.overflow[g], r);
                 __syncthreads();
             }
         }
+    }
+    if (threadIdx.x == 0) {
+        if (n_step) ctr_add((unsigned long long *)P.rep[0].counters, 5, (unsigned long long)n_step);
+        if (n_round) ctr_add((unsigned long long *)P.rep[0].counters, 6, (unsigned long long)n_round);
     }
 }
 
@@ -2023,6 +2150,8 @@ struct smr_mp_cluster {
     bool no_split_r2 = true;         // the split is OFF unless SMR_MP_SPLIT_R2 is in the environment at smr_mp_create: measured, it does not
                                      // pay (profiles/r8i: fast path alone 24.2 us + rest 4.9 us against 26.8 us for the one launch)
     bool split_r2 = false;           // smr_mp_run_ticks, the side stream busy: R2's bulk launch = fast path + rest (r2_body)
+    bool side_steady = true;         // smr_mp_run_ticks' side launch takes a listed group's quiet ticks as one block-cooperative step
+                                     // (side_steady_tick); SMR_MP_SIDE_STEADY=0 in the environment at smr_mp_create: the round bodies alone
     MpNextLocal next_local = MpNextLocal{nullptr, nullptr, nullptr, nullptr, 0u};   // smr_mp_run_ticks: the NEXT tick's client batches, for the tally launch of this one (round 6)
     bool fold_r1 = false;            // SMR_MP_FOLD_R1 in the environment at smr_mp_create: the tally launch of tick t also runs the leaders' steady-state
                                      // appends of tick t + 1 (built, tested both ways, off by default: a wash -- profiles/s18, s19)
@@ -2223,6 +2352,7 @@ int smr_mp_cluster_create(const smr_mp_cfg *cfg, smr_mp_cluster **out) {
     }
     c->ttl = cfg->straggler_ticks == SMR_STRAGGLER_OFF ? 0u : cfg->straggler_ticks;
     c->no_split_r2 = getenv("SMR_MP_SPLIT_R2") == nullptr;
+    { const char *e_ = getenv("SMR_MP_SIDE_STEADY"); c->side_steady = !(e_ && e_[0] == '0' && e_[1] == 0); }
     c->always_defer = getenv("SMR_MP_ALWAYS_DEFER_REST") != nullptr;
     c->fold_r1 = getenv("SMR_MP_FOLD_R1") != nullptr;
     if (c->ttl) {
@@ -2460,7 +2590,7 @@ int smr_mp_run_ticks(smr_mp_cluster *c, const smr_mp_tick_in *ticks, uint32_t n,
         SMR_HIP_TRY(hipGetLastError());
         SMR_HIP_TRY(hipEventRecord(c->ev_fork, st));
         SMR_HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        hipLaunchKernelGGL(mp_straggler_batch, dim3(STRAG_BATCH_BLOCKS), dim3(R <= 5 ? 320 : 512), 0, c->side, c->dp, c->lpar, b);
+        hipLaunchKernelGGL(mp_straggler_batch, dim3(STRAG_BATCH_BLOCKS), dim3(R <= 5 ? 320 : 512), 0, c->side, c->dp, c->lpar, b, c->side_steady ? 1 : 0);
         SMR_HIP_TRY(hipGetLastError());
         c->marked = c->side_on = c->forked = c->side_fused = true;   // the round calls below: bulk only, no fork of their own
         c->split_r2 = !quiet && !c->no_split_r2;
@@ -2827,6 +2957,15 @@ int smr_mp_debug_folded_batches(smr_mp_cluster *c, uint8_t rep, uint64_t *out) {
     unsigned long long h[5];
     SMR_HIP_TRY(ctr_read((const unsigned long long *)c->hp.rep[rep].counters, 5, h));
     *out = h[4];
+    return SMR_OK;
+}
+
+int smr_mp_debug_side_steps(smr_mp_cluster *c, uint64_t out[2]) {
+    if (!c || !out) return fail(SMR_ERR_ARG, "mp: bad argument");
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    unsigned long long h[7];
+    SMR_HIP_TRY(ctr_read((const unsigned long long *)c->hp.rep[0].counters, 7, h));   // (mp_straggler_batch counts both at replica 0)
+    out[0] = h[5]; out[1] = h[6];
     return SMR_OK;
 }
 

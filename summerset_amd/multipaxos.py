@@ -199,6 +199,13 @@ class MultiPaxosCluster:
         check(self._L.smr_mp_debug_folded_batches(self._h, rep, C.byref(n)))
         return int(n.value)
 
+    def debug_side_steps(self):
+        """(steady, round): group-ticks the side launch of `run_ticks` took through its block-cooperative steady step and through
+        the round bodies (`SMR_MP_SIDE_STEADY=0` in the environment at creation: all of them the latter)"""
+        arr = (C.c_uint64 * 2)()
+        check(self._L.smr_mp_debug_side_steps(self._h, C.byref(arr)))
+        return int(arr[0]), int(arr[1])
+
     def straggler_stats(self):
         """(capacity of the straggler list, groups the last mark pass wanted on it): more wanted than capacity = the list
         overflowed and the rest stayed with the bulk kernels (`smr_mp_straggler_stats`)"""
