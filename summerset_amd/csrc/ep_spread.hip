@@ -23,11 +23,10 @@
 #include <algorithm>
 #include <vector>
 
-#include "smr_common.h"
+#include "spread_common.h"
 
 namespace smr {
 
-constexpr int ES_MAXR = SMR_MAX_REPLICAS;
 constexpr uint32_t ES_OPS = 96;                  // copy operations per launch (the kernel's arguments hold them)
 struct EsOp { const uint8_t *src; uint8_t *dst; const uint8_t *drop; uint32_t bytes, fill; };   // drop: dst[i] = drop[i] ? 0 : src[i]; src NULL: dst[i] = fill
 struct EsOps { uint32_t n; EsOp op[ES_OPS]; };
@@ -64,14 +63,12 @@ static inline uint64_t es_msg_bytes(int kind, uint64_t G, uint64_t R) {
 
 using namespace smr;
 
-struct EsSlot { uint8_t *p = nullptr; };            // where a message lies this tick (a slot of sbuf / rbuf / lbuf)
 struct EsMsg { uint32_t b, a, z; };                 // block, from replica, to replica
-struct EsPlan {
+struct EsPlan : SpreadPlan {
     int kind = 0;
     std::vector<uint32_t> leaders;
-    std::vector<uint64_t> in_split, out_split;      // bytes to / from every rank
-    uint64_t n_send = 0, n_recv = 0, n_local = 0;
-    uint8_t *sbuf = nullptr, *rbuf = nullptr, *lbuf = nullptr;
+    uint64_t n_local = 0;                           // messages between two replicas of this rank: a buffer of their own, not exchanged
+    uint8_t *lbuf = nullptr;
     // slot of the message (b, a, z) that touches this rank: [b][a][z] -> pointer (NULL: not mine)
     std::vector<uint8_t *> slot;
 };
@@ -85,26 +82,19 @@ struct EsRep {                                      // a (block, replica) that l
     uint64_t *st_ballot = nullptr, *st_seq = nullptr, *a_ballot = nullptr;
     uint32_t *st_deps = nullptr;                           // [R][R][G]
 };
-struct smr_ep_spread {
-    uint32_t world = 0, rank = 0, R = 0, ordered = 0;
-    std::vector<uint32_t> block_groups;
-    std::vector<EsRep> reps;
-    std::vector<int> rep_of;                        // [b * R + r] -> index into reps, -1
+struct smr_ep_spread : SpreadJob {
+    uint32_t ordered = 0;
+    std::vector<EsRep> reps;                        // in create's order (rep_of's index)
     std::vector<EsPlan> plans;                      // in exchange order
     std::vector<uint8_t *> peer_c;                  // [b * R + s]: u8 [G_b] = s      (blocks with a replica here)
     std::vector<uint64_t *> bal_c;                  // [b * R + s]: u64 [G_b] = s + 1
-    char *arena = nullptr;
-    smr_comm *comm = nullptr;
-    uint32_t next_seg = 0;
-    uint64_t bytes_sent = 0;
     EsOps ops;
 };
 
 namespace smr {
-static inline uint32_t es_home(uint32_t b, uint32_t r, uint32_t world) { return (b + r) % world; }
 static inline size_t es_ix(const smr_ep_spread *s, uint32_t b, uint32_t a, uint32_t z) { return ((size_t)b * s->R + a) * s->R + z; }
 
-// the message list of one exchange, in the order every rank derives it in (spread_ep.py _plan): blocks, then leaders, then peers
+// the message list of one exchange in its canonical order (spread_ep.py _plan has the same): blocks, then leaders, then peers
 static void es_plan_msgs(const smr_ep_spread *s, const EsPlan &p, std::vector<EsMsg> &out) {
     for (uint32_t b = 0; b < s->world; b++) {
         if (!s->block_groups[b]) continue;
@@ -146,31 +136,18 @@ extern "C" {
 
 int smr_ep_spread_create(smr_ep_replica *const *reps, const uint32_t *rep_block, const uint8_t *rep_id, uint32_t n_reps,
                          const uint32_t *block_groups, uint32_t world, uint32_t rank, uint8_t population, int ordered, smr_ep_spread **out) {
-    if (!out || !block_groups || (n_reps && (!reps || !rep_block || !rep_id))) return fail(SMR_ERR_ARG, "epaxos spread: null argument");
-    if (world == 0 || rank >= world) return fail(SMR_ERR_ARG, "epaxos spread: rank / world");
-    if (population < 3 || population > ES_MAXR) return fail(SMR_ERR_ARG, "epaxos spread: population must be in 3..8");
+    static const std::string who = "epaxos spread";
+    int rc = spread_check_args(who, out, reps, rep_block, rep_id, n_reps, block_groups, world, rank, population);
+    if (rc != SMR_OK) return rc;
     smr_ep_spread *s = new smr_ep_spread();
-    s->world = world; s->rank = rank; s->R = population; s->ordered = ordered ? 1 : 0;
-    s->block_groups.assign(block_groups, block_groups + world);
-    s->rep_of.assign((size_t)world * population, -1);
+    s->ordered = ordered ? 1 : 0;
+    if ((rc = spread_seat(s, who, reps, rep_block, rep_id, n_reps, block_groups, world, rank, population)) != SMR_OK) { delete s; return rc; }
     const uint64_t R = population;
     for (uint32_t i = 0; i < n_reps; i++) {
-        const uint32_t b = rep_block[i], r = rep_id[i];
-        if (!reps[i] || b >= world || r >= population || es_home(b, r, world) != rank || !block_groups[b] || s->rep_of[(size_t)b * R + r] >= 0) {
-            delete s;
-            return fail(SMR_ERR_ARG, "epaxos spread: replica r of block b lives on rank (b + r) mod world, once, and only where the block has groups");
-        }
         EsRep x;
-        x.e = reps[i]; x.b = b; x.r = r; x.G = block_groups[b];
-        s->rep_of[(size_t)b * R + r] = (int)s->reps.size();
+        x.e = reps[i]; x.b = rep_block[i]; x.r = rep_id[i]; x.G = block_groups[x.b];
         s->reps.push_back(x);
     }
-    for (uint32_t b = 0; b < world; b++)
-        for (uint32_t r = 0; r < population; r++)
-            if (block_groups[b] && es_home(b, r, world) == rank && s->rep_of[(size_t)b * R + r] < 0) {
-                delete s;
-                return fail(SMR_ERR_ARG, "epaxos spread: a replica that lives on this rank was not handed over");
-            }
     // the exchanges: PreAccept, PreAcceptReply for all leaders; then Accept / AcceptReply / CommitNotice per leader set
     std::vector<std::vector<uint32_t>> sets;
     std::vector<uint32_t> all;
@@ -181,27 +158,22 @@ int smr_ep_spread_create(smr_ep_replica *const *reps, const uint32_t *rep_block,
     add(ES_PRE_ACCEPT, all); add(ES_PA_REPLY, all);
     for (auto &ld : sets) { add(ES_ACCEPT, ld); add(ES_ACC_REPLY, ld); add(ES_COMMIT, ld); }
     // sizes first, one arena, then the pointers
-    size_t bytes = 0;
-    auto take = [&](size_t n) { size_t o = bytes; bytes = (bytes + n + 255) & ~(size_t)255; return o; };
+    SpreadArena ar;
+    auto take = [&](size_t n) { return ar.take(n); };
     struct Off { size_t sbuf, rbuf, lbuf; };
     std::vector<Off> poff(s->plans.size());
-    std::vector<std::vector<std::pair<EsMsg, uint64_t>>> psend(s->plans.size()), precv(s->plans.size()), ploc(s->plans.size());
+    std::vector<std::vector<SpreadMsg>> pmsg(s->plans.size()), ploc(s->plans.size());      // through the exchange; inside this rank (soff: in lbuf)
     for (size_t k = 0; k < s->plans.size(); k++) {
         EsPlan &p = s->plans[k];
-        p.in_split.assign(world, 0); p.out_split.assign(world, 0);
         std::vector<EsMsg> msgs;
         es_plan_msgs(s, p, msgs);
-        std::vector<EsMsg> send, recv;
         for (const EsMsg &m : msgs) {
-            const uint32_t src = es_home(m.b, m.a, world), dst = es_home(m.b, m.z, world);
-            if (src == rank && dst != rank) send.push_back(m);
-            if (dst == rank && src != rank) recv.push_back(m);
-            if (src == rank && dst == rank) { ploc[k].push_back({m, p.n_local}); p.n_local += es_msg_bytes(p.kind, block_groups[m.b], R); }
+            const uint32_t src = spread_home(m.b, m.a, world), dst = spread_home(m.b, m.z, world);
+            const uint64_t n = es_msg_bytes(p.kind, block_groups[m.b], R);
+            if (src != dst) pmsg[k].push_back(SpreadMsg{src, dst, es_ix(s, m.b, m.a, m.z), n, 0, 0});
+            else if (src == rank) { ploc[k].push_back(SpreadMsg{src, dst, es_ix(s, m.b, m.a, m.z), n, p.n_local, 0}); p.n_local += n; }
         }
-        std::stable_sort(send.begin(), send.end(), [&](const EsMsg &x, const EsMsg &y) { return es_home(x.b, x.z, world) < es_home(y.b, y.z, world); });
-        std::stable_sort(recv.begin(), recv.end(), [&](const EsMsg &x, const EsMsg &y) { return es_home(x.b, x.a, world) < es_home(y.b, y.a, world); });
-        for (const EsMsg &m : send) { const uint64_t n = es_msg_bytes(p.kind, block_groups[m.b], R); psend[k].push_back({m, p.n_send}); p.n_send += n; p.in_split[es_home(m.b, m.z, world)] += n; }
-        for (const EsMsg &m : recv) { const uint64_t n = es_msg_bytes(p.kind, block_groups[m.b], R); precv[k].push_back({m, p.n_recv}); p.n_recv += n; p.out_split[es_home(m.b, m.a, world)] += n; }
+        spread_layout(pmsg[k], rank, world, p);
         poff[k] = Off{take(std::max<uint64_t>(p.n_send, 8)), take(std::max<uint64_t>(p.n_recv, 8)), take(std::max<uint64_t>(p.n_local, 8))};
     }
     struct RepOff { size_t pa_flags, masked, slow, acc, pa_col, pa_deps, pa_seq, st_flags, a_flags, st_ballot, st_seq, a_ballot, st_deps; };
@@ -218,15 +190,18 @@ int smr_ep_spread_create(smr_ep_replica *const *reps, const uint32_t *rep_block,
         if (!here) continue;
         for (uint32_t r = 0; r < population; r++) { pc_off[(size_t)b * R + r] = take(block_groups[b]); bc_off[(size_t)b * R + r] = take(8 * (size_t)block_groups[b]); }
     }
-    if (hipMalloc((void **)&s->arena, bytes + 256) != hipSuccess) { delete s; return fail(SMR_ERR_DEVICE, "epaxos spread: hipMalloc failed"); }
-    if (hipMemset(s->arena, 0, bytes + 256) != hipSuccess) { (void)hipFree(s->arena); delete s; return fail(SMR_ERR_DEVICE, "epaxos spread: hipMemset failed"); }
+    const hipError_t cleared = ar.alloc_zeroed(&s->arena);
+    if (!s->arena) { delete s; return fail(SMR_ERR_DEVICE, "epaxos spread: hipMalloc failed"); }
+    if (cleared != hipSuccess) { (void)hipFree(s->arena); delete s; return fail(SMR_ERR_DEVICE, "epaxos spread: hipMemset failed"); }
     for (size_t k = 0; k < s->plans.size(); k++) {
         EsPlan &p = s->plans[k];
         p.sbuf = (uint8_t *)s->arena + poff[k].sbuf; p.rbuf = (uint8_t *)s->arena + poff[k].rbuf; p.lbuf = (uint8_t *)s->arena + poff[k].lbuf;
         p.slot.assign((size_t)world * R * R, nullptr);
-        for (auto &x : psend[k]) p.slot[es_ix(s, x.first.b, x.first.a, x.first.z)] = p.sbuf + x.second;
-        for (auto &x : precv[k]) p.slot[es_ix(s, x.first.b, x.first.a, x.first.z)] = p.rbuf + x.second;
-        for (auto &x : ploc[k]) p.slot[es_ix(s, x.first.b, x.first.a, x.first.z)] = p.lbuf + x.second;
+        for (const SpreadMsg &m : pmsg[k]) {
+            if (m.src == rank) p.slot[m.slot] = p.sbuf + m.soff;
+            if (m.dst == rank) p.slot[m.slot] = p.rbuf + m.roff;
+        }
+        for (const SpreadMsg &m : ploc[k]) p.slot[m.slot] = p.lbuf + m.soff;
     }
     s->peer_c.assign((size_t)world * R, nullptr); s->bal_c.assign((size_t)world * R, nullptr);
     hipError_t err = hipSuccess;
@@ -269,24 +244,10 @@ void smr_ep_spread_destroy(smr_ep_spread *s) {
 int smr_ep_spread_n_exchanges(const smr_ep_spread *s) { return s ? (int)s->plans.size() : SMR_ERR_ARG; }
 
 int smr_ep_spread_buffers(smr_ep_spread *s, uint32_t exchange, void **send_dev, uint64_t *send_bytes, void **recv_dev, uint64_t *recv_bytes) {
-    if (!s || exchange >= s->plans.size() || !send_dev || !send_bytes || !recv_dev || !recv_bytes) return fail(SMR_ERR_ARG, "epaxos spread: bad argument");
-    const EsPlan &p = s->plans[exchange];
-    *send_dev = p.sbuf; *recv_dev = p.rbuf;
-    for (uint32_t k = 0; k < s->world; k++) { send_bytes[k] = p.in_split[k]; recv_bytes[k] = p.out_split[k]; }
-    return SMR_OK;
+    return spread_buffers(s, "epaxos spread", s && exchange < s->plans.size() ? &s->plans[exchange] : nullptr, send_dev, send_bytes, recv_dev, recv_bytes);
 }
 
-int smr_ep_spread_bind_comm(smr_ep_spread *s, smr_comm *comm) {
-    if (!s) return fail(SMR_ERR_ARG, "epaxos spread: null argument");
-    if (comm) {
-        uint64_t info[5];
-        int rc = smr_comm_info(comm, info);
-        if (rc != SMR_OK) return rc;
-        if (info[0] != s->rank || info[1] != s->world) return fail(SMR_ERR_ARG, "epaxos spread: the communicator's rank / world are not the job's");
-    }
-    s->comm = comm;
-    return SMR_OK;
-}
+int smr_ep_spread_bind_comm(smr_ep_spread *s, smr_comm *comm) { return spread_bind_comm(s, "epaxos spread", comm); }
 
 // segment `seg` of the tick: the compute between exchange seg - 1 (whose receive buffer it reads) and exchange seg (whose send
 // buffer it fills); seg == n_exchanges: behind the last one.  keys_dev / out: per replica of this rank, in smr_ep_spread_create's
@@ -296,14 +257,14 @@ int smr_ep_spread_segment(smr_ep_spread *s, uint32_t seg, const uint8_t *const *
                           const smr_ep_cluster_out *out, void *stream) {
     if (!s || (!keys_dev && !s->reps.empty()) || (!out && !s->reps.empty())) return fail(SMR_ERR_ARG, "epaxos spread: null argument");
     if (seg > s->plans.size()) return fail(SMR_ERR_ARG, "epaxos spread: no such segment");
-    if (seg != s->next_seg) return fail(SMR_ERR_STATE, "epaxos spread: segment " + std::to_string(seg) + " out of order (the open tick expects " + std::to_string(s->next_seg) + ")");
+    int rc = spread_in_order(s, "epaxos spread", seg);
+    if (rc != SMR_OK) return rc;
     for (size_t i = 0; i < s->reps.size(); i++)
         if (!keys_dev[i] || !out[i].proposed || !out[i].col || !out[i].seq0 || !out[i].deps0 || !out[i].decision || !out[i].committed || !out[i].seq || !out[i].deps)
             return fail(SMR_ERR_ARG, "epaxos spread: null key or output array");
     s->next_seg = seg == s->plans.size() ? 0 : seg + 1;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t R = s->R;
-    int rc;
     s->ops.n = 0;
     // ---- what consumes the previous exchange --------------------------------------------------------------------------
     if (seg > 0) {
@@ -419,11 +380,7 @@ int smr_ep_spread_segment(smr_ep_spread *s, uint32_t seg, const uint8_t *const *
     return SMR_OK;
 }
 
-int smr_ep_spread_abort_tick(smr_ep_spread *s) {
-    if (!s) return fail(SMR_ERR_ARG, "epaxos spread: null argument");
-    s->next_seg = 0;
-    return SMR_OK;
-}
+int smr_ep_spread_abort_tick(smr_ep_spread *s) { return spread_abort_tick(s, "epaxos spread"); }
 
 // the whole tick: segments and exchanges back to back on `stream` (smr_ep_spread_bind_comm first; world 1 needs none)
 int smr_ep_spread_tick(smr_ep_spread *s, const uint8_t *const *keys_dev, const uint8_t *const *drop_dev, const smr_ep_cluster_out *out, void *stream) {

@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "smr_common.h"
+#include "spread_common.h"
 
 namespace smr {
 
@@ -55,10 +55,7 @@ static inline uint64_t rss_msg_bytes(int kind, uint64_t G, uint64_t sl) {
 
 using namespace smr;
 
-struct RssPlan {
-    std::vector<uint64_t> in_split, out_split;
-    uint64_t n_send = 0, n_recv = 0;
-    uint8_t *sbuf = nullptr, *rbuf = nullptr;
+struct RssPlan : SpreadPlan {
     // [b * R + q]: the message between block b's leader and its follower q -- where its sender on this rank writes it (sslot), where
     // its receiver on this rank reads it (rslot).  A message between two replicas of this rank goes through the exchange like any
     // other (the rank's own segment: a device copy), as in summerset_amd/spread_rsp.py's plans.
@@ -77,24 +74,17 @@ struct RssRep {
     uint64_t *hb_ballot = nullptr;
     uint32_t *hb_c = nullptr;                       // [3][G] scratch of the Heartbeats the leader "sends back" (dropped)
 };
-struct smr_rsp_spread {
-    uint32_t world = 0, rank = 0, R = 0, W = 0, d = 0;
+struct smr_rsp_spread : SpreadJob {
+    uint32_t W = 0, d = 0;
     uint64_t L = 0, sl = 0;
-    std::vector<uint32_t> block_groups;
-    std::vector<RssRep> reps;
-    std::vector<int> rep_of;
+    std::vector<RssRep> reps;                       // in create's order (rep_of's index)
     RssPlan plans[4];
     std::vector<uint8_t *> peer_c;                  // [b * R + r]: u8 [G_b] = r
-    char *arena = nullptr;
-    smr_comm *comm = nullptr;
-    uint32_t next_seg = 0;
     int open_heartbeat = 0;
-    uint64_t bytes_sent = 0;
     RssOps ops;
 };
 
 namespace smr {
-static inline uint32_t rss_home(uint32_t b, uint32_t r, uint32_t world) { return (b + r) % world; }
 static int rss_flush(smr_rsp_spread *s, hipStream_t st) {
     if (!s->ops.n) return SMR_OK;
     uint32_t most = 0;
@@ -121,62 +111,39 @@ extern "C" {
 int smr_rsp_spread_create(smr_rsp_replica *const *reps, const uint32_t *rep_block, const uint8_t *rep_id, uint32_t n_reps,
                           const uint32_t *block_groups, uint32_t world, uint32_t rank, uint8_t population, uint32_t window, uint64_t data_len,
                           smr_rsp_spread **out) {
-    if (!out || !block_groups || (n_reps && (!reps || !rep_block || !rep_id))) return fail(SMR_ERR_ARG, "rspaxos spread: null argument");
-    if (world == 0 || rank >= world) return fail(SMR_ERR_ARG, "rspaxos spread: rank / world");
-    if (population < 3 || population > RS_MAXR) return fail(SMR_ERR_ARG, "rspaxos spread: population must be in 3..8");
+    static const std::string who = "rspaxos spread";
+    int rc = spread_check_args(who, out, reps, rep_block, rep_id, n_reps, block_groups, world, rank, population);
+    if (rc != SMR_OK) return rc;
     if (data_len == 0 || window == 0) return fail(SMR_ERR_ARG, "rspaxos spread: data_len / window is zero");
     smr_rsp_spread *s = new smr_rsp_spread();
-    s->world = world; s->rank = rank; s->R = population; s->W = window; s->L = data_len;
+    s->W = window; s->L = data_len;
     s->d = population / 2 + 1;
     s->sl = smr_rs_shard_len(data_len, (int)s->d);
-    s->block_groups.assign(block_groups, block_groups + world);
-    s->rep_of.assign((size_t)world * population, -1);
+    if ((rc = spread_seat(s, who, reps, rep_block, rep_id, n_reps, block_groups, world, rank, population)) != SMR_OK) { delete s; return rc; }
     const uint64_t R = population, sl = s->sl;
     for (uint32_t i = 0; i < n_reps; i++) {
-        const uint32_t b = rep_block[i], r = rep_id[i];
-        if (!reps[i] || b >= world || r >= population || rss_home(b, r, world) != rank || !block_groups[b] || s->rep_of[(size_t)b * R + r] >= 0) {
-            delete s;
-            return fail(SMR_ERR_ARG, "rspaxos spread: replica r of block b lives on rank (b + r) mod world, once, and only where the block has groups");
-        }
         RssRep x;
-        x.e = reps[i]; x.b = b; x.r = r; x.G = block_groups[b];
-        s->rep_of[(size_t)b * R + r] = (int)s->reps.size();
+        x.e = reps[i]; x.b = rep_block[i]; x.r = rep_id[i]; x.G = block_groups[x.b];
         s->reps.push_back(x);
     }
-    for (uint32_t b = 0; b < world; b++)
-        for (uint32_t r = 0; r < population; r++)
-            if (block_groups[b] && rss_home(b, r, world) == rank && s->rep_of[(size_t)b * R + r] < 0) {
-                delete s;
-                return fail(SMR_ERR_ARG, "rspaxos spread: a replica that lives on this rank was not handed over");
-            }
-    size_t bytes = 0;
-    auto take = [&](size_t n) { size_t o = bytes; bytes = (bytes + n + 255) & ~(size_t)255; return o; };
-    struct Off { size_t sbuf, rbuf, lbuf; };
+    SpreadArena ar;
+    auto take = [&](size_t n) { return ar.take(n); };
+    struct Off { size_t sbuf, rbuf; };
     Off poff[4];
-    std::vector<std::pair<size_t, uint64_t>> psend[4], precv[4];            // (b * R + q, offset)
+    std::vector<SpreadMsg> pmsg[4];                          // slot = b * R + q: the message between block b's leader and its follower q
     for (int k = 0; k < 4; k++) {
         RssPlan &p = s->plans[k];
-        p.in_split.assign(world, 0); p.out_split.assign(world, 0);
-        struct M { uint32_t src, dst, b, q; };
-        std::vector<M> msgs;
-        for (uint32_t b = 0; b < world; b++) {
+        for (uint32_t b = 0; b < world; b++) {               // the canonical order (spread_rsp.py _plan has the same): blocks, then followers
             if (!block_groups[b]) continue;
-            const uint32_t hl = rss_home(b, 0, world);
+            const uint32_t hl = spread_home(b, 0, world);
             for (uint32_t q = 1; q < population; q++) {
-                const uint32_t hq = rss_home(b, q, world);
-                msgs.push_back((k == RSS_ACCEPT || k == RSS_HB) ? M{hl, hq, b, q} : M{hq, hl, b, q});
+                const uint32_t hq = spread_home(b, q, world);
+                const bool down = k == RSS_ACCEPT || k == RSS_HB;             // leader -> follower, else follower -> leader
+                pmsg[k].push_back(SpreadMsg{down ? hl : hq, down ? hq : hl, (size_t)b * R + q, rss_msg_bytes(k, block_groups[b], sl), 0, 0});
             }
         }
-        std::vector<M> send, recv;
-        for (const M &m : msgs) {
-            if (m.src == rank) send.push_back(m);
-            if (m.dst == rank) recv.push_back(m);
-        }
-        std::stable_sort(send.begin(), send.end(), [](const M &x, const M &y) { return x.dst < y.dst; });
-        std::stable_sort(recv.begin(), recv.end(), [](const M &x, const M &y) { return x.src < y.src; });
-        for (const M &m : send) { const uint64_t n = rss_msg_bytes(k, block_groups[m.b], sl); psend[k].push_back({(size_t)m.b * R + m.q, p.n_send}); p.n_send += n; p.in_split[m.dst] += n; }
-        for (const M &m : recv) { const uint64_t n = rss_msg_bytes(k, block_groups[m.b], sl); precv[k].push_back({(size_t)m.b * R + m.q, p.n_recv}); p.n_recv += n; p.out_split[m.src] += n; }
-        poff[k] = Off{take(std::max<uint64_t>(p.n_send, 16)), take(std::max<uint64_t>(p.n_recv, 16)), 0};
+        spread_layout(pmsg[k], rank, world, p);
+        poff[k] = Off{take(std::max<uint64_t>(p.n_send, 16)), take(std::max<uint64_t>(p.n_recv, 16))};
     }
     struct RepOff { size_t mask, r_slot, cw, a_n, a_slot, a_val, a_ballot, st_ballot, live, st_flags, ones, hb_reply, hb_ballot, hb_c; };
     std::vector<RepOff> roff(s->reps.size());
@@ -195,14 +162,16 @@ int smr_rsp_spread_create(smr_rsp_replica *const *reps, const uint32_t *rep_bloc
         if (!here) continue;
         for (uint32_t r = 0; r < population; r++) pc_off[(size_t)b * R + r] = take(block_groups[b]) + 1;      // (+ 1: 0 = none)
     }
-    if (hipMalloc((void **)&s->arena, bytes + 256) != hipSuccess) { delete s; return fail(SMR_ERR_DEVICE, "rspaxos spread: hipMalloc failed"); }
-    hipError_t err = hipMemset(s->arena, 0, bytes + 256);
+    hipError_t err = ar.alloc_zeroed(&s->arena);
+    if (!s->arena) { delete s; return fail(SMR_ERR_DEVICE, "rspaxos spread: hipMalloc failed"); }
     for (int k = 0; k < 4; k++) {
         RssPlan &p = s->plans[k];
         p.sbuf = (uint8_t *)s->arena + poff[k].sbuf; p.rbuf = (uint8_t *)s->arena + poff[k].rbuf;
         p.sslot.assign((size_t)world * R, nullptr); p.rslot.assign((size_t)world * R, nullptr);
-        for (auto &x : psend[k]) p.sslot[x.first] = p.sbuf + x.second;
-        for (auto &x : precv[k]) p.rslot[x.first] = p.rbuf + x.second;
+        for (const SpreadMsg &m : pmsg[k]) {
+            if (m.src == rank) p.sslot[m.slot] = p.sbuf + m.soff;
+            if (m.dst == rank) p.rslot[m.slot] = p.rbuf + m.roff;
+        }
     }
     for (size_t i = 0; i < s->reps.size() && err == hipSuccess; i++) {
         RssRep &x = s->reps[i];
@@ -238,24 +207,10 @@ void smr_rsp_spread_destroy(smr_rsp_spread *s) {
 }
 
 int smr_rsp_spread_buffers(smr_rsp_spread *s, uint32_t exchange, void **send_dev, uint64_t *send_bytes, void **recv_dev, uint64_t *recv_bytes) {
-    if (!s || exchange >= 4 || !send_dev || !send_bytes || !recv_dev || !recv_bytes) return fail(SMR_ERR_ARG, "rspaxos spread: bad argument");
-    const RssPlan &p = s->plans[exchange];
-    *send_dev = p.sbuf; *recv_dev = p.rbuf;
-    for (uint32_t k = 0; k < s->world; k++) { send_bytes[k] = p.in_split[k]; recv_bytes[k] = p.out_split[k]; }
-    return SMR_OK;
+    return spread_buffers(s, "rspaxos spread", s && exchange < 4 ? &s->plans[exchange] : nullptr, send_dev, send_bytes, recv_dev, recv_bytes);
 }
 
-int smr_rsp_spread_bind_comm(smr_rsp_spread *s, smr_comm *comm) {
-    if (!s) return fail(SMR_ERR_ARG, "rspaxos spread: null argument");
-    if (comm) {
-        uint64_t info[5];
-        int rc = smr_comm_info(comm, info);
-        if (rc != SMR_OK) return rc;
-        if (info[0] != s->rank || info[1] != s->world) return fail(SMR_ERR_ARG, "rspaxos spread: the communicator's rank / world are not the job's");
-    }
-    s->comm = comm;
-    return SMR_OK;
-}
+int smr_rsp_spread_bind_comm(smr_rsp_spread *s, smr_comm *comm) { return spread_bind_comm(s, "rspaxos spread", comm); }
 
 // segment 0 .. 2 (5 on a heartbeat tick), see the file's header.  data_dev / val_dev: the led block's batches (u8 [G][data_len], rows
 // data_len apart) and their tokens (u32 [G], SMR_RSP_NULL: none) -- NULL on a rank that leads no block; lost_dev (may be NULL):
@@ -267,16 +222,16 @@ int smr_rsp_spread_segment(smr_rsp_spread *s, uint32_t seg, const uint8_t *data_
     if (!s) return fail(SMR_ERR_ARG, "rspaxos spread: null argument");
     const uint32_t last = heartbeat ? 5u : 2u;
     if (seg > last) return fail(SMR_ERR_ARG, "rspaxos spread: no such segment");
-    if (seg != s->next_seg) return fail(SMR_ERR_STATE, "rspaxos spread: segment " + std::to_string(seg) + " out of order (the open tick expects " + std::to_string(s->next_seg) + ")");
+    int rc = spread_in_order(s, "rspaxos spread", seg);
+    if (rc != SMR_OK) return rc;
     if (seg == 0) s->open_heartbeat = heartbeat ? 1 : 0;
     else if ((heartbeat ? 1 : 0) != s->open_heartbeat) return fail(SMR_ERR_STATE, "rspaxos spread: `heartbeat` differs from the one the tick's segment 0 was called with");
-    const int led = s->rep_of[(size_t)s->rank * s->R + 0] >= 0 && rss_home(s->rank, 0, s->world) == s->rank ? s->rep_of[(size_t)s->rank * s->R + 0] : -1;
+    const int led = s->rep_of[(size_t)s->rank * s->R + 0] >= 0 && spread_home(s->rank, 0, s->world) == s->rank ? s->rep_of[(size_t)s->rank * s->R + 0] : -1;
     if (led >= 0 && (!data_dev || !val_dev || !committed_dev)) return fail(SMR_ERR_ARG, "rspaxos spread: this rank leads a block: its batches, tokens and the committed array");
     s->next_seg = seg == last ? 0 : seg + 1;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t R = s->R;
     const uint64_t sl = s->sl;
-    int rc;
     s->ops.n = 0;
     auto lost = [&](uint32_t b, uint32_t k, uint32_t q) -> const uint8_t * { return lost_dev ? lost_dev[((size_t)b * 4 + k) * R + q] : nullptr; };
     if (seg == 0) {                                          // ---- the leader: encode + handle_req_batch + the Accepts
@@ -373,11 +328,7 @@ int smr_rsp_spread_segment(smr_rsp_spread *s, uint32_t seg, const uint8_t *data_
     return SMR_OK;
 }
 
-int smr_rsp_spread_abort_tick(smr_rsp_spread *s) {
-    if (!s) return fail(SMR_ERR_ARG, "rspaxos spread: null argument");
-    s->next_seg = 0;
-    return SMR_OK;
-}
+int smr_rsp_spread_abort_tick(smr_rsp_spread *s) { return spread_abort_tick(s, "rspaxos spread"); }
 
 // the whole tick: segments and exchanges back to back on `stream` (smr_rsp_spread_bind_comm first; a job of one rank needs none)
 int smr_rsp_spread_tick(smr_rsp_spread *s, const uint8_t *data_dev, const uint32_t *val_dev, const uint8_t *const *lost_dev, int heartbeat,

@@ -25,8 +25,9 @@ Two schedules:
     leader, leaders ascending -- 2 + 3 R exchanges per tick, the exact handler order of `ep_cluster.tick`, execution state
     included.
 """
-from . import shard
+from . import shard, spread_plan
 from .epaxos import EPaxosReplicaGroup
+from .spread_plan import home
 
 NONE = -1                                       # Option::None in a DepSet (0xFFFFFFFF as int32)
 # per-group bytes of a message's fields, widest first (R = population); s -> q kinds carry the instance, q -> s the answer
@@ -37,11 +38,6 @@ _KINDS = {
     "acc_reply": (("ballot", 8, 1), ("flags", 1, 1)),
     "commit": (("seq", 8, 1), ("deps", 4, "R"), ("col", 4, 1), ("flags", 1, 1), ("key", 1, 1)),
 }
-
-
-def home(block, replica, world):
-    """the rank replica `replica` of block `block` lives on"""
-    return (block + replica) % world
 
 
 class SpreadEPaxos:
@@ -83,7 +79,7 @@ class SpreadEPaxos:
     def _plan(self, kind, leaders):
         torch, W = self.torch, self.world
         to_acceptor = kind in ("pre_accept", "accept", "commit")
-        msgs = []                                              # (src rank, dst rank, block, from replica, to replica)
+        msgs = []                                              # (src rank, dst rank, (block, from replica, to replica))
         for b in range(W):
             lo, hi = self.range[b]
             if hi <= lo:
@@ -92,24 +88,11 @@ class SpreadEPaxos:
                 for q in range(self.R):
                     if q != s:
                         a, z = (s, q) if to_acceptor else (q, s)
-                        msgs.append((home(b, a, W), home(b, z, W), b, a, z))
-        send = sorted([m for m in msgs if m[0] == self.rank and m[1] != self.rank], key=lambda m: m[1])   # stable
-        recv = sorted([m for m in msgs if m[1] == self.rank and m[0] != self.rank], key=lambda m: m[0])
-        in_split, out_split, soff, roff = [0] * W, [0] * W, {}, {}
-        off = 0
-        for m in send:
-            soff[m[2:]] = off
-            off += self._msg_bytes(kind, m[2])
-            in_split[m[1]] += self._msg_bytes(kind, m[2])
-        n_send, off = off, 0
-        for m in recv:
-            roff[m[2:]] = off
-            off += self._msg_bytes(kind, m[2])
-            out_split[m[0]] += self._msg_bytes(kind, m[2])
-        return dict(kind=kind, send=[m[2:] for m in send], soff=soff, roff=roff, in_split=in_split, out_split=out_split, n_send=n_send, n_recv=off,
-                    sbuf=torch.zeros(max(n_send, 8), dtype=torch.uint8, device=self.device),
-                    rbuf=torch.zeros(max(off, 8), dtype=torch.uint8, device=self.device),
-                    pad={n: torch.zeros(n, dtype=torch.uint8, device=self.device) for n in range(1, 8)})
+                        if home(b, a, W) != home(b, z, W):     # (two replicas of one rank: handed over as it is, see _post)
+                            msgs.append((home(b, a, W), home(b, z, W), (b, a, z)))
+        plan = spread_plan.build(torch, msgs, lambda key: self._msg_bytes(kind, key[0]), self.rank, W, self.device, 8)
+        plan.update(kind=kind, send=list(plan["soff"]), pad={n: torch.zeros(n, dtype=torch.uint8, device=self.device) for n in range(1, 8)})
+        return plan
 
     # ---- one exchange -----------------------------------------------------------------------------------------------
     def _post(self, plan, out):
@@ -133,13 +116,7 @@ class SpreadEPaxos:
         self.bytes_sent += plan["n_send"]
 
     def _collective(self, plan):
-        import torch.distributed as dist
-        if self.world > 1:                                     # (the buffers are never empty tensors; the collective sees exactly the planned bytes)
-            if self.comm is not None:                          # the library's exchange (smr_comm_exchange: RCCL send / recv pairs)
-                self.comm.exchange(plan["sbuf"], plan["in_split"], plan["rbuf"], plan["out_split"])
-            else:
-                dist.all_to_all_single(plan["rbuf"][:plan["n_recv"]], plan["sbuf"][:plan["n_send"]], output_split_sizes=plan["out_split"],
-                                       input_split_sizes=plan["in_split"])
+        spread_plan.exchange(plan, self.world, self.comm)
 
     # ---- the tick inside the library (round 6: smr_ep_spread_*, csrc/ep_spread.hip) ---------------------------------------------
     def use_library_tick(self):
@@ -149,26 +126,21 @@ class SpreadEPaxos:
         import ctypes as C
         from . import _lib
         self._L = _lib.load()
-        order = sorted(self.reps)
-        self._lib_order = order
-        n = len(order)
-        arr = (C.c_void_p * max(n, 1))(*[self.reps[k]._h for k in order])
-        blocks = (C.c_uint32 * max(n, 1))(*[k[0] for k in order])
-        ids = (C.c_uint8 * max(n, 1))(*[k[1] for k in order])
-        groups = (C.c_uint32 * self.world)(*[self.range[b][1] - self.range[b][0] for b in range(self.world)])
+        self._lib_order, arr, blocks, ids, n, groups = spread_plan.replica_arrays(self.reps, self.range, self.world)
         h = C.c_void_p()
         _lib.check(self._L.smr_ep_spread_create(arr, blocks, ids, n, groups, self.world, self.rank, self.R, 1 if self.ordered else 0, C.byref(h)))
         self._lib_h = h
         assert self._L.smr_ep_spread_n_exchanges(h) == self.exchanges_per_tick()
         if self.comm is not None:
             _lib.check(self._L.smr_ep_spread_bind_comm(h, self.comm._h))
-        # the exchanges' buffers as tensors (for a host that moves them itself)
-        self._lib_bufs = []
+        # the exchanges' buffers as the dicts `_collective` takes: tensors over the library's memory (for a host that moves them itself)
+        self._lib_plans = []
         for k in range(self.exchanges_per_tick()):
-            sp, rp = C.c_void_p(), C.c_void_p()
-            sb, rb = (C.c_uint64 * self.world)(), (C.c_uint64 * self.world)()
-            _lib.check(self._L.smr_ep_spread_buffers(h, k, C.byref(sp), sb, C.byref(rp), rb))
-            self._lib_bufs.append(dict(send=sp.value, recv=rp.value, in_split=[int(x) for x in sb], out_split=[int(x) for x in rb]))
+            sp, rp, in_split, out_split = spread_plan.library_buffers(self._L.smr_ep_spread_buffers, h, k, self.world)
+            n_send, n_recv = sum(in_split), sum(out_split)
+            self._lib_plans.append(dict(kind=k, in_split=in_split, out_split=out_split, n_send=n_send, n_recv=n_recv,
+                                        sbuf=spread_plan.tensor_over(self.torch, sp, max(n_send, 8), self.device),
+                                        rbuf=spread_plan.tensor_over(self.torch, rp, max(n_recv, 8), self.device)))
         self._lib_outs = None
         return self
 
@@ -214,17 +186,8 @@ class SpreadEPaxos:
         for seg in range(nx + 1):
             _lib.check(self._L.smr_ep_spread_segment(self._lib_h, seg, kp, dp, outs, _lib.stream_ptr(None)))
             if seg < nx:
-                yield self._lib_plan(seg)
+                yield self._lib_plans[seg]
         self._lib_results()
-
-    def _lib_plan(self, k):
-        """exchange k's buffers as the dict `_collective` takes (tensors over the library's memory)"""
-        b = self._lib_bufs[k]
-        if "sbuf" not in b:
-            n_send, n_recv = sum(b["in_split"]), sum(b["out_split"])
-            b.update(kind=k, n_send=n_send, n_recv=n_recv, sbuf=_tensor_over(self.torch, b["send"], max(n_send, 8), self.device),
-                     rbuf=_tensor_over(self.torch, b["recv"], max(n_recv, 8), self.device))
-        return b
 
     def close_library_tick(self):
         if getattr(self, "_lib_h", None):
@@ -235,8 +198,7 @@ class SpreadEPaxos:
         """every exchange of the tick through the library: `comm` (summerset_amd.comm.Comm, this rank's end of the job's
         communicator) -> `smr_comm_exchange` on the plans' own send / receive buffers with their static split sizes, on the
         stream the handlers' kernels run on.  None: back to torch.distributed.all_to_all_single (gloo jobs)."""
-        if comm is not None and (comm.world != self.world or comm.rank != self.rank):
-            raise ValueError("the communicator is rank %d of %d, the job's rank is %d of %d" % (comm.rank, comm.world, self.rank, self.world))
+        spread_plan.check_comm(comm, self.rank, self.world)
         self.comm = comm
         if getattr(self, "_lib_h", None):
             from . import _lib
@@ -378,19 +340,6 @@ class SpreadEPaxos:
         return sum(o["committed"].sum() for o in out.values())
 
 
-def _tensor_over(torch, ptr, nbytes, device):
-    """a uint8 tensor over `nbytes` of device (or, on the emulator, host) memory the library owns"""
-    import ctypes as C
-    import numpy as np
-    if str(device).startswith("cuda"):
-        class _Mem:                                          # __cuda_array_interface__: torch.as_tensor wraps device memory without a copy
-            pass
-        m = _Mem()
-        m.__cuda_array_interface__ = dict(shape=(int(nbytes),), typestr="|u1", data=(int(ptr), False), version=2)
-        return torch.as_tensor(m, device=device)
-    return torch.from_numpy(np.ctypeslib.as_array((C.c_uint8 * int(nbytes)).from_address(int(ptr))))
-
-
 class in_process:
     """All `world` ranks of a spread EPaxos job inside one process (one device, or the emulator): the same objects,
     plans and buffers as the multi-process job; only the collective is a copy.  Every rank runs a stage before any rank
@@ -411,16 +360,8 @@ class in_process:
                     pass
             if not plans:
                 break
-            assert len(plans) == len(self.ranks)
-            for s_, p in enumerate(plans):
-                so = 0
-                for d, n in enumerate(p["in_split"]):
-                    q = plans[d]
-                    ro = sum(q["out_split"][:s_])
-                    assert q["out_split"][s_] == n and q["kind"] == p["kind"]
-                    if n:
-                        q["rbuf"][ro:ro + n].copy_(p["sbuf"][so:so + n])
-                    so += n
+            assert len(plans) == len(self.ranks) and len({p["kind"] for p in plans}) == 1
+            spread_plan.copy_between(plans)
         out = {}
         for r in self.ranks:
             out.update(r.out)

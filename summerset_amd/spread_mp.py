@@ -17,27 +17,12 @@ exchanges per tick (two without a heartbeat round), each a single collective.
 Results are bit for bit the co-located engine's (tests/test_spread_mp_gloo.py: world_size 2 over gloo with the
 emulator build of the engine on every rank, against the single-process run, every tick).  Group freezes (`overflow`,
 a harness guard) are per rank here: a run that overflows a ring is outside what the two layouts agree on."""
-import numpy as np
-
-from . import _lib, shard
+from . import _lib, shard, spread_plan
 from ._lib import MpImageOp, check, stream_ptr
 from .multipaxos import MultiPaxosCluster
+from .spread_plan import home
 
 OUTBOX, ACKS, PREPARE_REPLIES, HEARTBEAT = 0, 1, 2, 3
-
-
-def home(block, replica, world):
-    """the rank replica `replica` of block `block` lives on"""
-    return (block + replica) % world
-
-
-class _Msg:
-    __slots__ = ("src", "dst", "block", "kind", "rep", "other", "size", "soff", "roff", "dup_of")
-
-    def __init__(self, src, dst, block, kind, rep, other=0):
-        self.src, self.dst, self.block, self.kind, self.rep, self.other = src, dst, block, kind, rep, other
-        self.size = self.soff = self.roff = 0
-        self.dup_of = None
 
 
 class SpreadMultiPaxos:
@@ -78,69 +63,52 @@ class SpreadMultiPaxos:
         return sorted({home(b, r, self.world) for r in range(self.R)})
 
     def _messages(self, phase):
+        """the exchange's messages in canonical order, as spread_plan.build takes them; a message's key is (src rank, dst rank, block,
+        kind, replica, other)"""
         out = []
+        add = lambda src, dst, *piece: out.append((src, dst, (src, dst) + piece))   # noqa: E731
         for b in range(self.world):
             lo, hi = self.n_groups[b]
             if hi <= lo:
                 continue
             for r in range(self.R):
                 hr = home(b, r, self.world)
-                if phase in ("outbox", "heartbeat"):           # a replica's piece goes to every other rank that holds the block
-                    out += [_Msg(hr, d, b, OUTBOX if phase == "outbox" else HEARTBEAT, r) for d in self._ranks_of(b) if d != hr]
-                else:
-                    out += [_Msg(hr, d, b, PREPARE_REPLIES, r) for d in self._ranks_of(b) if d != hr]
+                for d in self._ranks_of(b):                    # a replica's piece goes to every other rank that holds the block
+                    if d != hr:
+                        add(hr, d, b, {"outbox": OUTBOX, "replies": PREPARE_REPLIES, "heartbeat": HEARTBEAT}[phase], r, 0)
+                if phase == "replies":
                     for q in range(self.R):                    # follower q's answers to sender r travel to r's rank
                         hq = home(b, q, self.world)
                         if q != r and hq != hr:
-                            out.append(_Msg(hq, hr, b, ACKS, r, q))
+                            add(hq, hr, b, ACKS, r, q)
         return out
 
     def _img_bytes(self, b, kind):
-        lo, hi = self.n_groups[b]
-        cl = self.blocks[b][0] if b in self.blocks else None
-        if cl is not None:
-            return int(self._L.smr_mp_image_bytes(cl._h, kind, self.S, self.ovf_cap))
-        # a block this rank holds no replica of never appears in its messages
-        raise AssertionError("image size of a block this rank takes no part in")
+        if b not in self.blocks:                               # a block this rank holds no replica of never appears in its messages
+            raise AssertionError("image size of a block this rank takes no part in")
+        return int(self._L.smr_mp_image_bytes(self.blocks[b][0]._h, kind, self.S, self.ovf_cap))
 
     def _plan(self, phase):
-        torch = self.torch
-        msgs = self._messages(phase)
-        send = sorted([m for m in msgs if m.src == self.rank], key=lambda m: m.dst)       # stable: canonical order per dst
-        recv = sorted([m for m in msgs if m.dst == self.rank], key=lambda m: m.src)
-        in_split, out_split = [0] * self.world, [0] * self.world
-        off, first = 0, {}
-        for m in send:
-            m.size, m.soff = self._img_bytes(m.block, m.kind), off
-            key = (m.block, m.kind, m.rep, m.other)
-            m.dup_of = first.get(key)                          # the same piece for another rank: packed once, copied
-            first.setdefault(key, m)
-            off += m.size
-            in_split[m.dst] += m.size
-        n_send = off
-        off = 0
-        for m in recv:
-            m.size, m.roff = self._img_bytes(m.block, m.kind), off
-            off += m.size
-            out_split[m.src] += m.size
-        plan = dict(send=send, recv=recv, in_split=in_split, out_split=out_split,
-                    sbuf=torch.zeros(max(n_send, 16), dtype=torch.uint8, device=self.device),
-                    rbuf=torch.zeros(max(off, 16), dtype=torch.uint8, device=self.device))
+        plan = spread_plan.build(self.torch, self._messages(phase), lambda key: self._img_bytes(key[2], key[3]), self.rank, self.world, self.device, 16)
+        first, plan["dup_of"] = {}, {}                         # send key -> the offset of the same piece for another rank: packed once, copied
+        for key, off in plan["soff"].items():
+            plan["dup_of"][key] = first.get(key[2:])
+            first.setdefault(key[2:], off)
         # the exchange's operations never change: handed to the library once (smr_mp_image_plan_create), an exchange is
         # then 3 launches to pack (clear headers, pack, duplicate) + 1 to unpack instead of one or two per image
-        plan["pack"] = self._make_plan(send, plan["sbuf"].data_ptr(), True)
-        plan["unpack"] = self._make_plan(recv, plan["rbuf"].data_ptr(), False)
+        plan["pack"] = self._make_plan(plan["soff"], plan["sbuf"].data_ptr(), plan["dup_of"])
+        plan["unpack"] = self._make_plan(plan["roff"], plan["rbuf"].data_ptr(), {})
         return plan
 
-    def _make_plan(self, msgs, base, sending):
+    def _make_plan(self, offs, base, dup_of):
         import ctypes as C
-        ops = (MpImageOp * max(len(msgs), 1))()
-        for o, m in zip(ops, msgs):
-            o.cluster, o.kind, o.rep, o.other = self.blocks[m.block][0]._h, m.kind, m.rep, m.other
-            o.img_dev, o.img_bytes = base + (m.soff if sending else m.roff), m.size
-            o.copy_of_dev = (base + m.dup_of.soff) if (sending and m.dup_of is not None) else None
+        ops = (MpImageOp * max(len(offs), 1))()
+        for o, (key, off) in zip(ops, offs.items()):
+            _, _, b, o.kind, o.rep, o.other = key
+            o.cluster, o.img_dev, o.img_bytes = self.blocks[b][0]._h, base + off, self._img_bytes(b, o.kind)
+            o.copy_of_dev = None if dup_of.get(key) is None else base + dup_of[key]
         h = C.c_void_p()
-        check(self._L.smr_mp_image_plan_create(ops, len(msgs), self.S, self.ovf_cap, C.byref(h)))
+        check(self._L.smr_mp_image_plan_create(ops, len(offs), self.S, self.ovf_cap, C.byref(h)))
         return h
 
     def close(self):
@@ -166,16 +134,12 @@ class SpreadMultiPaxos:
 
     def _collective(self, phase):
         """the exchange itself: ONE all_to_all_single over the plan's send / receive buffers (RCCL over xGMI)"""
-        import torch.distributed as dist
         p = self._plans[phase]
-        self.bytes_sent += sum(p["in_split"])
-        if self.world > 1:
-            if self.peers is not None:                         # all ranks of the job in THIS process (tests, one device)
-                _copy_between(self.peers, phase)
-            else:
-                # (the buffers are padded to a minimum size: the collective sees exactly the planned bytes)
-                dist.all_to_all_single(p["rbuf"][:sum(p["out_split"])], p["sbuf"][:sum(p["in_split"])], output_split_sizes=p["out_split"],
-                                       input_split_sizes=p["in_split"])
+        self.bytes_sent += p["n_send"]
+        if self.world > 1 and self.peers is not None:          # all ranks of the job in THIS process (tests, one device)
+            _copy_between(self.peers, phase)
+        else:
+            spread_plan.exchange(p, self.world)
 
     def bind_comm(self, comm):
         """the collectives into the library: `comm` (summerset_amd.comm.Comm, one per rank of the job) and the three exchanges'
@@ -241,7 +205,7 @@ class SpreadMultiPaxos:
         arr = self._inputs(inputs)
         if self.comm is not None:                              # the exchanges are the library's: the whole tick is one call
             check(self._L.smr_mp_spread_tick(self._spread, arr, int(bool(heartbeat)), stream_ptr(stream)))
-            self.bytes_sent += sum(sum(self._plans[p]["in_split"]) for p in (("outbox", "replies", "heartbeat") if heartbeat else ("outbox", "replies")))
+            self.bytes_sent += sum(self._plans[p]["n_send"] for p in (("outbox", "replies", "heartbeat") if heartbeat else ("outbox", "replies")))
             return
         self.segment(0, arr, heartbeat, stream)
         self._collective("outbox")
@@ -282,40 +246,27 @@ class SpreadMultiPaxos:
         """overflow-list entries lost because an image's list ran full (must be 0: size ovf_cap for the workload)"""
         n = 0
         for p in self._plans.values():
-            for m, buf in [(m, p["sbuf"]) for m in p["send"]] + [(m, p["rbuf"]) for m in p["recv"]]:
-                off = m.soff if buf is p["sbuf"] else m.roff
-                n += int(buf[off:off + 16].view(self.torch.int32)[2].item())
+            for buf, offs in ((p["sbuf"], p["soff"]), (p["rbuf"], p["roff"])):
+                for off in offs.values():
+                    n += int(buf[off:off + 16].view(self.torch.int32)[2].item())
         return n
 
 
 def _copy_between(peers, phase):
-    """the all-to-all of a job whose ranks all live in this process: rank s's segment for d -> d's segment from s.  Runs
-    once per exchange, when the LAST rank arrives (the ranks are stepped one after the other, see in_process).  The segment
-    pairs of an exchange never change: their views are made once, and an exchange is ONE multi-tensor copy (round 5: twelve
-    `copy_` calls at ~10 us of host time each were a tenth of a virtual-rank tick)."""
-    peers[0]._arrived[phase] = peers[0]._arrived.get(phase, 0) + 1
-    if peers[0]._arrived[phase] < len(peers):
+    """the all-to-all of a job whose ranks all live in this process (spread_plan.segment_pairs).  Runs once per exchange, when the
+    LAST rank arrives (the ranks are stepped one after the other, see in_process).  The segment pairs of an exchange never
+    change: their views are made once, and an exchange is ONE multi-tensor copy (twelve `copy_` calls at ~10 us of
+    host time each were a tenth of a virtual-rank tick)."""
+    first = peers[0]
+    first._arrived[phase] = first._arrived.get(phase, 0) + 1
+    if first._arrived[phase] < len(peers):
         return
-    peers[0]._arrived[phase] = 0
-    pairs = peers[0]._pairs.get(phase) if hasattr(peers[0], "_pairs") else None
+    first._arrived[phase] = 0
+    pairs = first._pairs.get(phase)
     if pairs is None:
-        dsts, srcs = [], []
-        for s_, ps in enumerate(peers):
-            p = ps._plans[phase]
-            so = 0
-            for d, n in enumerate(p["in_split"]):
-                q = peers[d]._plans[phase]
-                ro = sum(q["out_split"][:s_])
-                assert q["out_split"][s_] == n
-                if n:
-                    dsts.append(q["rbuf"][ro:ro + n]); srcs.append(p["sbuf"][so:so + n])
-                so += n
-        pairs = (dsts, srcs)
-        if not hasattr(peers[0], "_pairs"):
-            peers[0]._pairs = {}
-        peers[0]._pairs[phase] = pairs
+        pairs = first._pairs[phase] = spread_plan.segment_pairs([r._plans[phase] for r in peers])
     if pairs[0]:
-        peers[0].torch._foreach_copy_(pairs[0], pairs[1])
+        first.torch._foreach_copy_(pairs[0], pairs[1])
 
 
 class in_process:
@@ -325,7 +276,7 @@ class in_process:
 
     def __init__(self, total_groups, population, window, world, device, slots_per_tick, **kw):
         self.ranks = [SpreadMultiPaxos(total_groups, population, window, r, world, device, slots_per_tick, **kw) for r in range(world)]
-        self.ranks[0]._arrived = {}
+        self.ranks[0]._arrived, self.ranks[0]._pairs = {}, {}
         for r in self.ranks:
             r.peers = self.ranks
         # on a device every virtual rank gets a stream of its own: ranks are processes on GPUs of their own in the real job, so
@@ -368,7 +319,7 @@ class in_process:
 
         def collective(phase):
             for r in rs:
-                r.bytes_sent += sum(r._plans[phase]["in_split"])
+                r.bytes_sent += r._plans[phase]["n_send"]
             if sts is not None:                                # the collective: every rank has packed; the copies; every rank goes on
                 for st in sts:
                     main.wait_stream(st)

@@ -19,18 +19,13 @@ Per tick, per rank:
   on a heartbeat tick two more exchanges: the leader's Heartbeat out, the followers' Heartbeats back.
 Results are bit for bit the co-located loop's (tests/test_spread_rsp_gloo.py: world_size 2 over gloo with the emulator
 build of the engine, against `rsp_cluster.SteadyLoop` in one process; tests/test_spread_rsp.py: every rank in one process)."""
-import numpy as np
-
-from . import shard
+from . import shard, spread_plan
 from .rscoding import RSCodewordBatch, rs_shard_len
 from .rspaxos import RSPaxosReplicaGroup
+from .spread_plan import home
 
 NULL = 0xFFFFFFFF
 _A16 = lambda n: (n + 15) // 16 * 16   # noqa: E731
-
-
-def home(block, replica, world):
-    return (block + replica) % world
 
 
 class SpreadRSPaxos:
@@ -87,8 +82,7 @@ class SpreadRSPaxos:
         return _A16(G * 21)                                     # hb_back: the same + reply u8
 
     def _plan(self, kind):
-        torch = self.torch
-        msgs = []                                               # (src, dst, block, follower)
+        msgs = []                                               # (src rank, dst rank, (block, follower)); a rank's messages to itself too
         for b in range(self.world):
             lo, hi = self.n_groups[b]
             if hi <= lo:
@@ -98,39 +92,16 @@ class SpreadRSPaxos:
                 if q == self.LEADER:
                     continue
                 hq = home(b, q, self.world)
-                msgs.append((hl, hq, b, q) if kind in ("accept", "hb") else (hq, hl, b, q))
-        send = sorted([m for m in msgs if m[0] == self.rank], key=lambda m: m[1])       # stable: canonical order per destination
-        recv = sorted([m for m in msgs if m[1] == self.rank], key=lambda m: m[0])
-        in_split, out_split = [0] * self.world, [0] * self.world
-        soff, roff, o = {}, {}, 0
-        for m in send:
-            soff[(m[2], m[3])] = o
-            n = self._msg_bytes(kind, m[2])
-            o += n
-            in_split[m[1]] += n
-        n_send, o = o, 0
-        for m in recv:
-            roff[(m[2], m[3])] = o
-            n = self._msg_bytes(kind, m[2])
-            o += n
-            out_split[m[0]] += n
-        return dict(soff=soff, roff=roff, in_split=in_split, out_split=out_split,
-                    sbuf=torch.zeros(max(n_send, 16), dtype=torch.uint8, device=self.device),
-                    rbuf=torch.zeros(max(o, 16), dtype=torch.uint8, device=self.device))
+                msgs.append((hl, hq, (b, q)) if kind in ("accept", "hb") else (hq, hl, (b, q)))
+        return spread_plan.build(self.torch, msgs, lambda key: self._msg_bytes(kind, key[0]), self.rank, self.world, self.device, 16)
 
     def _collective(self, kind):
-        import torch.distributed as dist
         p = self._plans[kind]
-        self.bytes_sent += sum(p["in_split"])
+        self.bytes_sent += p["n_send"]
         if self.exchange is not None:
             self.exchange(kind, self)
-        elif self.world > 1 and self.comm is not None:          # the library's exchange (smr_comm_exchange: RCCL send / recv pairs)
-            self.comm.exchange(p["sbuf"], p["in_split"], p["rbuf"], p["out_split"])
-        elif self.world > 1:
-            dist.all_to_all_single(p["rbuf"][:sum(p["out_split"])], p["sbuf"][:sum(p["in_split"])], output_split_sizes=p["out_split"],
-                                   input_split_sizes=p["in_split"])
         else:
-            p["rbuf"][:sum(p["out_split"])].copy_(p["sbuf"][:sum(p["in_split"])])
+            spread_plan.exchange(p, self.world, self.comm)
 
     # ---- the tick inside the library (round 6: smr_rsp_spread_*, csrc/rsp_spread.hip) --------------------------------------------
     def use_library_tick(self):
@@ -140,27 +111,17 @@ class SpreadRSPaxos:
         stays where it was).  Not with payload stores (those stay this module's)."""
         import ctypes as C
         from . import _lib
-        from .spread_ep import _tensor_over
         if self.stores:
             raise ValueError("the library tick carries the shards in the exchange's buffers: payload=False")
         self._L = _lib.load()
-        order = sorted(self.reps)
-        n = len(order)
-        arr = (C.c_void_p * max(n, 1))(*[self.reps[k]._h for k in order])
-        blocks = (C.c_uint32 * max(n, 1))(*[k[0] for k in order])
-        ids = (C.c_uint8 * max(n, 1))(*[k[1] for k in order])
-        groups = (C.c_uint32 * self.world)(*[self.n_groups[b][1] - self.n_groups[b][0] for b in range(self.world)])
+        _, arr, blocks, ids, n, groups = spread_plan.replica_arrays(self.reps, self.n_groups, self.world)
         h = C.c_void_p()
         _lib.check(self._L.smr_rsp_spread_create(arr, blocks, ids, n, groups, self.world, self.rank, self.R, self.W, self.L, C.byref(h)))
         self._lib_h = h
-        for k, kind in enumerate(("accept", "accept_reply", "hb", "hb_back")):
-            sp, rp = C.c_void_p(), C.c_void_p()
-            sb, rb = (C.c_uint64 * self.world)(), (C.c_uint64 * self.world)()
-            _lib.check(self._L.smr_rsp_spread_buffers(h, k, C.byref(sp), sb, C.byref(rp), rb))
-            p = self._plans[kind]
-            assert [int(x) for x in sb] == p["in_split"] and [int(x) for x in rb] == p["out_split"], kind
-            p["sbuf"] = _tensor_over(self.torch, sp.value, max(sum(p["in_split"]), 16), self.device)
-            p["rbuf"] = _tensor_over(self.torch, rp.value, max(sum(p["out_split"]), 16), self.device)
+        for k, p in enumerate(self._plans.values()):             # (the library's plan has the same split sizes: tests/test_spread_plan_digests.py)
+            sp, rp, _, _ = spread_plan.library_buffers(self._L.smr_rsp_spread_buffers, h, k, self.world)
+            p["sbuf"] = spread_plan.tensor_over(self.torch, sp, max(p["n_send"], 16), self.device)
+            p["rbuf"] = spread_plan.tensor_over(self.torch, rp, max(p["n_recv"], 16), self.device)
         if self.comm is not None:
             _lib.check(self._L.smr_rsp_spread_bind_comm(h, self.comm._h))
         self._lib_committed = {b: self.torch.zeros(self.n_groups[b][1] - self.n_groups[b][0], dtype=self.torch.uint8, device=self.device) for b in self.lead}
@@ -204,8 +165,7 @@ class SpreadRSPaxos:
         """every exchange of the tick (Accepts + shards out, AcceptReplies back, the two heartbeat legs) through the library:
         `comm` (summerset_amd.comm.Comm) -> `smr_comm_exchange` on the plans' own buffers with their static split sizes.
         None: back to torch.distributed.all_to_all_single (gloo jobs)."""
-        if comm is not None and (comm.world != self.world or comm.rank != self.rank):
-            raise ValueError("the communicator is rank %d of %d, the job's rank is %d of %d" % (comm.rank, comm.world, self.rank, self.world))
+        spread_plan.check_comm(comm, self.rank, self.world)
         self.comm = comm
         if getattr(self, "_lib_h", None):
             from . import _lib
@@ -418,7 +378,7 @@ class SpreadRSPaxos:
             self._lib_args(data, val, lost, heartbeat)
             d, v, tab, hb, c = self._lib_call
             _lib.check(self._L.smr_rsp_spread_tick(self._lib_h, d, v, tab, hb, c, _lib.stream_ptr(None)))
-            self.bytes_sent += sum(sum(self._plans[k]["in_split"]) for k in (("accept", "accept_reply", "hb", "hb_back") if heartbeat else ("accept", "accept_reply")))
+            self.bytes_sent += sum(self._plans[k]["n_send"] for k in (("accept", "accept_reply", "hb", "hb_back") if heartbeat else ("accept", "accept_reply")))
             return {b: self._lib_committed[b] for b in self.lead}
         self.phase_a(data, val, lost, heartbeat)
         self._collective("accept")
@@ -437,19 +397,6 @@ class SpreadRSPaxos:
         return sum(int(self.reps[(b, self.LEADER)].dump()["counters"][0]) for b in self.lead)
 
 
-def _copy_between(ranks, kind):
-    """the all-to-all of a job whose ranks all live in this process"""
-    for s_, ps in enumerate(ranks):
-        p = ps._plans[kind]
-        so = 0
-        for d, n in enumerate(p["in_split"]):
-            q = ranks[d]._plans[kind]
-            ro = sum(q["out_split"][:s_])
-            assert q["out_split"][s_] == n
-            q["rbuf"][ro:ro + n].copy_(p["sbuf"][so:so + n])
-            so += n
-
-
 class in_process:
     """every rank of the job inside one process (one device, or the emulator): same objects, plans and buffers, the collective a
     copy; every rank finishes a phase before any rank starts the next"""
@@ -463,8 +410,8 @@ class in_process:
 
         def coll(kind):
             for r in rs:
-                r.bytes_sent += sum(r._plans[kind]["in_split"])
-            _copy_between(rs, kind)
+                r.bytes_sent += r._plans[kind]["n_send"]
+            spread_plan.copy_between([r._plans[kind] for r in rs])
         for r in rs:
             r.phase_a(data, val, lost, heartbeat)
         coll("accept")
