@@ -453,6 +453,39 @@ int smr_mp_snapshot_info_get(const smr_mp_snapshot *s, smr_mp_snapshot_info *out
 int64_t smr_mp_snapshot_export(const smr_mp_snapshot *s, uint8_t *host, uint64_t cap);
 int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len);
 
+/* ---- chosen groups between clusters, on the device -------------------------------------------------------------------------
+ * A group is one lane and talks to no other group, so its state travels on its own: a job that block-partitions independent
+ * groups over ranks (layout L1) rebalances a hot rank, drains a device, splits a cluster or admits a new group into a slot
+ * another has left without saving and loading whole clusters.  No new format: an image of "these n groups, in this order" is
+ * the version-1 image of an n-group cluster, group i of the image being group groups_host[i] of the cluster.
+ *   smr_mp_snapshot_create_groups  a snapshot object for n groups of a cluster like `like`: its population, commit_extra and
+ *                            live mask, worst-case room for its window and outbox_cap (and growing by host-known sizes as
+ *                            above).  info, export and import work on it unchanged; import checks against n_groups = n;
+ *   smr_mp_save_groups       one kernel on `stream`; enqueues only, apart from handing the list to the device (an async copy
+ *                            on `stream` into a buffer the snapshot owns).  Scalars, overflow flag, live slots and pending
+ *                            next-tick outbox entries of the listed groups, exactly as smr_mp_save_state writes them, the
+ *                            record order taken over list positions (tile = 64 list entries).  The cluster is not modified;
+ *   smr_mp_load_groups       the inverse: group i of an n-group image overwrites the whole logical state of group
+ *                            groups_host[i], for the live replicas; nothing of any other group changes.  The image may come
+ *                            from smr_mp_save_groups or be an ordinary smr_mp_save_state image of an n-group cluster.
+ *                            Synchronises once per save to read the image's header;
+ *   smr_mp_reset_groups      the listed groups back to exactly what smr_mp_cluster_create leaves for a group: no leader, empty
+ *                            log, flags clear.
+ * What does not travel: the counters and the unpolled commit list.  They are the cluster's reporting, not a group's state:
+ * events stay counted where they happened, so the sum over clusters is conserved, and a moved group's unpolled entries stay on
+ * the source's list under the source's group id -- poll the source before the slot is reused.  A group image holds zero
+ * counters and n_commits = 0; smr_mp_load_groups ignores an image's counters, refuses one with n_commits != 0, and leaves the
+ * target's counters, commit list, straggler list and role rotation alone.  Which job group sits in which slot is the host's
+ * table.
+ * The list is a host array (a move is a rare host decision), checked before anything is launched: n in 1 .. n_groups, every
+ * id below n_groups, none twice; for save and load n is the snapshot's n_groups.  SMR_ERR_ARG for these, for a null argument,
+ * another population / commit_extra / live mask, a log or outbox that does not fit the target's window / outbox_cap;
+ * SMR_ERR_STATE inside an open tick and for an empty snapshot.  A refused call leaves cluster and snapshot untouched. */
+int smr_mp_snapshot_create_groups(const smr_mp_cluster *like, uint32_t n, smr_mp_snapshot **out);
+int smr_mp_save_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, smr_mp_snapshot *s, void *stream);
+int smr_mp_load_groups(smr_mp_cluster *c, const smr_mp_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_mp_reset_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, void *stream);
+
 /* counters of replica `rep`: [0] leader-side commits (Accepting->Committed,
  * messages.rs:412-433), [1] redirected batches (request.rs:128-154),
  * [2] batches refused by ring back-pressure */

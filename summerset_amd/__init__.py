@@ -9,7 +9,7 @@ include/summerset_hip.h; PyTorch only provides device buffers and streams.
 """
 from ._lib import SummersetError, SMR_CTL_IDENTITY, SMR_NO_REPLICA  # noqa: F401
 from .rscoding import RSCodewordBatch, rs_matrix, rs_shard_len  # noqa: F401
-from .multipaxos import MpSnapshot, MultiPaxosCluster  # noqa: F401
+from .multipaxos import MpSnapshot, MultiPaxosCluster, move_groups  # noqa: F401
 from .quorumread import KvStateMachine, QuorumReadGroup, StringKvStateMachine  # noqa: F401
 from .raft import CRaftLeaderGroup, RaftLeaderGroup, RaftSnapshot, load_cluster_state, save_cluster_state  # noqa: F401
 from .epaxos import EPaxosReplicaGroup, EPaxosSnapshot  # noqa: F401

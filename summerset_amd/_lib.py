@@ -294,6 +294,10 @@ SYMBOLS = [
     ("smr_mp_snapshot_info_get", _i, [_vp, C.POINTER(MpSnapshotInfo)]),
     ("smr_mp_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
     ("smr_mp_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_mp_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_mp_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_mp_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_mp_reset_groups", _i, [_vp, _vp, _u32, _vp]),
     ("smr_mp_profile_enable", _i, [_vp, _i]),
     ("smr_mp_profile_read", _i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("smr_raft_leader_create", _i, [C.POINTER(RaftCfg), C.POINTER(_vp)]),

@@ -2131,6 +2131,10 @@ __global__ __launch_bounds__(256) void mp_round_heartbeat_multi(const MpMulti M)
 
 using namespace smr;
 
+// a list of groups on the device (smr_mp_save_groups / _load_groups / _reset_groups): owned by the snapshot object the call
+// works on (reset: by the cluster), made once and grown only when a longer list comes
+struct GroupListBuf { uint32_t *dev = nullptr; uint32_t cap = 0; };
+
 struct smr_mp_cluster {
     smr_mp_cfg cfg;
     MpParams hp;            // host copy (device pointers inside)
@@ -2161,6 +2165,7 @@ struct smr_mp_cluster {
     const uint32_t *rest_ackctl = nullptr;
     uint32_t lead_hint = 0;          // the replica most groups are led by (smr_mp_preset_leader): the tally's speculative loads
     bool spread_open = false;        // a smr_mp_spread tick is open on this block (between its segment 0 and its end / abort): no save, no load
+    GroupListBuf glist;              // smr_mp_reset_groups' list
     bool profile = false;
     std::vector<ProfEv> evs;
     double prof_ms[5] = {0, 0, 0, 0, 0};
@@ -2340,8 +2345,8 @@ int smr_mp_cluster_create(const smr_mp_cfg *cfg, smr_mp_cluster **out) {
         delete c;
         return fail(SMR_ERR_DEVICE, "mp: replica arrays are not equally spaced in the arena");
     }
-    e = hipMemset(c->arena.base, 0, c->arena.size);
-    for (uint32_t r = 0; e == hipSuccess && r < P.R; r++) e = hipMemset(P.rep[r].leader, 0xFF, P.G);
+    e = hipMemset(c->arena.base, (int)(MP_INIT_WORD & 0xFFu), c->arena.size);          // a group's initial state: mp_types.h
+    for (uint32_t r = 0; e == hipSuccess && r < P.R; r++) e = hipMemset(P.rep[r].leader, (int)MP_INIT_LEADER, P.G);
     if (e == hipSuccess) e = hipMalloc((void **)&c->dp, sizeof(MpParams));
     if (e == hipSuccess) e = hipMemcpy(c->dp, &c->hp, sizeof(MpParams), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -2376,6 +2381,7 @@ void smr_mp_cluster_destroy(smr_mp_cluster *c) {
     if (c->side) (void)hipStreamDestroy(c->side);
     for (auto &e : c->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     if (c->dp) (void)hipFree(c->dp);
+    if (c->glist.dev) (void)hipFree(c->glist.dev);
     if (c->arena.base) (void)hipFree(c->arena.base);
     delete c;
 }
@@ -3263,6 +3269,7 @@ struct smr_mp_snapshot {
     uint64_t cap_slots = 0, cap_ob = 0, cap_cl = 0;              // records the device buffer's three sections have room for
     SnapHdr hdr;                                                 // the image's header, once buf.hdr_known
     uint32_t lead_hint = 0;                                      // (scheduling only: not part of the image)
+    GroupListBuf glist;                                          // smr_mp_save_groups / smr_mp_load_groups: the list on the device
 };
 
 static const char *const MPSNAP = "mp snapshot: ";
@@ -3303,20 +3310,26 @@ static bool snap_like(const smr_mp_snapshot *s, const smr_mp_cluster *c) {
     return s->G == c->cfg.n_groups && s->R == c->cfg.population && s->commit_extra == c->cfg.commit_extra && s->live == (uint8_t)c->hp.live;
 }
 
-int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+// a snapshot object for n groups of a cluster like `like` (n = its n_groups: the whole cluster)
+static int snap_create(const smr_mp_cluster *like, uint32_t n, smr_mp_snapshot **out) {
     if (like->hp.live == 0) return fail(SMR_ERR_ARG, "mp snapshot: the cluster has no live replica");
     smr_mp_snapshot *s = new smr_mp_snapshot();
-    s->G = like->cfg.n_groups; s->R = like->cfg.population; s->commit_extra = like->cfg.commit_extra; s->live = (uint8_t)like->hp.live;
+    s->G = n; s->R = like->cfg.population; s->commit_extra = like->cfg.commit_extra; s->live = (uint8_t)like->hp.live;
     memset(&s->hdr, 0, sizeof(s->hdr));
     if (int rc = snap_room(s, like)) { delete s; return rc; }
     *out = s;
     return SMR_OK;
 }
 
+int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
+    return snap_create(like, like->cfg.n_groups, out);
+}
+
 void smr_mp_snapshot_destroy(smr_mp_snapshot *s) {
     if (!s) return;
     snap_buf_free(s->buf);
+    if (s->glist.dev) (void)hipFree(s->glist.dev);               // (snap_buf_free has synchronised)
     delete s;
 }
 
@@ -3361,6 +3374,120 @@ int smr_mp_load_state(smr_mp_cluster *c, const smr_mp_snapshot *cs, void *stream
     c->lead_hint = s->lead_hint < c->cfg.population ? s->lead_hint : 0u;
     const SnapImg S = snap_img(s);
     hipLaunchKernelGGL(mp_snap_unpack, dim3(S.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, c->dp, c->par, S);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+/* ---- chosen groups between clusters (mp_snapshot.h: the same image, the same unit bodies, through a group list) ---------------
+ * A group is one lane and talks to no other group, so its state travels on its own: an image of "these n groups, in this order"
+ * is the image of an n-group cluster.  The list is a host array -- a move is a rare host decision -- checked here before
+ * anything is launched. */
+static int glist_room(GroupListBuf &b, uint32_t n) {
+    if (b.dev && n <= b.cap) return SMR_OK;
+    if (b.dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(b.dev); b.dev = nullptr; b.cap = 0; }   // (a launch may still read it)
+    hipError_t e = hipMalloc((void **)&b.dev, (size_t)n * 4);
+    if (e != hipSuccess) { b.dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("mp groups: hipMalloc of the list: ") + hipGetErrorString(e)); }
+    b.cap = n;
+    return SMR_OK;
+}
+// n in 1 .. n_groups, every id below n_groups, none twice (a bitmap: O(n))
+static int glist_check(const smr_mp_cluster *c, const uint32_t *groups, uint32_t n) {
+    const uint32_t G = c->cfg.n_groups;
+    if (n == 0 || n > G) return fail(SMR_ERR_ARG, "mp groups: a list of " + std::to_string(n) + " groups for a cluster of " + std::to_string(G));
+    std::vector<uint64_t> seen(((size_t)G + 63) / 64, 0ull);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t g = groups[i];
+        if (g >= G) return fail(SMR_ERR_ARG, "mp groups: list entry " + std::to_string(i) + " is group " + std::to_string(g) + " of " + std::to_string(G));
+        if ((seen[g >> 6] >> (g & 63u)) & 1ull) return fail(SMR_ERR_ARG, "mp groups: group " + std::to_string(g) + " is listed twice");
+        seen[g >> 6] |= 1ull << (g & 63u);
+    }
+    return SMR_OK;
+}
+// what save and load through a list ask of (cluster, snapshot, list) before they look at the image
+static int groups_check(const smr_mp_cluster *c, const smr_mp_snapshot *s, const uint32_t *groups, uint32_t n, const char *verb) {
+    if (!c || !s || !groups) return fail(SMR_ERR_ARG, "mp groups: null argument");
+    if (int rc = glist_check(c, groups, n)) return rc;
+    if (n != s->G) return fail(SMR_ERR_ARG, "mp groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
+    if (s->R != c->cfg.population || s->commit_extra != c->cfg.commit_extra || s->live != (uint8_t)c->hp.live)
+        return fail(SMR_ERR_ARG, "mp groups: the snapshot was made for another population / commit_extra / live mask");
+    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, std::string("mp groups: ") + verb + " inside an open tick");
+    return SMR_OK;
+}
+// The list in front of the kernel, on its stream.  The caller's array is pageable memory, which the runtime has read (staged)
+// by the time the copy call returns: the caller may reuse it at once, and the next call may overwrite the device buffer, in
+// stream order
+static int glist_upload(GroupListBuf &b, const uint32_t *groups, uint32_t n, hipStream_t st) {
+    if (int rc = glist_room(b, n)) return rc;
+    SMR_HIP_TRY(hipMemcpyAsync(b.dev, groups, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    return SMR_OK;
+}
+// a deferred R3 rest of the WHOLE cluster must run before single groups are read or replaced (defence only, as in save)
+static int flush_rest(smr_mp_cluster *c, hipStream_t st) {
+    if (!c->rest_pending) return SMR_OK;
+    c->rest_pending = false;
+    hipLaunchKernelGGL(mp_round_replies, mp_grid(c), dim3(MP_BLOCK), 0, st, c->dp, c->rest_par, c->rest_ackctl, 0, 0);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_mp_snapshot_create_groups(const smr_mp_cluster *like, uint32_t n, smr_mp_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "mp groups: null argument");
+    if (n == 0 || n > like->cfg.n_groups)
+        return fail(SMR_ERR_ARG, "mp groups: a snapshot of " + std::to_string(n) + " groups of a cluster of " + std::to_string(like->cfg.n_groups));
+    smr_mp_snapshot *s = nullptr;
+    if (int rc = snap_create(like, n, &s)) return rc;
+    if (int rc = glist_room(s->glist, n)) { smr_mp_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
+    *out = s;
+    return SMR_OK;
+}
+
+int smr_mp_save_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, smr_mp_snapshot *s, void *stream) {
+    if (int rc = groups_check(c, s, groups_host, n, "save")) return rc;
+    if (int rc = snap_room(s, c)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = flush_rest(c, st)) return rc;
+    if (int rc = glist_upload(s->glist, groups_host, n, st)) return rc;
+    const SnapImg S = snap_img(s);
+    hipLaunchKernelGGL(mp_snap_pack_groups, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S, (const uint32_t *)s->glist.dev);
+    SMR_HIP_TRY(hipGetLastError());
+    s->buf.filled = true; s->buf.hdr_known = false;
+    s->lead_hint = c->lead_hint;
+    return SMR_OK;
+}
+
+int smr_mp_load_groups(smr_mp_cluster *c, const smr_mp_snapshot *cs, const uint32_t *groups_host, uint32_t n, void *stream) {
+    smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);      // (the header is read back and cached on first use)
+    if (int rc = groups_check(c, s, groups_host, n, "load")) return rc;
+    if (int rc = snap_header(s)) return rc;
+    const SnapHdr &h = s->hdr;
+    if (h.n_groups != n || h.population != c->cfg.population || h.commit_extra != c->cfg.commit_extra || h.live_mask != (uint8_t)c->hp.live)
+        return fail(SMR_ERR_ARG, "mp groups: the image is of another n_groups / population / commit_extra / live mask");
+    if (h.max_live > c->cfg.window)
+        return fail(SMR_ERR_ARG, "mp groups: a log of " + std::to_string(h.max_live) + " live slots does not fit window " + std::to_string(c->cfg.window));
+    if (h.max_outbox > c->cfg.outbox_cap)
+        return fail(SMR_ERR_ARG, "mp groups: " + std::to_string(h.max_outbox) + " pending outbox entries do not fit outbox_cap " + std::to_string(c->cfg.outbox_cap));
+    if (h.n_commits != 0)                                        // they are the source's reporting, under the source's group ids
+        return fail(SMR_ERR_ARG, "mp groups: the image carries " + std::to_string(h.n_commits) + " unpolled commits: poll the source first");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = flush_rest(c, st)) return rc;
+    if (int rc = glist_upload(s->glist, groups_host, n, st)) return rc;
+    const SnapImg S = snap_img(s);
+    hipLaunchKernelGGL(mp_snap_unpack_groups, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S, (const uint32_t *)s->glist.dev, 0);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_mp_reset_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!c || !groups_host) return fail(SMR_ERR_ARG, "mp groups: null argument");
+    if (int rc = glist_check(c, groups_host, n)) return rc;
+    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, "mp groups: reset inside an open tick");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = flush_rest(c, st)) return rc;
+    if (int rc = glist_upload(c->glist, groups_host, n, st)) return rc;
+    SnapImg S;                                                   // no image: the geometry of n groups alone
+    S.base = nullptr; S.cap_slots = S.cap_ob = S.cap_cl = 0;
+    S.geo = snap_geom(n, c->cfg.population, c->hp.live); S.commit_extra = c->cfg.commit_extra;
+    hipLaunchKernelGGL(mp_snap_unpack_groups, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S, (const uint32_t *)c->glist.dev, 1);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
 }

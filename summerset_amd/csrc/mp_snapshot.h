@@ -150,22 +150,48 @@ SMR_HD SnapScal snap_scal(uint8_t *base, const SnapGeom &q, uint32_t i) {
     return s;
 }
 
+// ---- which group of the cluster an image position holds ------------------------------------------------------------------
+// An image has its own group index (position i, stride n = its n_groups, lane = i & 63) and the cluster has its own (group g,
+// stride P.G, rows at tix(W, row, g)).  For a whole-cluster image they are one and the same; an image of "these n groups, in
+// this order" (smr_mp_save_groups / smr_mp_load_groups) is the image of an n-group cluster whose group i is group list[i] of
+// this one -- the same format, the same tiles, bases and placement run over list positions, and the cluster side a gather or
+// scatter: two listed groups share a line of a ring row only where they sit in the same 64-group tile.  The unit bodies below
+// take the map as a parameter; with SnapAllGroups they are what they were.
+// What a group image does not carry (WHOLE = false): the counters and the unpolled commit list.  They are the cluster's
+// reporting, not a group's state -- events stay counted where they happened, so the sum over clusters is conserved, and a moved
+// group's unpolled entries stay on the source's list under the source's group id (the host polls the source before it reuses
+// the slot).  The image's counters and commit-list words are zero and n_commits = 0; a load through a list leaves the
+// target's counters, commit list, straggler list, role_rot and the host's scheduling state alone.
+struct SnapAllGroups {
+    static constexpr bool WHOLE = true;
+    __device__ __forceinline__ uint32_t n(const MpParams &P, const SnapGeom &) const { return P.G; }
+    __device__ __forceinline__ uint32_t group(uint32_t i, bool) const { return i; }
+};
+struct SnapGroupList {
+    static constexpr bool WHOLE = false;
+    const uint32_t *__restrict__ list;                           // [n], every entry < P.G, none twice (the host has checked)
+    __device__ __forceinline__ uint32_t n(const MpParams &, const SnapGeom &Q) const { return Q.G; }
+    __device__ __forceinline__ uint32_t group(uint32_t i, bool in) const { return in ? list[i] : 0u; }
+};
+
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // A wavefront's tiles carry all their live replicas.  Tiles, bases and placement are snapshot_common.h's; a
 // group's counts cost the bases 12 B per replica out of the L2.
 
-// live slots and pending outbox entries of replica r (the i-th live one) of group g: the cluster's own (PACK) or the image's
-template <bool PACK>
-__device__ __forceinline__ void snap_count(const MpParams &P, int par, const SnapImg &S, uint32_t r, uint32_t i, uint32_t g, uint32_t &ns,
-                                           uint32_t &no) {
+// live slots and pending outbox entries of replica r (the i-th live one) at image position x: the cluster's own (PACK: of
+// the group the map puts there) or the image's
+template <bool PACK, class Map>
+__device__ __forceinline__ void snap_count(const MpParams &P, int par, const SnapImg &S, const Map &M, uint32_t r, uint32_t i, uint32_t x,
+                                           uint32_t &ns, uint32_t &no) {
     if (PACK) {
         const RepView v{P.rep[0], (size_t)r * P.rep_stride};
+        const uint32_t g = M.group(x, true);
         ns = v.log_len()[g] - v.start_slot()[g];
         no = v.ob_cnt(par)[g];
     } else {
         const SnapScal sc = snap_scal(S.base, S.geo, i);
-        ns = sc.len[g] - sc.start[g];
-        no = sc.nob[g];
+        ns = sc.len[x] - sc.start[x];
+        no = sc.nob[x];
     }
     if (ns > P.W) ns = P.W;
     if (no > P.cap) no = P.cap;
@@ -175,8 +201,9 @@ __device__ __forceinline__ void snap_count(const MpParams &P, int par, const Sna
 // replica by replica: with the replicas as the inner loop of snap_bases' per-group functor, save and load of the headline shape
 // (65 536 groups x 5 replicas) took 16 % and 22 % longer on the MI355X (profiles/snapshot_refactor_ab.log) -- each replica's
 // pass streams through three arrays, and the simple loop over groups is what the compiler keeps several loads in flight for
-template <bool PACK>
-__device__ __forceinline__ void mp_snap_bases(const MpParams &P, int par, const SnapImg &S, const SnapWave &w, uint64_t (&base)[2], uint32_t (&mx)[2]) {
+template <bool PACK, class Map>
+__device__ __forceinline__ void mp_snap_bases(const MpParams &P, int par, const SnapImg &S, const Map &M, const SnapWave &w, uint64_t (&base)[2],
+                                              uint32_t (&mx)[2]) {
     __shared__ uint64_t sh_s[4], sh_o[4];
     __shared__ uint32_t sh_ms[4], sh_mo[4];
     const uint32_t wv = threadIdx.x >> 6;
@@ -186,7 +213,7 @@ __device__ __forceinline__ void mp_snap_bases(const MpParams &P, int par, const 
         if (!((S.geo.live >> r) & 1u)) continue;
         for (uint32_t g = threadIdx.x; g < w.gb0; g += 256) {
             uint32_t ns, no;
-            snap_count<PACK>(P, par, S, r, i, g, ns, no);
+            snap_count<PACK>(P, par, S, M, r, i, g, ns, no);
             s += ns; o += no; xs = ns > xs ? ns : xs; xo = no > xo ? no : xo;
         }
         i++;
@@ -203,7 +230,7 @@ __device__ __forceinline__ void mp_snap_bases(const MpParams &P, int par, const 
         if (!((S.geo.live >> r) & 1u)) continue;
         for (uint32_t g = w.gb0 + w.lane; g < w.gw0; g += 64) {
             uint32_t ns, no;
-            snap_count<PACK>(P, par, S, r, i, g, ns, no);
+            snap_count<PACK>(P, par, S, M, r, i, g, ns, no);
             s += ns; o += no; xs = ns > xs ? ns : xs; xo = no > xo ? no : xo;
         }
         i++;
@@ -214,12 +241,14 @@ __device__ __forceinline__ void mp_snap_bases(const MpParams &P, int par, const 
 }
 
 // one (tile, replica): scalars, then the slot rows, then the outbox rows.  base: record index of the unit's first slot /
-// outbox record on entry, of the next unit's on return
-__device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const SnapImg &S, uint32_t r, uint32_t i, uint32_t tile,
+// outbox record on entry, of the next unit's on return.  x: the lane's position in the image, g: its group in the cluster
+template <class Map>
+__device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const SnapImg &S, const Map &M, uint32_t r, uint32_t i, uint32_t tile,
                                                uint64_t (&base)[2], uint32_t (&mx)[2]) {
     const SnapGeom &Q = S.geo;
-    const uint32_t lane = threadIdx.x & 63u, g = tile * 64 + lane;
-    const bool in = g < P.G;
+    const uint32_t lane = threadIdx.x & 63u, x = tile * 64 + lane, nx = M.n(P, Q);
+    const bool in = x < nx;
+    const uint32_t g = M.group(x, in);
     const RepView v{P.rep[0], (size_t)r * P.rep_stride};
     const SnapScal sc = snap_scal(S.base, Q, i);
     uint32_t leader = NO_REP, start = 0, len = 0, cbar = 0, brun = SNAP_NONE, nob = 0;
@@ -228,11 +257,11 @@ __device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const
         leader = v.leader()[g]; bms = v.bal_max_seen()[g]; start = v.start_slot()[g]; len = v.log_len()[g];
         cbar = v.commit_bar()[g]; brun = v.bal_lo()[g]; nob = v.ob_cnt(par)[g];
         if (nob > P.cap) nob = P.cap;
-        sc.leader[g] = (uint8_t)leader; sc.bps[g] = v.bal_prep_sent()[g]; sc.bpd[g] = v.bal_prepared()[g]; sc.bms[g] = bms;
-        sc.start[g] = start; sc.len[g] = len; sc.abar[g] = v.accept_bar()[g]; sc.cbar[g] = cbar; sc.ebar[g] = v.exec_bar()[g];
-        sc.snap[g] = v.snap_bar()[g]; sc.nob[g] = nob;
-        for (uint32_t p = 0; p < P.R; p++) sc.peb[(size_t)p * P.G + g] = p == r ? 0u : v.peer_exec_bar()[(size_t)p * P.G + g];
-        if (i == 0) S.base[Q.off_ovf + g] = P.overflow[g];
+        sc.leader[x] = (uint8_t)leader; sc.bps[x] = v.bal_prep_sent()[g]; sc.bpd[x] = v.bal_prepared()[g]; sc.bms[x] = bms;
+        sc.start[x] = start; sc.len[x] = len; sc.abar[x] = v.accept_bar()[g]; sc.cbar[x] = cbar; sc.ebar[x] = v.exec_bar()[g];
+        sc.snap[x] = v.snap_bar()[g]; sc.nob[x] = nob;
+        for (uint32_t p = 0; p < P.R; p++) sc.peb[(size_t)p * nx + x] = p == r ? 0u : v.peer_exec_bar()[(size_t)p * P.G + g];
+        if (i == 0) S.base[Q.off_ovf + x] = P.overflow[g];
     }
     uint32_t n = in ? len - start : 0u;
     if (n > P.W) n = P.W;
@@ -240,7 +269,7 @@ __device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const
     const uint32_t maxn = snap_place(n, base[0], S.cap_slots, lane, [&](uint32_t k, uint64_t pos) {
         const uint32_t slot = start + k;
         const size_t t = tix(P.W, slot & P.Wmask, g);
-        const uint32_t val = v.s_val()[t];
+        const uint32_t val = v.s_val()[t];                       // (three independent loads of one row, issued together)
         uint32_t m = v.s_meta()[t];
         uint64_t bal = v.s_bal()[t];
         mp_slot_stored(slot, brun, leader, r, cbar, bms, val, bal, m);
@@ -264,34 +293,40 @@ __device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const
     mx[0] = maxn > mx[0] ? maxn : mx[0]; mx[1] = maxo > mx[1] ? maxo : mx[1];
 }
 
-__device__ __forceinline__ void snap_unpack_unit(const MpParams &P, int par, const SnapImg &S, uint32_t r, uint32_t i, uint32_t tile,
+// ... and back.  FRESH: the unpack of nothing -- no image is read, the group becomes what smr_mp_cluster_create leaves
+// (mp_types.h: MP_INIT_WORD, MP_INIT_LEADER), which is how smr_mp_reset_groups empties a slot
+template <class Map, bool FRESH>
+__device__ __forceinline__ void snap_unpack_unit(const MpParams &P, int par, const SnapImg &S, const Map &M, uint32_t r, uint32_t i, uint32_t tile,
                                                  uint64_t (&base)[2]) {
     const SnapGeom &Q = S.geo;
-    const uint32_t lane = threadIdx.x & 63u, g = tile * 64 + lane;
-    const bool in = g < P.G;
+    const uint32_t lane = threadIdx.x & 63u, x = tile * 64 + lane, nx = M.n(P, Q);
+    const bool in = x < nx;
+    const uint32_t g = M.group(x, in);
     const RepView v{P.rep[0], (size_t)r * P.rep_stride};
     const SnapScal sc = snap_scal(S.base, Q, i);
+    const auto img = [&](const auto *a, size_t k) { return FRESH ? decltype(+a[0])(MP_INIT_WORD) : +a[k]; };
     uint32_t start = 0, len = 0, ebar = 0, nob = 0;
     if (in) {
-        start = sc.start[g]; len = sc.len[g]; ebar = sc.ebar[g]; nob = sc.nob[g];
+        start = img(sc.start, x); len = img(sc.len, x); ebar = img(sc.ebar, x); nob = img(sc.nob, x);
         if (nob > P.cap) nob = P.cap;
-        v.leader()[g] = sc.leader[g]; v.bal_prep_sent()[g] = sc.bps[g]; v.bal_prepared()[g] = sc.bpd[g]; v.bal_max_seen()[g] = sc.bms[g];
-        v.start_slot()[g] = start; v.log_len()[g] = len; v.accept_bar()[g] = sc.abar[g]; v.commit_bar()[g] = sc.cbar[g];
-        v.exec_bar()[g] = ebar; v.snap_bar()[g] = sc.snap[g];
-        for (uint32_t p = 0; p < P.R; p++) v.peer_exec_bar()[(size_t)p * P.G + g] = sc.peb[(size_t)p * P.G + g];
+        v.leader()[g] = FRESH ? (uint8_t)MP_INIT_LEADER : sc.leader[x];
+        v.bal_prep_sent()[g] = img(sc.bps, x); v.bal_prepared()[g] = img(sc.bpd, x); v.bal_max_seen()[g] = img(sc.bms, x);
+        v.start_slot()[g] = start; v.log_len()[g] = len; v.accept_bar()[g] = img(sc.abar, x); v.commit_bar()[g] = img(sc.cbar, x);
+        v.exec_bar()[g] = ebar; v.snap_bar()[g] = img(sc.snap, x);
+        for (uint32_t p = 0; p < P.R; p++) v.peer_exec_bar()[(size_t)p * P.G + g] = img(sc.peb, (size_t)p * nx + x);
         // every ballot and meta word below is stored: no run.  The next steady-state append starts one at the log end
         // (BAL_EXTEND, r1_body / r2_body), which is the state every end_run() leaves
-        v.bal_lo()[g] = SNAP_NONE;
+        v.bal_lo()[g] = FRESH ? MP_INIT_WORD : SNAP_NONE;
         v.ob_cnt(par)[g] = nob; v.ob_cnt(par ^ 1)[g] = 0;
         v.ob_reg(0)[g] = 0; v.ob_reg(1)[g] = 0;                  // explicit entries
         v.pr_cnt()[g] = 0;
-        if (i == 0) { P.overflow[g] = S.base[Q.off_ovf + g]; P.r1_done[g] = 0; }
+        if (i == 0) { P.overflow[g] = (uint8_t)img(S.base + Q.off_ovf, x); P.r1_done[g] = 0; }
     }
     uint32_t n = in ? len - start : 0u;
     if (n > P.W) n = P.W;
     const SnapSlot *const recs = (const SnapSlot *)(S.base + Q.fixed);
     uint32_t nlb = SNAP_NONE;                                    // first Null at or above exec_bar (MpRep::null_lb), else the log end
-    snap_place(n, base[0], S.cap_slots, lane, [&](uint32_t k, uint64_t pos) {
+    if (!FRESH) snap_place(n, base[0], S.cap_slots, lane, [&](uint32_t k, uint64_t pos) {
         const uint32_t slot = start + k;
         const size_t t = tix(P.W, slot & P.Wmask, g);
         const SnapSlot c = recs[pos];
@@ -305,7 +340,7 @@ __device__ __forceinline__ void snap_unpack_unit(const MpParams &P, int par, con
     });
     if (in) v.null_lb()[g] = nlb == SNAP_NONE ? len : nlb;
     const SnapMsg *const msgs = (const SnapMsg *)(S.base + snap_off_msgs(S));
-    snap_place(nob, base[1], S.cap_ob, lane, [&](uint32_t j, uint64_t pos) {
+    if (!FRESH) snap_place(nob, base[1], S.cap_ob, lane, [&](uint32_t j, uint64_t pos) {
         const size_t o = tix(P.cap, j, g);
         const SnapMsg e = msgs[pos];
         v.ob_slot(par)[o] = e.slot; v.ob_bal(par)[o] = e.bal; v.ob_val(par)[o] = e.val;
@@ -348,51 +383,77 @@ __device__ __forceinline__ void snap_lists(const MpParams &P, const SnapImg &S, 
     n_commits = off;
 }
 
-__global__ __launch_bounds__(256) void mp_snap_pack(const MpParams *__restrict__ Pp, int par, const SnapImg S) {
-    const MpParams &P = *Pp;
+// save: the whole cluster (mp_snap_pack) or the listed groups (mp_snap_pack_groups)
+template <class Map>
+__device__ __forceinline__ void snap_pack_all(const MpParams &P, int par, const SnapImg &S, const Map &M) {
     const SnapGeom &Q = S.geo;
-    const SnapWave w = snap_wave(Q.tiles, P.G);
+    const uint32_t nx = M.n(P, Q);
+    const SnapWave w = snap_wave(Q.tiles, nx);
     uint64_t base[2];                                            // slot, outbox records in front
     uint32_t mx[2];
-    mp_snap_bases<true>(P, par, S, w, base, mx);
+    mp_snap_bases<true>(P, par, S, M, w, base, mx);
     for (uint32_t t = w.t0; t < w.t1; t++)
         for (uint32_t r = 0, i = 0; r < P.R; r++) {
             if (!((Q.live >> r) & 1u)) continue;
-            snap_pack_unit(P, par, S, r, i, t, base, mx);
+            snap_pack_unit(P, par, S, M, r, i, t, base, mx);
             i++;
         }
-    uint64_t n_commits;
-    uint32_t max_commits;
-    snap_lists<true>(P, S, n_commits, max_commits);
+    uint64_t n_commits = 0;
+    uint32_t max_commits = 0;
+    if (Map::WHOLE) snap_lists<true>(P, S, n_commits, max_commits);
+    else if (blockIdx.x == 0 && threadIdx.x < Q.L) {             // a group image carries no counters and no commit entries
+        SnapRep z;
+        z.counters[0] = z.counters[1] = z.counters[2] = 0; z.clist_total = z.clist_carried = 0;
+        ((SnapRep *)(S.base + Q.off_rep))[threadIdx.x] = z;
+    }
     if (w.last && w.lane == 0) {                                 // the wavefront of the last tile knows the totals
         SnapHdr h;
         h.magic = SNAP_MAGIC; h.version = SNAP_VERSION;
-        h.n_groups = P.G; h.population = (uint8_t)P.R; h.commit_extra = (uint8_t)S.commit_extra; h.live_mask = (uint8_t)Q.live; h.reserved0 = 0;
+        h.n_groups = nx; h.population = (uint8_t)P.R; h.commit_extra = (uint8_t)S.commit_extra; h.live_mask = (uint8_t)Q.live; h.reserved0 = 0;
         h.n_slots = base[0]; h.n_outbox = base[1]; h.n_commits = n_commits;
         h.bytes = Q.fixed + base[0] * sizeof(SnapSlot) + base[1] * sizeof(SnapMsg) + n_commits * 8;
         h.max_live = mx[0]; h.max_outbox = mx[1]; h.max_commits = max_commits; h.reserved1 = 0;
         *(SnapHdr *)S.base = h;
-        snap_zero_pad(S.base, Q.off_ovf, P.G);                   // padding is zero
-        for (uint32_t i = 0; i < Q.L; i++) snap_zero_pad(S.base, Q.off_scal + (uint64_t)i * Q.scal_stride, Q.o_leader + P.G);
+        snap_zero_pad(S.base, Q.off_ovf, nx);                    // padding is zero
+        for (uint32_t i = 0; i < Q.L; i++) snap_zero_pad(S.base, Q.off_scal + (uint64_t)i * Q.scal_stride, Q.o_leader + nx);
     }
 }
-
-__global__ __launch_bounds__(256) void mp_snap_unpack(const MpParams *__restrict__ Pp, int par, const SnapImg S) {
-    const MpParams &P = *Pp;
+// load: the whole cluster (mp_snap_unpack), the listed groups from an image (mp_snap_unpack_groups) or from nothing (FRESH)
+template <class Map, bool FRESH>
+__device__ __forceinline__ void snap_unpack_all(const MpParams &P, int par, const SnapImg &S, const Map &M) {
     const SnapGeom &Q = S.geo;
-    const SnapWave w = snap_wave(Q.tiles, P.G);
-    uint64_t base[2];
+    const SnapWave w = snap_wave(Q.tiles, M.n(P, Q));
+    uint64_t base[2] = {0, 0};
     uint32_t mx[2];
-    mp_snap_bases<false>(P, par, S, w, base, mx);
+    if (!FRESH) mp_snap_bases<false>(P, par, S, M, w, base, mx);
     for (uint32_t t = w.t0; t < w.t1; t++)
         for (uint32_t r = 0, i = 0; r < P.R; r++) {
             if (!((Q.live >> r) & 1u)) continue;
-            snap_unpack_unit(P, par, S, r, i, t, base);
+            snap_unpack_unit<Map, FRESH>(P, par, S, M, r, i, t, base);
             i++;
         }
-    uint64_t n_commits;
-    uint32_t max_commits;
-    snap_lists<false>(P, S, n_commits, max_commits);
+    if (Map::WHOLE) {
+        uint64_t n_commits;
+        uint32_t max_commits;
+        snap_lists<false>(P, S, n_commits, max_commits);
+    }
+}
+
+__global__ __launch_bounds__(256) void mp_snap_pack(const MpParams *__restrict__ Pp, int par, const SnapImg S) {
+    snap_pack_all(*Pp, par, S, SnapAllGroups{});
+}
+__global__ __launch_bounds__(256) void mp_snap_unpack(const MpParams *__restrict__ Pp, int par, const SnapImg S) {
+    snap_unpack_all<SnapAllGroups, false>(*Pp, par, S, SnapAllGroups{});
+}
+// group i of the image (S.geo.G = n groups) <-> group list[i] of the cluster; fresh: no image, the listed groups as
+// smr_mp_cluster_create leaves a group (S carries the geometry of n groups and no buffer)
+__global__ __launch_bounds__(256) void mp_snap_pack_groups(const MpParams *__restrict__ Pp, int par, const SnapImg S, const uint32_t *__restrict__ list) {
+    snap_pack_all(*Pp, par, S, SnapGroupList{list});
+}
+__global__ __launch_bounds__(256) void mp_snap_unpack_groups(const MpParams *__restrict__ Pp, int par, const SnapImg S, const uint32_t *__restrict__ list,
+                                                             int fresh) {
+    if (fresh) snap_unpack_all<SnapGroupList, true>(*Pp, par, S, SnapGroupList{list});
+    else snap_unpack_all<SnapGroupList, false>(*Pp, par, S, SnapGroupList{list});
 }
 
 }  // namespace smr

@@ -59,6 +59,12 @@ constexpr uint32_t OB_SLOT_MASK = (1u << 30) - 1;
 
 constexpr uint32_t NO_REP = 0xFFu;
 constexpr int MAXR = 8;
+// What smr_mp_cluster_create leaves for a group: no leader, and every other word of its state (scalars, bars, run start, outbox
+// counts, flags) MP_INIT_WORD -- an empty log at slot 0.  The one place that says it: create fills the arena from here, and
+// smr_mp_reset_groups (mp_snapshot.h: the unpack of nothing) returns a listed group to the same values
+constexpr uint32_t MP_INIT_WORD = 0;
+constexpr uint32_t MP_INIT_LEADER = NO_REP;
+static_assert(MP_INIT_WORD == 0 && MP_INIT_LEADER <= 0xFFu, "create fills bytes: a word of equal bytes, a one-byte leader id");
 
 // Wave-tiled indexing of every array with a row dimension (ring slots, outbox entries,
 // ack-matrix rows, PrepareReply entries):  X[g / 64][row][g % 64].  A wavefront's 64

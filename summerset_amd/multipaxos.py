@@ -27,6 +27,10 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _group_list(groups):
+    return np.ascontiguousarray(np.asarray(groups, dtype=np.int64).astype(np.uint32))
+
+
 class MpSnapshot(DeviceSnapshot):
     """A cluster's state between two ticks, held on the device (`smr_mp_snapshot`): what `MultiPaxosCluster.save_state`
     fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any two clusters that hold the
@@ -34,11 +38,22 @@ class MpSnapshot(DeviceSnapshot):
     population, commit_extra, live_mask"""
     _STEM, _INFO = "smr_mp_snapshot", _lib.MpSnapshotInfo
 
+    def __init__(self, like, n_groups=None):
+        """room for the worst case of `like`; n_groups: for that many of its groups only (`smr_mp_snapshot_create_groups`:
+        what `save_groups` fills and `load_groups` takes -- the image of an n_groups cluster)"""
+        if n_groups is None:
+            super().__init__(like)
+            return
+        self._L = _lib.load()
+        h = C.c_void_p()
+        check(self._L.smr_mp_snapshot_create_groups(like._h, int(n_groups), C.byref(h)))
+        self._h = h
+
     @classmethod
-    def from_bytes(cls, data, like):
-        """the snapshot an exported image holds; `like`: a cluster of the image's n_groups, population, commit_extra and
-        live mask (its window and capacities do not matter)"""
-        return cls(like).import_(data)
+    def from_bytes(cls, data, like, n_groups=None):
+        """the snapshot an exported image holds; `like`: a cluster of the image's n_groups (or any cluster, with n_groups given),
+        population, commit_extra and live mask (its window and capacities do not matter)"""
+        return cls(like, n_groups).import_(data)
 
 
 class MultiPaxosCluster:
@@ -183,6 +198,25 @@ class MultiPaxosCluster:
         and live mask; window, outbox_cap and commit_list_cap at least what the snapshot holds"""
         check(self._L.smr_mp_load_state(self._h, snap._h, stream_ptr(stream)))
 
+    def save_groups(self, groups, snap=None, stream=None):
+        """the listed groups' state as the image of a len(groups) cluster, group i of it = groups[i] (`smr_mp_save_groups`);
+        counters and unpolled commits stay here"""
+        g = _group_list(groups)
+        snap = MpSnapshot(self, len(g)) if snap is None else snap
+        check(self._L.smr_mp_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
+        return snap
+
+    def load_groups(self, snap, groups, stream=None):
+        """group i of a len(groups) image overwrites group groups[i]; every other group, the counters and the commit list
+        are left alone (`smr_mp_load_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_mp_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+    def reset_groups(self, groups, stream=None):
+        """the listed groups back to what a new cluster holds: no leader, empty log (`smr_mp_reset_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_mp_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
     def counters(self, rep):
         arr = (C.c_uint64 * 3)()
         check(self._L.smr_mp_counters(self._h, rep, C.byref(arr)))
@@ -231,3 +265,14 @@ class MultiPaxosCluster:
         ms, n = C.c_double(), C.c_uint64()
         check(self._L.smr_mp_profile_read(self._h, which, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def move_groups(src, src_groups, dst, dst_groups, snap=None, reset=True):
+    """groups src_groups[i] of `src` become groups dst_groups[i] of `dst` (between two ticks of both; poll `src`'s commits
+    first: they stay on its list): save, load, and the source's slots back to empty.  Returns the snapshot, for the next move
+    of as many groups.  Which job group sits in which slot is the caller's table"""
+    snap = src.save_groups(src_groups, snap)
+    dst.load_groups(snap, dst_groups)
+    if reset:
+        src.reset_groups(src_groups)
+    return snap
