@@ -769,6 +769,54 @@ int64_t smr_raft_snapshot_export(const smr_raft_snapshot *s, uint8_t *host, uint
 int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t len);
 int smr_raft_cluster_save_state(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, void *stream);
 int smr_raft_cluster_load_state(uint32_t n, smr_raft_leader *const *reps, const smr_raft_snapshot *const *snaps, void *stream);
+
+/* ---- chosen groups between replica objects, on the device --------------------------------------------------------------------
+ * A group is one lane and talks to no other group, so its state travels on its own: a job that shards Raft groups over ranks
+ * (layout L1) rebalances a hot rank, drains a device, splits, or admits a new group into a slot another has left without saving
+ * and loading whole replica objects of equal n_groups.  The contract is the one smr_mp_snapshot_create_groups settled.  No new
+ * format: an image of "these n groups, in this order" is the version-1 image of an n-group replica (what the reference's
+ * snapshot file and WAL hold for those groups, raft/snapshot.rs, raft/recovery.rs recover_from_wal, craft/snapshot.rs, plus the
+ * volatile state of summerset_server/src/main.rs:124-167), group i of the image being group groups_host[i] of the replica; it
+ * interchanges both ways with smr_raft_save_state / smr_raft_load_state images of an n-group replica object.
+ *   smr_raft_snapshot_create_groups  a snapshot object for n groups of a replica like `like`: its population, replica id,
+ *                            commit_extra and variant (fault_tolerance, repeat_threshold), worst-case room for its window and
+ *                            a full Reconstruct queue (growing by host-known sizes as above).  info, export and import work
+ *                            on it unchanged; import checks against n_groups = n;
+ *   smr_raft_save_groups     one kernel on `stream`; enqueues only, apart from handing the list to the device (an async copy
+ *                            on `stream` into a buffer the snapshot owns).  Every per-group scalar and peer row, the live
+ *                            entries' terms and, for CRaft, their shard bitmaps, the heartbeat counters, full_copy / alive /
+ *                            partial / last_recon and the Reconstruct queue of the listed groups, exactly as
+ *                            smr_raft_save_state writes them; record order, tiles (64 list entries), max_live /
+ *                            max_reconstructs and the header's totals taken over list positions.  ring_lo is stored
+ *                            canonically, so the target may have another window.  The replica is not modified;
+ *   smr_raft_load_groups     the inverse: group i of an n-group image overwrites the whole logical state of group
+ *                            groups_host[i]; nothing of any other group changes.  The image may come from
+ *                            smr_raft_save_groups or be an ordinary smr_raft_save_state image of an n-group replica.
+ *                            Synchronises once per save to read the image's header;
+ *   smr_raft_reset_groups    the listed groups back to exactly what smr_raft_leader_create (become_the_leader on a log that
+ *                            holds the dummy entry, raft/leadership.rs:145-218) and, for a CRaft replica,
+ *                            smr_raft_craft_enable (reply counters (1, 0, 0), every peer alive, server/heartbeat.rs:117-131)
+ *                            leave for a group, all `window` ring rows and the per-peer rows included;
+ *   smr_raft_cluster_save_groups / _load_groups / _reset_groups   a group lives in R replica objects: n_reps <= 8 distinct
+ *                            replicas of one device that share n_groups / population / variant, ONE list for all of them,
+ *                            each replica with its own snapshot, in ONE launch -- exactly what the n_reps single calls give.
+ * What does not travel: the eight counters.  Events stay counted where they happened, so the sum over replica objects is
+ * conserved: a group image holds zero counters, smr_raft_load_groups ignores an image's counters and leaves the target's alone.
+ * Nor do the CRaft payload store's shard bytes (smr_craft_pstore_*), as with smr_raft_save_state: a moved group's rows of the
+ * target's store are refilled by follow / Reconstruct as after any restart.  Which job group sits in which slot is the host's
+ * table.
+ * The list is a host array (a move is a rare host decision), checked before anything is launched: n in 1 .. n_groups, every id
+ * below n_groups, none twice; for save and load n is the snapshot's n_groups.  SMR_ERR_ARG for these, for a null argument,
+ * another population / replica id / commit_extra / variant / fault_tolerance / repeat_threshold, a max_live above the target's
+ * window, a replica or snapshot listed twice in a cluster form; SMR_ERR_STATE for an empty snapshot.  A refused call leaves
+ * replica and snapshot untouched. */
+int smr_raft_snapshot_create_groups(const smr_raft_leader *like, uint32_t n, smr_raft_snapshot **out);
+int smr_raft_save_groups(smr_raft_leader *l, const uint32_t *groups_host, uint32_t n, smr_raft_snapshot *s, void *stream);
+int smr_raft_load_groups(smr_raft_leader *l, const smr_raft_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_raft_reset_groups(smr_raft_leader *l, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_raft_cluster_save_groups(uint32_t n_reps, smr_raft_leader *const *reps, const uint32_t *groups_host, uint32_t n, smr_raft_snapshot *const *snaps, void *stream);
+int smr_raft_cluster_load_groups(uint32_t n_reps, smr_raft_leader *const *reps, const smr_raft_snapshot *const *snaps, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_raft_cluster_reset_groups(uint32_t n_reps, smr_raft_leader *const *reps, const uint32_t *groups_host, uint32_t n, void *stream);
 /* debug / measurement only: the device allocation that holds the replica's arrays (ring rows dead or alive, counter shards) and,
  * for a CRaft replica, the block smr_raft_craft_enable added (NULL / 0 otherwise), i.e. what a wholesale copy of the replica's
  * state would move -- tools/time_raft_snapshot.py times those copies beside smr_raft_save_state.  The layout inside is the

@@ -335,6 +335,13 @@ SYMBOLS = [
     ("smr_raft_snapshot_import", _i, [_vp, _vp, _u64]),
     ("smr_raft_cluster_save_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("smr_raft_cluster_load_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_raft_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_raft_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_raft_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_raft_reset_groups", _i, [_vp, _vp, _u32, _vp]),
+    ("smr_raft_cluster_save_groups", _i, [_u32, C.POINTER(_vp), _vp, _u32, C.POINTER(_vp), _vp]),
+    ("smr_raft_cluster_load_groups", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp, _u32, _vp]),
+    ("smr_raft_cluster_reset_groups", _i, [_u32, C.POINTER(_vp), _vp, _u32, _vp]),
     ("smr_raft_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_raft_craft_poll_reconstructs", _i, [_vp, _u32, _vp, _vp, _vp, _vp]),
     ("smr_raft_craft_handle_reconstruct_reply", _i, [_vp, _vp, _vp, _vp, _vp, _u32, _vp]),

@@ -1223,6 +1223,7 @@ struct smr_raft_leader {
     RaftView *d_view = nullptr;      // a device copy of v for smr_raft_cluster_replicate (made on first use; craft_enable changes v)
     bool d_view_ok = false;
     CraftView *d_cv = nullptr;       // ... and of cv, for the cluster forms of save / load (filled by craft_enable)
+    SnapGroupListBuf glist;          // smr_raft_reset_groups' list on the device
 };
 
 namespace smr {
@@ -1273,17 +1274,18 @@ int smr_raft_leader_create(const smr_raft_cfg *cfg, smr_raft_leader **out) {
     v.G = cfg->n_groups; v.W = cfg->window; v.Wmask = cfg->window - 1; v.R = cfg->population;
     v.me = cfg->leader_id; v.thresh = quorum + cfg->commit_extra;
     const size_t G = v.G;
-    e = hipMemset(l->arena.base, 0, l->arena.size);
-    // state right after become_the_leader on a log holding only the dummy entry
+    e = hipMemset(l->arena.base, (int)RAFT_INIT_WORD, l->arena.size);
+    // state right after become_the_leader on a log holding only the dummy entry: a group's initial values are
+    // raft_snapshot.h's RAFT_INIT_* (shared with smr_raft_reset_groups); the memset above is RAFT_INIT_WORD
     std::vector<uint64_t> t(G, cfg->term);
-    std::vector<uint32_t> one(G * v.R, 1u);
-    if (e == hipSuccess) e = hipMemset(v.role, ROLE_LEADER, G);
+    std::vector<uint32_t> len(G, RAFT_INIT_LOG_LEN), next(G * v.R, RAFT_INIT_NEXT), tryn(G * v.R, RAFT_INIT_TRY_NEXT);
+    if (e == hipSuccess) e = hipMemset(v.role, RAFT_INIT_ROLE, G);
     if (e == hipSuccess) e = hipMemset(v.leader, cfg->leader_id, G);
-    if (e == hipSuccess) e = hipMemset(v.voted_for, 0xFF, G);
+    if (e == hipSuccess) e = hipMemset(v.voted_for, RAFT_INIT_VOTED, G);
     if (e == hipSuccess) e = hipMemcpy(v.curr_term, t.data(), G * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(v.log_len, one.data(), G * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(v.next_slot, one.data(), G * v.R * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(v.try_next_slot, one.data(), G * v.R * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(v.log_len, len.data(), G * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(v.next_slot, next.data(), G * v.R * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(v.try_next_slot, tryn.data(), G * v.R * 4, hipMemcpyHostToDevice);
     // the device copy of the view smr_raft_cluster_replicate's followers are read through: made HERE (and again by craft_enable),
     // so that the stream-ordered call allocates and copies nothing (a blocking hipMalloc + hipMemcpy inside it)
     if (e == hipSuccess) e = hipGetDevice(&l->device);
@@ -1312,6 +1314,7 @@ void smr_raft_leader_destroy(smr_raft_leader *l) {
     if (l->d_view) (void)hipFree(l->d_view);
     if (l->d_cv) (void)hipFree(l->d_cv);
     if (l->wire_acc) (void)hipFree(l->wire_acc);
+    if (l->glist.dev) (void)hipFree(l->glist.dev);
     delete l;
 }
 
@@ -1395,22 +1398,23 @@ int smr_raft_craft_enable(smr_raft_leader *l, uint8_t fault_tolerance, uint8_t r
     const size_t ng4 = (G * 4 + 255) & ~(size_t)255, nq4 = ((size_t)CRAFT_RQ * G * 4 + 255) & ~(size_t)255, nq8 = ((size_t)CRAFT_RQ * G * 8 + 255) & ~(size_t)255;
     const size_t total = 2 * n8 + n1 + 2 * ng + nm + ng + 2 * ng4 + nq4 + nq8;
     SMR_HIP_TRY(hipMalloc((void **)&l->craft_base, total));
-    SMR_HIP_TRY(hipMemset(l->craft_base, 0, total));
+    SMR_HIP_TRY(hipMemset(l->craft_base, (int)RAFT_INIT_WORD, total));   // a group's initial values: raft_snapshot.h (shared with smr_raft_reset_groups)
     l->craft_bytes = total;
     CraftView &cv = l->cv;
     uint8_t *b = l->craft_base;
     cv.hb_replied = (uint64_t *)b; b += n8; cv.hb_seen = (uint64_t *)b; b += n8;
     cv.hb_repeat = b; b += n1; cv.full_copy = b; b += ng; cv.alive = b; b += ng;
     l->v.entry_mask = b;                                       // the dummy entry 0 and whatever the log holds so far: every shard
-    SMR_HIP_TRY(hipMemset(l->v.entry_mask, (int)((1u << R) - 1u), (size_t)l->v.W * G));
+    SMR_HIP_TRY(hipMemset(l->v.entry_mask, (int)craft_init_bits(R), (size_t)l->v.W * G));
     b += nm;
     cv.rq_term = (uint64_t *)b; b += nq8; cv.rq_slot = (uint32_t *)b; b += nq4; cv.last_recon = (uint32_t *)b; b += ng4;
     cv.rq_n = (uint32_t *)b; b += ng4; cv.partial = b;
     cv.ft = fault_tolerance; cv.rep_thr = repeat_threshold; cv.quorum = quorum;
-    std::vector<uint64_t> one(R * G, 1);                      // heartbeat.rs:117-119 reply_cnts start at (1, 0, 0)
-    for (size_t g = 0; g < G; g++) one[(size_t)l->v.me * G + g] = 0;
+    std::vector<uint64_t> one(R * G);                         // heartbeat.rs:117-119 reply_cnts start at (1, 0, 0)
+    for (size_t p = 0; p < R; p++)
+        for (size_t g = 0; g < G; g++) one[p * G + g] = craft_init_hb_replied(p != l->v.me);
     SMR_HIP_TRY(hipMemcpy(cv.hb_replied, one.data(), R * G * 8, hipMemcpyHostToDevice));
-    SMR_HIP_TRY(hipMemset(cv.alive, (int)((1u << R) - 1u), G));   // heartbeat.rs:131
+    SMR_HIP_TRY(hipMemset(cv.alive, (int)craft_init_bits(R), G));   // heartbeat.rs:131
     l->v.thresh = quorum + fault_tolerance;
     l->craft = true;
     SMR_HIP_TRY(hipMemcpy(l->d_view, &l->v, sizeof(RaftView), hipMemcpyHostToDevice));   // (the threshold moved: the view's device copy follows)
@@ -1739,6 +1743,7 @@ struct smr_raft_snapshot {
     SnapBuf buf;
     uint64_t cap_e = 0, cap_rq = 0;                              // records the device buffer's sections have room for
     RaftSnapHdr hdr;                                             // the image's header, once buf.hdr_known
+    SnapGroupListBuf glist;                                      // smr_raft_save_groups / smr_raft_load_groups: the list on the device
 };
 
 namespace smr {
@@ -1771,10 +1776,12 @@ static int rsnap_copy(const smr_raft_snapshot *s, uint8_t *host, const RaftSnapH
     return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
                               {{q.fixed, h.n_entries * 8, h.n_entries * 8}, {rsnap_off_rq(q, S), rq, rq}, {rsnap_off_mask(q, S), mask, snap_a8(mask)}});
 }
-static bool rsnap_like(const smr_raft_snapshot *s, const smr_raft_leader *l) {
-    return s->G == l->cfg.n_groups && s->R == l->cfg.population && s->me == l->cfg.leader_id && s->commit_extra == l->cfg.commit_extra &&
+// made for a replica like l, whatever its n_groups (a snapshot of chosen groups has its own)
+static bool rsnap_like_kind(const smr_raft_snapshot *s, const smr_raft_leader *l) {
+    return s->R == l->cfg.population && s->me == l->cfg.leader_id && s->commit_extra == l->cfg.commit_extra &&
            (s->craft != 0) == l->craft && (!l->craft || (s->ft == l->cv.ft && s->rep_thr == l->cv.rep_thr));
 }
+static bool rsnap_like(const smr_raft_snapshot *s, const smr_raft_leader *l) { return s->G == l->cfg.n_groups && rsnap_like_kind(s, l); }
 static bool rsnap_hdr_like(const RaftSnapHdr &h, const smr_raft_snapshot *s) {
     return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.commit_extra == s->commit_extra && h.variant == s->craft &&
            h.fault_tolerance == s->ft && h.repeat_threshold == s->rep_thr;
@@ -1812,14 +1819,64 @@ static int rsnap_setup(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapsh
     }
     return SMR_OK;
 }
+
+// ---- chosen groups between replica objects (raft_snapshot.h: the same image, the same bodies, through a group list) ----------
+static const char *const RGROUPS = "raft groups: ";
+enum RGroupsCall { RG_SAVE, RG_LOAD, RG_RESET };
+// the arguments of the one launch over n_reps replicas for the n listed groups (one list for all of them); every check before
+// anything is written, allocated or launched.  A reset has no snapshots
+static int rgroups_setup(uint32_t n_reps, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, const uint32_t *groups, uint32_t n,
+                         RGroupsCall call, RaftSnapArgs &A, RaftSnapGroups &L) {
+    if (!groups) return fail(SMR_ERR_ARG, "raft groups: null argument");
+    const auto replica = [&](uint32_t k) {
+        const smr_raft_leader *l = reps[k];
+        if (l->v.G != reps[0]->v.G || l->v.R != reps[0]->v.R || l->craft != reps[0]->craft)
+            return fail(SMR_ERR_ARG, "raft groups: the replicas differ in groups / population / variant");
+        if (l->device != reps[0]->device) return fail(SMR_ERR_ARG, "raft groups: a replica lives on another device");
+        if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, "raft groups: a replica has no device copy of its view");
+        return (int)SMR_OK;
+    };
+    if (call == RG_RESET) {                                      // (no snapshots: the replicas stand in for them in the pairs' check)
+        if (int rc = snap_pairs_check(n_reps, reps, reps, RGROUPS, replica)) return rc;
+    } else if (int rc = snap_pairs_check(n_reps, reps, snaps, RGROUPS, [&](uint32_t k) {
+                   if (int rc2 = replica(k)) return rc2;
+                   const smr_raft_snapshot *s = snaps[k];
+                   if (s->buf.device != reps[k]->device) return fail(SMR_ERR_ARG, "raft groups: a snapshot lives on another device");
+                   if (!rsnap_like_kind(s, reps[k])) return fail(SMR_ERR_ARG, "raft groups: the snapshot was made for another population / replica id / commit_extra / variant (plain or CRaft, fault_tolerance, repeat_threshold)");
+                   if (s->G != n) return fail(SMR_ERR_ARG, "raft groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
+                   return (int)SMR_OK;
+               })) return rc;
+    if (int rc = snap_glist_check(groups, n, reps[0]->v.G, RGROUPS)) return rc;
+    if (call == RG_LOAD)
+        for (uint32_t k = 0; k < n_reps; k++) {
+            smr_raft_snapshot *s = snaps[k];
+            if (int rc = rsnap_header(s)) return rc;
+            if (!rsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string("raft groups: the image is of ") + RSNAP_OTHER);
+            if (s->hdr.max_live > reps[k]->cfg.window)
+                return fail(SMR_ERR_ARG, "raft groups: a log of " + std::to_string(s->hdr.max_live) + " live entries does not fit window " +
+                                             std::to_string(reps[k]->cfg.window));
+        }
+    if (call == RG_SAVE)
+        for (uint32_t k = 0; k < n_reps; k++)
+            if (int rc = rsnap_room(snaps[k], reps[k])) return rc;
+    memset(&A, 0, sizeof(A));
+    memset(&L, 0, sizeof(L));
+    A.geo = rsnap_geom(n, reps[0]->v.R, reps[0]->craft);        // the geometry of an n-group replica
+    for (uint32_t k = 0; k < n_reps; k++) {
+        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.commit_extra[k] = reps[k]->cfg.commit_extra;
+        if (call != RG_RESET) { A.img[k] = snaps[k]->buf.dev; A.cap_e[k] = snaps[k]->cap_e; A.cap_rq[k] = snaps[k]->cap_rq; }
+        L.init_term[k] = reps[k]->cfg.term;
+    }
+    return SMR_OK;
+}
 }  // namespace smr
 
 extern "C" {
 
-int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+// a snapshot object for n groups of a replica like `like` (n = its n_groups: the whole replica)
+static int rsnap_create(const smr_raft_leader *like, uint32_t n, smr_raft_snapshot **out) {
     smr_raft_snapshot *s = new smr_raft_snapshot();
-    s->G = like->cfg.n_groups; s->R = like->cfg.population; s->me = like->cfg.leader_id; s->commit_extra = like->cfg.commit_extra;
+    s->G = n; s->R = like->cfg.population; s->me = like->cfg.leader_id; s->commit_extra = like->cfg.commit_extra;
     s->craft = like->craft ? 1 : 0; s->ft = like->craft ? (uint8_t)like->cv.ft : 0; s->rep_thr = like->craft ? (uint8_t)like->cv.rep_thr : 0;
     s->buf.device = like->device;
     memset(&s->hdr, 0, sizeof(s->hdr));
@@ -1828,9 +1885,78 @@ int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **ou
     return SMR_OK;
 }
 
+int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
+    return rsnap_create(like, like->cfg.n_groups, out);
+}
+
+int smr_raft_snapshot_create_groups(const smr_raft_leader *like, uint32_t n, smr_raft_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "raft groups: null argument");
+    if (n == 0 || n > like->cfg.n_groups)
+        return fail(SMR_ERR_ARG, "raft groups: a snapshot of " + std::to_string(n) + " groups of a replica of " + std::to_string(like->cfg.n_groups));
+    smr_raft_snapshot *s = nullptr;
+    if (int rc = rsnap_create(like, n, &s)) return rc;
+    if (int rc = snap_glist_room(s->glist, n, RGROUPS)) { smr_raft_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
+    *out = s;
+    return SMR_OK;
+}
+
+int smr_raft_cluster_save_groups(uint32_t n_reps, smr_raft_leader *const *reps, const uint32_t *groups_host, uint32_t n, smr_raft_snapshot *const *snaps,
+                                 void *stream) {
+    RaftSnapArgs A;
+    RaftSnapGroups L;
+    if (int rc = rgroups_setup(n_reps, reps, snaps, groups_host, n, RG_SAVE, A, L)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RGROUPS)) return rc;
+    L.list = snaps[0]->glist.dev;
+    hipLaunchKernelGGL(raft_snap_pack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, L);
+    SMR_HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < n_reps; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    return SMR_OK;
+}
+
+int smr_raft_cluster_load_groups(uint32_t n_reps, smr_raft_leader *const *reps, const smr_raft_snapshot *const *csnaps, const uint32_t *groups_host, uint32_t n,
+                                 void *stream) {
+    smr_raft_snapshot *const *snaps = const_cast<smr_raft_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
+    RaftSnapArgs A;
+    RaftSnapGroups L;
+    if (int rc = rgroups_setup(n_reps, reps, snaps, groups_host, n, RG_LOAD, A, L)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RGROUPS)) return rc;
+    L.list = snaps[0]->glist.dev;
+    hipLaunchKernelGGL(raft_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, L, 0);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_raft_cluster_reset_groups(uint32_t n_reps, smr_raft_leader *const *reps, const uint32_t *groups_host, uint32_t n, void *stream) {
+    RaftSnapArgs A;
+    RaftSnapGroups L;
+    if (int rc = rgroups_setup(n_reps, reps, nullptr, groups_host, n, RG_RESET, A, L)) return rc;
+    if (int rc = snap_glist_upload(reps[0]->glist, groups_host, n, (hipStream_t)stream, RGROUPS)) return rc;
+    L.list = reps[0]->glist.dev;
+    hipLaunchKernelGGL(raft_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, L, 1);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_raft_save_groups(smr_raft_leader *l, const uint32_t *groups_host, uint32_t n, smr_raft_snapshot *s, void *stream) {
+    if (!l || !s) return fail(SMR_ERR_ARG, "raft groups: null argument");
+    return smr_raft_cluster_save_groups(1, &l, groups_host, n, &s, stream);
+}
+
+int smr_raft_load_groups(smr_raft_leader *l, const smr_raft_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!l || !s) return fail(SMR_ERR_ARG, "raft groups: null argument");
+    return smr_raft_cluster_load_groups(1, &l, &s, groups_host, n, stream);
+}
+
+int smr_raft_reset_groups(smr_raft_leader *l, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!l) return fail(SMR_ERR_ARG, "raft groups: null argument");
+    return smr_raft_cluster_reset_groups(1, &l, groups_host, n, stream);
+}
+
 void smr_raft_snapshot_destroy(smr_raft_snapshot *s) {
     if (!s) return;
     snap_buf_free(s->buf);
+    if (s->glist.dev) (void)hipFree(s->glist.dev);               // (snap_buf_free has synchronised)
     delete s;
 }
 

@@ -10,6 +10,10 @@
 // Not carried: wire_acc (zero between calls), ring rows outside the live span (load leaves them alone, the dumps give zero
 // there) and the CRaft payload store's shard bytes (smr_craft_pstore_*: a restored replica's store is refilled by follow /
 // Reconstruct as after any restart).
+// Chosen groups (smr_raft_save_groups / smr_raft_load_groups / smr_raft_reset_groups and their cluster forms) go through the
+// same image and the same bodies: an image of "these n groups, in this order" is the image of an n-group replica, read and
+// written through a group list (RaftSnapGroupList below).  A group image holds zero counters, and like every image none of
+// the CRaft payload store's shard bytes.
 //
 // Image (little-endian; every section starts on a multiple of 8; padding bytes are zero):
 //   RaftSnapHdr                                      64 B
@@ -121,6 +125,42 @@ SMR_HD RaftSnapScal rsnap_scal(uint8_t *base, const RaftSnapGeom &q) {
     return s;
 }
 
+// ---- what a new replica object holds for a group ----------------------------------------------------------------------
+// The one place that says it: smr_raft_leader_create and smr_raft_craft_enable fill their arrays from here, and
+// smr_raft_reset_groups (the unpack of nothing, below) returns a listed group to the same values -- the state right after
+// become_the_leader (leadership.rs:145-218) on a log that holds only the dummy entry: role, leader = the replica's own id,
+// curr_term = the term it was created with, nobody voted for, log_len / next_slot / try_next_slot as below, every other word
+// of the group (its other scalars, match_slot, all W ring rows, the counters of the variant's queue) RAFT_INIT_WORD.  CRaft
+// on top: reply_cnts (1, 0, 0) for every peer (heartbeat.rs:117-119) and (0, 0, 0) for the replica itself, every peer alive
+// (heartbeat.rs:131), and every ring row's shard bitmap full (the dummy entry and whatever a log holds: every shard).
+constexpr uint32_t RAFT_INIT_WORD = 0;
+constexpr uint8_t RAFT_INIT_ROLE = ROLE_LEADER, RAFT_INIT_VOTED = NO_REP;
+constexpr uint32_t RAFT_INIT_LOG_LEN = 1, RAFT_INIT_NEXT = 1, RAFT_INIT_TRY_NEXT = 1;
+SMR_HD uint64_t craft_init_hb_replied(bool peer) { return peer ? 1ull : 0ull; }
+SMR_HD uint8_t craft_init_bits(uint32_t R) { return (uint8_t)((1u << R) - 1u); }   // alive, and a ring row's shard bitmap
+static_assert(RAFT_INIT_WORD == 0, "create fills bytes");
+
+// ---- which group of the replica an image position holds -----------------------------------------------------------------
+// An image has its own group index (position x, stride n = its n_groups, lane = x & 63) and the replica has its own (group g,
+// stride v.G).  For a whole-replica image they are one and the same; an image of "these n groups, in this order"
+// (smr_raft_save_groups / smr_raft_load_groups) is the image of an n-group replica whose group x is group list[x] of this one:
+// the same format, the same tiles, bases and placement run over list positions, and the replica side a gather or scatter.
+// The bodies below take the map as a parameter; with RaftSnapAllGroups they are what they were.
+// What a group image does not carry (WHOLE = false): the eight counters.  They are the replica object's reporting, not a
+// group's state -- events stay counted where they happened, so the sum over objects is conserved.  The image's counters are
+// zero, and a load through a list leaves the target's alone.
+struct RaftSnapAllGroups {
+    static constexpr bool WHOLE = true;
+    __device__ __forceinline__ uint32_t n(const RaftView &v, const RaftSnapGeom &) const { return v.G; }
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
+};
+struct RaftSnapGroupList {
+    static constexpr bool WHOLE = false;
+    const uint32_t *__restrict__ list;                           // [n], every entry < v.G, none twice (the host has checked)
+    __device__ __forceinline__ uint32_t n(const RaftView &, const RaftSnapGeom &Q) const { return Q.G; }
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
+};
+
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1); the replicas are reached
 // through the device copies of their views, as smr_raft_cluster_replicate's followers are.  Tiles, bases and placement are
@@ -133,21 +173,29 @@ struct RaftSnapArgs {
     uint8_t commit_extra[RMAX];
     RaftSnapGeom geo;
 };
+// what the listed-groups kernels take on top: the list (one for all replicas of the call) and, for a reset, the term each
+// replica was created with
+struct RaftSnapGroups {
+    const uint32_t *list;
+    uint64_t init_term[RMAX];
+};
 
-// live entries and queued Reconstruct slots in front of a wavefront: the replica's own (PACK) or the image's
-template <bool PACK>
-__device__ __forceinline__ void rsnap_bases(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, const SnapWave &w,
+// live entries and queued Reconstruct slots in front of a wavefront, over image positions: the replica's own (PACK: of the
+// group the map puts there) or the image's
+template <bool PACK, class Map>
+__device__ __forceinline__ void rsnap_bases(const RaftView &v, const CraftView &cv, bool craft, const RaftSnapScal &sc, const Map &M, const SnapWave &w,
                                             uint64_t (&base)[2], uint32_t (&mx)[2]) {
     snap_bases(
-        [&](uint32_t g, uint64_t (&add)[2], uint32_t (&m)[2]) {
+        [&](uint32_t x, uint64_t (&add)[2], uint32_t (&m)[2]) {
             uint32_t ne, nq;
             if (PACK) {
+                const uint32_t g = M.group(x, true);
                 ne = raft_live_n(v.start_slot[g], v.ring_lo[g], v.log_len[g], v.W);
                 nq = craft ? cv.rq_n[g] : 0u;
             } else {
-                ne = raft_live_n(sc.start[g], sc.rlo[g], sc.len[g], RSNAP_MAX_LOG);
+                ne = raft_live_n(sc.start[x], sc.rlo[x], sc.len[x], RSNAP_MAX_LOG);
                 if (ne > v.W) ne = v.W;                          // (load has refused such an image: max_live <= window)
-                nq = craft ? sc.rqn[g] : 0u;
+                nq = craft ? sc.rqn[x] : 0u;
             }
             if (nq > CRAFT_RQ) nq = CRAFT_RQ;
             add[0] += ne; add[1] += nq; m[0] = ne > m[0] ? ne : m[0]; m[1] = nq > m[1] ? nq : m[1];
@@ -177,7 +225,10 @@ __device__ __forceinline__ RaftSnapSel rsnap_select(const RaftSnapArgs &A) {
     return s;
 }
 
-__global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
+// save: the whole replica (raft_snap_pack) or the listed groups (raft_snap_pack_groups).  x: the lane's position in the
+// image (stride nx), g: its group in the replica (stride G)
+template <class Map>
+__device__ __forceinline__ void rsnap_pack_all(const RaftSnapArgs &A, const Map &M) {
     const RaftSnapGeom &Q = A.geo;
     const RaftSnapSel X = rsnap_select(A);
     const RaftView &v = X.v;
@@ -185,36 +236,39 @@ __global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
     const RaftSnapImg &S = X.S;
     const bool craft = Q.craft != 0;
     const RaftSnapScal sc = rsnap_scal(S.base, Q);
-    const SnapWave w = snap_wave(Q.tiles, v.G);
-    const size_t G = v.G;
+    const uint32_t nx = M.n(v, Q);
+    const SnapWave w = snap_wave(Q.tiles, nx);
+    const size_t G = v.G, NX = nx;
     uint64_t base[2];                                            // entries, queue records in front
     uint32_t mx[2];
-    rsnap_bases<true>(v, cv, craft, sc, w, base, mx);
+    rsnap_bases<true>(v, cv, craft, sc, M, w, base, mx);
     uint64_t *const terms = (uint64_t *)(S.base + Q.fixed);
     RaftSnapRq *const rqs = (RaftSnapRq *)(S.base + rsnap_off_rq(Q, S));
     uint8_t *const masks = S.base + rsnap_off_mask(Q, S);
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
+        const uint32_t x = t * 64 + w.lane;
+        const bool in = x < nx;
+        const uint32_t g = M.group(x, in);
         uint32_t n = 0, lo = 0, nq = 0;
-        if (g < v.G) {
+        if (in) {
             const uint32_t len = v.log_len[g], start = v.start_slot[g], rlo = raft_ring_lo(v.ring_lo[g], len, v.W);
             lo = raft_live_lo(start, rlo, len, v.W); n = len > lo ? len - lo : 0u;
-            sc.term[g] = v.curr_term[g]; sc.len[g] = len; sc.start[g] = start; sc.commit[g] = v.last_commit[g]; sc.snap[g] = v.last_snap[g];
-            sc.rlo[g] = rlo; sc.nexec[g] = v.n_exec[g]; sc.ntrunc[g] = v.n_trunc[g];
-            sc.role[g] = v.role[g]; sc.leader[g] = v.leader[g]; sc.voted[g] = v.voted_for[g]; sc.votes[g] = v.votes[g];
+            sc.term[x] = v.curr_term[g]; sc.len[x] = len; sc.start[x] = start; sc.commit[x] = v.last_commit[g]; sc.snap[x] = v.last_snap[g];
+            sc.rlo[x] = rlo; sc.nexec[x] = v.n_exec[g]; sc.ntrunc[x] = v.n_trunc[g];
+            sc.role[x] = v.role[g]; sc.leader[x] = v.leader[g]; sc.voted[x] = v.voted_for[g]; sc.votes[x] = v.votes[g];
             for (uint32_t p = 0; p < v.R; p++) {
-                const size_t o = (size_t)p * G + g;
+                const size_t o = (size_t)p * G + g, i = (size_t)p * NX + x;
                 const bool peer = p != v.me;
-                sc.next[o] = peer ? v.next_slot[o] : 0u; sc.tryn[o] = peer ? v.try_next_slot[o] : 0u; sc.match[o] = peer ? v.match_slot[o] : 0u;
+                sc.next[i] = peer ? v.next_slot[o] : 0u; sc.tryn[i] = peer ? v.try_next_slot[o] : 0u; sc.match[i] = peer ? v.match_slot[o] : 0u;
             }
             if (craft) {
                 nq = cv.rq_n[g];
                 if (nq > CRAFT_RQ) nq = CRAFT_RQ;
-                sc.full[g] = cv.full_copy[g]; sc.alive[g] = cv.alive[g]; sc.partial[g] = cv.partial[g];
-                sc.lrecon[g] = cv.last_recon[g]; sc.rqn[g] = nq;
+                sc.full[x] = cv.full_copy[g]; sc.alive[x] = cv.alive[g]; sc.partial[x] = cv.partial[g];
+                sc.lrecon[x] = cv.last_recon[g]; sc.rqn[x] = nq;
                 for (uint32_t p = 0; p < v.R; p++) {
-                    const size_t o = (size_t)p * G + g;
-                    sc.hbr[o] = cv.hb_replied[o]; sc.hbs[o] = cv.hb_seen[o]; sc.hbrep[o] = cv.hb_repeat[o];
+                    const size_t o = (size_t)p * G + g, i = (size_t)p * NX + x;
+                    sc.hbr[i] = cv.hb_replied[o]; sc.hbs[i] = cv.hb_seen[o]; sc.hbrep[i] = cv.hb_repeat[o];
                 }
             }
         }
@@ -231,11 +285,12 @@ __global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
         });
         mx[0] = maxn > mx[0] ? maxn : mx[0]; mx[1] = maxq > mx[1] ? maxq : mx[1];
     }
-    snap_counters_save<(int)SMR_CTR_STRIDE>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
+    if (Map::WHOLE) snap_counters_save<(int)SMR_CTR_STRIDE>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
+    else if (blockIdx.x == 0 && threadIdx.x < 8) ((uint64_t *)(S.base + Q.off_ctr))[threadIdx.x] = 0;   // a group image carries no counters
     if (w.last && w.lane == 0) {                                 // the wavefront of the last tile knows the totals
         RaftSnapHdr h;
         h.magic = RSNAP_MAGIC; h.version = RSNAP_VERSION;
-        h.n_groups = v.G; h.population = (uint8_t)v.R; h.me = (uint8_t)v.me; h.commit_extra = (uint8_t)X.commit_extra; h.variant = craft ? 1 : 0;
+        h.n_groups = nx; h.population = (uint8_t)v.R; h.me = (uint8_t)v.me; h.commit_extra = (uint8_t)X.commit_extra; h.variant = craft ? 1 : 0;
         h.fault_tolerance = craft ? (uint8_t)cv.ft : (uint8_t)0; h.repeat_threshold = craft ? (uint8_t)cv.rep_thr : (uint8_t)0;
         for (int k = 0; k < 6; k++) h.reserved0[k] = 0;
         h.n_entries = base[0]; h.n_rq = base[1]; h.bytes = rsnap_bytes(Q, base[0], base[1]);
@@ -250,9 +305,14 @@ __global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) {
 }
 
 // Load re-establishes: every scalar and peer row (row `me` as smr_raft_leader_create leaves it), the live entries' ring rows,
-// ring_lo for THIS window, the counters as one shard, the whole Reconstruct queue.  Ring rows outside the live span keep
-// what they held: no handler reads them (RaftLane::term_at, the leader's rlo guards) and the dumps give zero there.
-__global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) {
+// ring_lo for THIS window, the counters as one shard (the whole replica only), the whole Reconstruct queue.  Ring rows outside
+// the live span keep what they held: no handler reads them (RaftLane::term_at, the leader's rlo guards) and the dumps give
+// zero there.
+// FRESH: the unpack of nothing -- no image is read, the listed groups become what smr_raft_leader_create and
+// smr_raft_craft_enable leave (RAFT_INIT_* above), all W ring rows and the queue's rows included, which is how
+// smr_raft_reset_groups empties a slot
+template <class Map, bool FRESH>
+__device__ __forceinline__ void rsnap_unpack_all(const RaftSnapArgs &A, const Map &M, uint64_t init_term) {
     const RaftSnapGeom &Q = A.geo;
     const RaftSnapSel X = rsnap_select(A);
     const RaftView &v = X.v;
@@ -260,40 +320,67 @@ __global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) {
     const RaftSnapImg &S = X.S;
     const bool craft = Q.craft != 0;
     const RaftSnapScal sc = rsnap_scal(S.base, Q);
-    const SnapWave w = snap_wave(Q.tiles, v.G);
-    const size_t G = v.G;
-    uint64_t base[2];
+    const uint32_t nx = M.n(v, Q);
+    const SnapWave w = snap_wave(Q.tiles, nx);
+    const size_t G = v.G, NX = nx;
+    uint64_t base[2] = {0, 0};
     uint32_t mx[2];
-    rsnap_bases<false>(v, cv, craft, sc, w, base, mx);
+    if (!FRESH) rsnap_bases<false>(v, cv, craft, sc, M, w, base, mx);
     const uint64_t *const terms = (const uint64_t *)(S.base + Q.fixed);
     const RaftSnapRq *const rqs = (const RaftSnapRq *)(S.base + rsnap_off_rq(Q, S));
     const uint8_t *const masks = S.base + rsnap_off_mask(Q, S);
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
+        const uint32_t x = t * 64 + w.lane;
+        const bool in = x < nx;
+        const uint32_t g = M.group(x, in);
         uint32_t n = 0, lo = 0, nq = 0;
-        if (g < v.G) {
-            const uint32_t len = sc.len[g], start = sc.start[g], rlo = sc.rlo[g];
-            lo = raft_live_lo(start, rlo, len, RSNAP_MAX_LOG); n = len > lo ? len - lo : 0u;
-            if (n > v.W) { lo += n - v.W; n = v.W; }              // (refused by the host: max_live <= window)
-            v.curr_term[g] = sc.term[g]; v.log_len[g] = len; v.start_slot[g] = start; v.last_commit[g] = sc.commit[g]; v.last_snap[g] = sc.snap[g];
-            v.ring_lo[g] = raft_ring_lo(rlo, len, v.W); v.n_exec[g] = sc.nexec[g]; v.n_trunc[g] = sc.ntrunc[g];
-            v.role[g] = sc.role[g]; v.leader[g] = sc.leader[g]; v.voted_for[g] = sc.voted[g]; v.votes[g] = sc.votes[g];
+        if (in && FRESH) {
+            v.curr_term[g] = init_term; v.log_len[g] = RAFT_INIT_LOG_LEN; v.start_slot[g] = RAFT_INIT_WORD; v.last_commit[g] = RAFT_INIT_WORD;
+            v.last_snap[g] = RAFT_INIT_WORD; v.ring_lo[g] = RAFT_INIT_WORD; v.n_exec[g] = RAFT_INIT_WORD; v.n_trunc[g] = RAFT_INIT_WORD;
+            v.role[g] = RAFT_INIT_ROLE; v.leader[g] = (uint8_t)v.me; v.voted_for[g] = RAFT_INIT_VOTED; v.votes[g] = (uint8_t)RAFT_INIT_WORD;
             for (uint32_t p = 0; p < v.R; p++) {
                 const size_t o = (size_t)p * G + g;
-                const bool peer = p != v.me;
-                v.next_slot[o] = peer ? sc.next[o] : 1u; v.try_next_slot[o] = peer ? sc.tryn[o] : 1u; v.match_slot[o] = peer ? sc.match[o] : 0u;
+                v.next_slot[o] = RAFT_INIT_NEXT; v.try_next_slot[o] = RAFT_INIT_TRY_NEXT; v.match_slot[o] = RAFT_INIT_WORD;
+            }
+            for (uint32_t k = 0; k < v.W; k++) {
+                v.entry_term[(size_t)k * G + g] = RAFT_INIT_WORD;
+                if (craft) v.entry_mask[(size_t)k * G + g] = craft_init_bits(v.R);
             }
             if (craft) {
-                nq = sc.rqn[g];
-                if (nq > CRAFT_RQ) nq = CRAFT_RQ;
-                cv.full_copy[g] = sc.full[g]; cv.alive[g] = sc.alive[g]; cv.partial[g] = sc.partial[g];
-                cv.last_recon[g] = sc.lrecon[g]; cv.rq_n[g] = nq;
+                cv.full_copy[g] = (uint8_t)RAFT_INIT_WORD; cv.alive[g] = craft_init_bits(v.R); cv.partial[g] = (uint8_t)RAFT_INIT_WORD;
+                cv.last_recon[g] = RAFT_INIT_WORD; cv.rq_n[g] = RAFT_INIT_WORD;
                 for (uint32_t p = 0; p < v.R; p++) {
                     const size_t o = (size_t)p * G + g;
-                    cv.hb_replied[o] = sc.hbr[o]; cv.hb_seen[o] = sc.hbs[o]; cv.hb_repeat[o] = sc.hbrep[o];
+                    cv.hb_replied[o] = craft_init_hb_replied(p != v.me); cv.hb_seen[o] = RAFT_INIT_WORD; cv.hb_repeat[o] = (uint8_t)RAFT_INIT_WORD;
+                }
+                for (uint32_t j = 0; j < CRAFT_RQ; j++) { cv.rq_term[(size_t)j * G + g] = RAFT_INIT_WORD; cv.rq_slot[(size_t)j * G + g] = RAFT_INIT_WORD; }
+            }
+        }
+        if (in && !FRESH) {
+            const uint32_t len = sc.len[x], start = sc.start[x], rlo = sc.rlo[x];
+            lo = raft_live_lo(start, rlo, len, RSNAP_MAX_LOG); n = len > lo ? len - lo : 0u;
+            if (n > v.W) { lo += n - v.W; n = v.W; }              // (refused by the host: max_live <= window)
+            v.curr_term[g] = sc.term[x]; v.log_len[g] = len; v.start_slot[g] = start; v.last_commit[g] = sc.commit[x]; v.last_snap[g] = sc.snap[x];
+            v.ring_lo[g] = raft_ring_lo(rlo, len, v.W); v.n_exec[g] = sc.nexec[x]; v.n_trunc[g] = sc.ntrunc[x];
+            v.role[g] = sc.role[x]; v.leader[g] = sc.leader[x]; v.voted_for[g] = sc.voted[x]; v.votes[g] = sc.votes[x];
+            for (uint32_t p = 0; p < v.R; p++) {
+                const size_t o = (size_t)p * G + g, i = (size_t)p * NX + x;
+                const bool peer = p != v.me;
+                v.next_slot[o] = peer ? sc.next[i] : RAFT_INIT_NEXT; v.try_next_slot[o] = peer ? sc.tryn[i] : RAFT_INIT_TRY_NEXT;
+                v.match_slot[o] = peer ? sc.match[i] : RAFT_INIT_WORD;
+            }
+            if (craft) {
+                nq = sc.rqn[x];
+                if (nq > CRAFT_RQ) nq = CRAFT_RQ;
+                cv.full_copy[g] = sc.full[x]; cv.alive[g] = sc.alive[x]; cv.partial[g] = sc.partial[x];
+                cv.last_recon[g] = sc.lrecon[x]; cv.rq_n[g] = nq;
+                for (uint32_t p = 0; p < v.R; p++) {
+                    const size_t o = (size_t)p * G + g, i = (size_t)p * NX + x;
+                    cv.hb_replied[o] = sc.hbr[i]; cv.hb_seen[o] = sc.hbs[i]; cv.hb_repeat[o] = sc.hbrep[i];
                 }
             }
         }
+        if (FRESH) continue;
         snap_place(n, base[0], S.cap_e, w.lane, [&](uint32_t k, uint64_t pos) {
             const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
             v.entry_term[i] = terms[pos];
@@ -305,7 +392,20 @@ __global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) {
             cv.rq_term[i] = e.term; cv.rq_slot[i] = e.slot;
         });
     }
-    snap_counters_load<(int)SMR_CTR_STRIDE>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
+    if (Map::WHOLE) snap_counters_load<(int)SMR_CTR_STRIDE>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
+}
+
+__global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) { rsnap_pack_all(A, RaftSnapAllGroups{}); }
+__global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) { rsnap_unpack_all<RaftSnapAllGroups, false>(A, RaftSnapAllGroups{}, 0); }
+// group x of the image (A.geo.G = n groups) <-> group list[x] of the replica; fresh: no image, the listed groups as a new
+// replica object holds them (A carries the geometry of n groups and no buffers)
+__global__ __launch_bounds__(256) void raft_snap_pack_groups(const RaftSnapArgs A, const RaftSnapGroups L) { rsnap_pack_all(A, RaftSnapGroupList{L.list}); }
+__global__ __launch_bounds__(256) void raft_snap_unpack_groups(const RaftSnapArgs A, const RaftSnapGroups L, int fresh) {
+    uint64_t term = 0;
+#pragma unroll
+    for (int k = 0; k < (int)RMAX; k++) if (blockIdx.y == (unsigned)k) term = L.init_term[k];
+    if (fresh) rsnap_unpack_all<RaftSnapGroupList, true>(A, RaftSnapGroupList{L.list}, term);
+    else rsnap_unpack_all<RaftSnapGroupList, false>(A, RaftSnapGroupList{L.list}, term);
 }
 
 }  // namespace smr

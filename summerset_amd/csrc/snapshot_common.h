@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <initializer_list>
+#include <vector>
 
 #include "smr_common.h"
 
@@ -230,6 +231,42 @@ int snap_pairs_check(uint32_t n, Rep *const *reps, Snap *const *snaps, const cha
             if (reps[j] == reps[k] || snaps[j] == snaps[k]) return fail(SMR_ERR_ARG, std::string(what) + "a replica or a snapshot is listed twice");
         if (int rc = each(k)) return rc;
     }
+    return SMR_OK;
+}
+
+// a list of groups for a listed-groups call (chosen groups between objects: the list is a host array -- a move is a rare host
+// decision -- checked before anything is launched).  On the device it lives in a buffer owned by the snapshot object the call
+// works on (a reset: by the engine object), made once and grown only when a longer list comes
+struct SnapGroupListBuf { uint32_t *dev = nullptr; uint32_t cap = 0; };
+inline int snap_glist_room(SnapGroupListBuf &b, uint32_t n, const char *what) {
+    if (b.dev && n <= b.cap) return SMR_OK;
+    if (b.dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(b.dev); b.dev = nullptr; b.cap = 0; }   // (a launch may still read it)
+    hipError_t e = hipMalloc((void **)&b.dev, (size_t)n * 4);
+    if (e != hipSuccess) { b.dev = nullptr; return fail(SMR_ERR_DEVICE, std::string(what) + "hipMalloc of the list: " + hipGetErrorString(e)); }
+    b.cap = n;
+    return SMR_OK;
+}
+inline void snap_glist_free(SnapGroupListBuf &b) {
+    if (b.dev) { (void)hipDeviceSynchronize(); (void)hipFree(b.dev); b.dev = nullptr; b.cap = 0; }
+}
+// n in 1 .. G, every id below G, none twice (a bitmap: O(n))
+inline int snap_glist_check(const uint32_t *groups, uint32_t n, uint32_t G, const char *what) {
+    if (n == 0 || n > G) return fail(SMR_ERR_ARG, std::string(what) + "a list of " + std::to_string(n) + " groups for " + std::to_string(G));
+    std::vector<uint64_t> seen(((size_t)G + 63) / 64, 0ull);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t g = groups[i];
+        if (g >= G) return fail(SMR_ERR_ARG, std::string(what) + "list entry " + std::to_string(i) + " is group " + std::to_string(g) + " of " + std::to_string(G));
+        if ((seen[g >> 6] >> (g & 63u)) & 1ull) return fail(SMR_ERR_ARG, std::string(what) + "group " + std::to_string(g) + " is listed twice");
+        seen[g >> 6] |= 1ull << (g & 63u);
+    }
+    return SMR_OK;
+}
+// The list in front of the kernel, on its stream.  The caller's array is pageable memory, which the runtime has read (staged)
+// by the time the copy call returns: the caller may reuse it at once, and the next call may overwrite the device buffer, in
+// stream order
+inline int snap_glist_upload(SnapGroupListBuf &b, const uint32_t *groups, uint32_t n, hipStream_t st, const char *what) {
+    if (int rc = snap_glist_room(b, n, what)) return rc;
+    SMR_HIP_TRY(hipMemcpyAsync(b.dev, groups, (size_t)n * 4, hipMemcpyHostToDevice, st));
     return SMR_OK;
 }
 

@@ -22,6 +22,14 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def _group_list(groups):
+    return np.ascontiguousarray(np.asarray(groups, dtype=np.int64).astype(np.uint32))
+
+
+def _handles(xs):
+    return (C.c_void_p * len(xs))(*[x._h for x in xs])
+
+
 class RaftSnapshot(DeviceSnapshot):
     """One replica object's state between two handler calls, held on the device (`smr_raft_snapshot`): what
     `RaftLeaderGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
@@ -29,6 +37,17 @@ class RaftSnapshot(DeviceSnapshot):
     made for; its window does not matter).  `info()`: bytes, n_entries, n_reconstructs, n_groups, max_live, max_reconstructs,
     population, replica_id, commit_extra, craft, fault_tolerance, repeat_threshold"""
     _STEM, _INFO = "smr_raft_snapshot", _lib.RaftSnapshotInfo
+
+    def __init__(self, like, n_groups=None):
+        """room for the worst case of `like`; n_groups: for that many of its groups only (`smr_raft_snapshot_create_groups`:
+        what `save_groups` fills and `load_groups` takes -- the image of an n_groups replica)"""
+        if n_groups is None:
+            super().__init__(like)
+            return
+        self._L = _lib.load()
+        h = C.c_void_p()
+        check(self._L.smr_raft_snapshot_create_groups(like._h, int(n_groups), C.byref(h)))
+        self._h = h
 
 
 def save_cluster_state(reps, snaps=None, stream=None):
@@ -52,6 +71,44 @@ def load_cluster_state(reps, snaps, stream=None):
     L = _lib.load()
     check(L.smr_raft_cluster_load_state(n, (C.c_void_p * n)(*[r._h for r in reps]), (C.c_void_p * len(snaps))(*[s._h for s in snaps]),
                                         stream_ptr(stream)))
+
+
+def save_cluster_groups(reps, groups, snaps=None, stream=None):
+    """`reps[k].save_groups(groups, snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch, one list for all of
+    them (`smr_raft_cluster_save_groups`); returns the snapshots (new ones without `snaps`)"""
+    g = _group_list(groups)
+    snaps = [RaftSnapshot(r, len(g)) for r in reps] if snaps is None else list(snaps)
+    if len(snaps) != len(reps):
+        raise ValueError("save_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_raft_cluster_save_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), _handles(snaps), stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_groups(reps, snaps, groups, stream=None):
+    """`reps[k].load_groups(snaps[k], groups)` for up to 8 replicas of one co-located cluster in ONE launch
+    (`smr_raft_cluster_load_groups`)"""
+    g = _group_list(groups)
+    if len(snaps) != len(reps):
+        raise ValueError("load_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_raft_cluster_load_groups(len(reps), _handles(reps), _handles(snaps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+
+def reset_cluster_groups(reps, groups, stream=None):
+    """`reps[k].reset_groups(groups)` for up to 8 replicas of one co-located cluster in ONE launch (`smr_raft_cluster_reset_groups`)"""
+    g = _group_list(groups)
+    check(_lib.load().smr_raft_cluster_reset_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+
+def move_groups(src_reps, src_groups, dst_reps, dst_groups, snaps=None, reset=True):
+    """groups src_groups[i] of the replica objects `src_reps` become groups dst_groups[i] of `dst_reps` (replica k to replica k,
+    between two handler calls of both): one cluster save, one cluster load, and the source's slots back to what a new object
+    holds.  The counters stay where the events happened.  Returns the snapshots, for the next move of as many groups.  Which job
+    group sits in which slot is the caller's table"""
+    snaps = save_cluster_groups(src_reps, src_groups, snaps)
+    load_cluster_groups(dst_reps, snaps, dst_groups)
+    if reset:
+        reset_cluster_groups(src_reps, src_groups)
+    return snaps
 
 
 class RaftLeaderGroup:
@@ -192,6 +249,25 @@ class RaftLeaderGroup:
         """overwrite my whole logical state with a snapshot's (`smr_raft_load_state`): same n_groups, population, replica id,
         commit_extra and variant; window at least the snapshot's max_live"""
         check(self._L.smr_raft_load_state(self._h, snap._h, stream_ptr(stream)))
+
+    def save_groups(self, groups, snap=None, stream=None):
+        """the listed groups' state as the image of a len(groups) replica, group i of it = groups[i] (`smr_raft_save_groups`);
+        the counters stay here"""
+        g = _group_list(groups)
+        snap = RaftSnapshot(self, len(g)) if snap is None else snap
+        check(self._L.smr_raft_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
+        return snap
+
+    def load_groups(self, snap, groups, stream=None):
+        """group i of a len(groups) image overwrites group groups[i]; every other group and the counters are left alone
+        (`smr_raft_load_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_raft_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+    def reset_groups(self, groups, stream=None):
+        """the listed groups back to what a new replica object holds (`smr_raft_reset_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_raft_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
 
     def debug_arena_view(self):
         """debug / measurement only: [(device pointer, bytes)] of the allocations that hold my arrays -- the arena and, for a CRaft
