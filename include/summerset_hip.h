@@ -1294,6 +1294,53 @@ int64_t smr_rsp_snapshot_export(const smr_rsp_snapshot *s, uint8_t *host, uint64
 int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t len);
 int smr_rsp_cluster_save_state(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, void *stream);
 int smr_rsp_cluster_load_state(uint32_t n, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *snaps, void *stream);
+
+/* ---- chosen groups between replica objects, on the device --------------------------------------------------------------------
+ * The contract smr_mp_snapshot_create_groups and smr_raft_snapshot_create_groups settled, for an RSPaxos replica object.  No new
+ * format: an image of "these n groups, in this order" is the version-1 "SRPS" image of an n-group replica (what
+ * rspaxos/snapshot.rs and rspaxos/recovery.rs hold for those groups plus the volatile state of
+ * summerset_server/src/main.rs:124-167), group i of the image being group groups_host[i] of the replica; it interchanges both
+ * ways with smr_rsp_save_state / smr_rsp_load_state images of an n-group replica object, byte for byte where the content is equal.
+ *   smr_rsp_snapshot_create_groups  a snapshot object for n groups of a replica like `like`: its population, replica id and
+ *                            fault_tolerance, worst-case room for n groups at its window (growing by host-known sizes as
+ *                            above).  info, export and import work on it unchanged; import checks against n_groups = n;
+ *   smr_rsp_save_groups      one kernel on `stream`; enqueues only, apart from handing the list to the device (an async copy
+ *                            on `stream` into a buffer the snapshot owns).  Every per-group scalar and peer row, the live
+ *                            instances' records and the unpolled execution list (xn, xq: per-group rows, so unlike MultiPaxos'
+ *                            shared commit list they travel, and the target hands them to smr_rsp_exec_poll) of the listed
+ *                            groups, exactly as smr_rsp_save_state writes them; record order, tiles (64 list entries),
+ *                            max_live / max_exec and the header's totals taken over list positions.  The replica is not
+ *                            modified;
+ *   smr_rsp_load_groups      the inverse: group i of an n-group image overwrites the whole logical state of group
+ *                            groups_host[i]; nothing of any other group changes.  The image may come from
+ *                            smr_rsp_save_groups or be an ordinary smr_rsp_save_state image of an n-group replica.
+ *                            Synchronises once per save to read the image's header;
+ *   smr_rsp_reset_groups     the listed groups back to exactly what smr_rsp_replica_create leaves for a group (no leader
+ *                            known, zeros, null value ids over all `window` ring rows) -- not what smr_rsp_preset_leader
+ *                            leaves;
+ *   smr_rsp_cluster_save_groups / _load_groups / _reset_groups   a group lives in R replica objects: n_reps <= 8 distinct
+ *                            replicas of one device that share n_groups / population, ONE list for all of them, each replica
+ *                            with its own snapshot, in ONE launch -- exactly what the n_reps single calls give.
+ * What does not travel: the four counters.  Events stay counted where they happened, so the sum over replica objects is
+ * conserved: a group image holds zero counters, smr_rsp_load_groups ignores an image's counters and leaves the target's alone.
+ * The shard bytes of a moved group travel with smr_rsp_pstore_save_groups / _load_groups below, which a move must pair with
+ * these calls: the store follows the engine's masks.  Which job group sits in which slot is the host's table.
+ * The list is a host array (a move is a rare host decision), checked before anything is launched: n in 1 .. n_groups, every id
+ * below n_groups, none twice; for save and load n is the snapshot's n_groups.  SMR_ERR_ARG for these, for a null argument,
+ * another population / replica id / fault_tolerance, another window (there is no ring_lo beside len, as for
+ * smr_rsp_load_state), a replica or snapshot listed twice in a cluster form; SMR_ERR_STATE for an empty snapshot.  A refused
+ * call leaves replica and snapshot untouched.
+ * The list's device buffer belongs to the snapshot object (a cluster form uses snaps[0]'s for all replicas; a reset the
+ * replica's, reps[0]'s), and smr_rsp_load_groups writes it although its snapshot argument is const: calls that use one
+ * snapshot (one replica, for resets) with different lists must be on one stream or ordered by the caller -- two of them on
+ * different streams race on that buffer.  The same holds for smr_mp_*_groups, smr_raft_*_groups and the store calls below. */
+int smr_rsp_snapshot_create_groups(const smr_rsp_replica *like, uint32_t n, smr_rsp_snapshot **out);
+int smr_rsp_save_groups(smr_rsp_replica *e, const uint32_t *groups_host, uint32_t n, smr_rsp_snapshot *s, void *stream);
+int smr_rsp_load_groups(smr_rsp_replica *e, const smr_rsp_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_rsp_reset_groups(smr_rsp_replica *e, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_rsp_cluster_save_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const uint32_t *groups_host, uint32_t n, smr_rsp_snapshot *const *snaps, void *stream);
+int smr_rsp_cluster_load_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *snaps, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_rsp_cluster_reset_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const uint32_t *groups_host, uint32_t n, void *stream);
 /* debug / measurement only: the device allocation that holds the replica's arrays (ring rows dead or alive, counter shards), i.e.
  * what a wholesale copy of the replica's state would move -- tools/time_rsp_snapshot.py times that copy beside
  * smr_rsp_save_state.  The layout inside is the library's own; nothing else may depend on it. */
@@ -1436,6 +1483,35 @@ int smr_rsp_pstore_load(smr_rsp_pstore *s, const smr_rsp_pstore_snapshot *snap, 
 int smr_rsp_pstore_snapshot_info_get(const smr_rsp_pstore_snapshot *s, smr_rsp_pstore_snapshot_info *out);
 int64_t smr_rsp_pstore_snapshot_export(const smr_rsp_pstore_snapshot *s, uint8_t *host, uint64_t cap);
 int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *host, uint64_t len);
+
+/* ---- chosen groups between stores, shard bytes included (both kinds of store) ---------------------------------------------------
+ * The store's half of a group move: a moved RSPaxos group is useless without its bytes (the store follows the engine's masks),
+ * and a moved CRaft group whose rows arrive with it needs no refill by follow / Reconstruct.  The same contract: an image of
+ * "these n groups, in this order" is the version-1 "SRPB" image of an n-group store, image cell row * n + i being store cell
+ * row * n_groups + groups_host[i]; it interchanges both ways with smr_rsp_pstore_save / _load images of an n-group store.
+ *   smr_rsp_pstore_snapshot_create_groups  a snapshot object for n groups of a store like `like`: its window, scheme, plane
+ *                            count and kind, room for the worst case of n groups (every cell holding every shard at `like`'s
+ *                            max_data_len; grows by host-known sizes).  info, export and import work on it unchanged;
+ *   smr_rsp_pstore_save_groups   two launches on `stream`, enqueues only (the list goes to the device by an async copy on
+ *                            `stream` into a buffer the snapshot owns): the listed groups' cell headers of every plane, the
+ *                            alias bytes, and the bytes of every shard that is present and not an alias, gathered into the
+ *                            dense image with 16-byte loads and stores; the byte launch is as long as the list, not the store;
+ *   smr_rsp_pstore_load_groups   the inverse.  For a listed group all planes x window cell headers and alias bytes are
+ *                            rewritten (a null image cell becomes a null cell) and the stored shards' bytes written, each up
+ *                            to its length; bytes behind a shard's length, and everything of every other group, stay;
+ *   smr_rsp_pstore_reset_groups  the listed groups' cells back to what smr_rsp_pstore_create / smr_craft_pstore_create leave:
+ *                            token null, length 0, no shards, no alias.  Row bytes are not touched.
+ * What does not travel: the five counters (a group image holds zeros; a load through a list leaves the target's alone), and what
+ * is not state (the work list, dlv, the GF table, row bytes behind a shard's length).
+ * The list is checked as above before anything is launched.  SMR_ERR_ARG for a bad list, a null argument, a snapshot made for
+ * another n, another window / n_shards / n_data_shards / plane count / kind, a max_dlen above the target's max_data_len;
+ * SMR_ERR_STATE for an empty snapshot.  A refused call leaves store and snapshot untouched.
+ * The list's device buffer is the snapshot object's (a reset: the store's); smr_rsp_pstore_load_groups writes it although its
+ * snapshot argument is const, so loads of one snapshot through different lists belong on one stream, as above. */
+int smr_rsp_pstore_snapshot_create_groups(const smr_rsp_pstore *like, uint32_t n, smr_rsp_pstore_snapshot **out);
+int smr_rsp_pstore_save_groups(smr_rsp_pstore *s, const uint32_t *groups_host, uint32_t n, smr_rsp_pstore_snapshot *snap, void *stream);
+int smr_rsp_pstore_load_groups(smr_rsp_pstore *s, const smr_rsp_pstore_snapshot *snap, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_rsp_pstore_reset_groups(smr_rsp_pstore *s, const uint32_t *groups_host, uint32_t n, void *stream);
 /* debug / measurement only: the store's three device allocations (headers and lists, REQS plane, VOTED plane -- 0 bytes for a
  * CRaft store), i.e. what a wholesale copy of the store would move -- tools/time_rsp_snapshot.py times those copies beside
  * smr_rsp_pstore_save.  The layout inside is the library's own; nothing else may depend on it. */

@@ -17,6 +17,7 @@ from .raft import move_groups as move_raft_groups  # noqa: F401
 from .epaxos import EPaxosReplicaGroup, EPaxosSnapshot  # noqa: F401
 from .rspaxos import RSPaxosReplicaGroup, RSPaxosSnapshot  # noqa: F401
 from .rsp_payload import CRaftPayloadStore, PayloadStoreSnapshot, RSPaxosPayloadStore, RSPaxosReplicaWithPayload  # noqa: F401
+from .rsp_payload import move_craft_groups, move_rsp_groups, move_store_groups  # noqa: F401
 from .repnothing import RepNothingReplica  # noqa: F401
 from .heartbeater import Heartbeater  # noqa: F401
 from .leaseman import LeaseManager  # noqa: F401

@@ -422,6 +422,13 @@ SYMBOLS = [
     ("smr_rsp_snapshot_import", _i, [_vp, _vp, _u64]),
     ("smr_rsp_cluster_save_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("smr_rsp_cluster_load_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_rsp_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_rsp_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_rsp_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_rsp_reset_groups", _i, [_vp, _vp, _u32, _vp]),
+    ("smr_rsp_cluster_save_groups", _i, [_u32, C.POINTER(_vp), _vp, _u32, C.POINTER(_vp), _vp]),
+    ("smr_rsp_cluster_load_groups", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp, _u32, _vp]),
+    ("smr_rsp_cluster_reset_groups", _i, [_u32, C.POINTER(_vp), _vp, _u32, _vp]),
     ("smr_rsp_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_rsp_pstore_create", _i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("smr_rsp_pstore_destroy", None, [_vp]),
@@ -446,6 +453,10 @@ SYMBOLS = [
     ("smr_rsp_pstore_snapshot_info_get", _i, [_vp, C.POINTER(PstoreSnapshotInfo)]),
     ("smr_rsp_pstore_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
     ("smr_rsp_pstore_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_rsp_pstore_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_rsp_pstore_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_rsp_pstore_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_rsp_pstore_reset_groups", _i, [_vp, _vp, _u32, _vp]),
     ("smr_rsp_pstore_debug_allocs", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_craft_pstore_create", _i, [_u32, _u32, _u32, _u32, _u32, C.POINTER(_vp)]),
     ("smr_craft_pstore_put", _i, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp]),

@@ -19,6 +19,9 @@
 //                                                    padded to a multiple of 16 (the pad is written as zeros, never copied from
 //                                                    the row).  An aliased shard's bytes are carried once, in the REQS cell.
 // The image is dense: the device buffer holds exactly the exported bytes.
+// Chosen groups (smr_rsp_pstore_save_groups / _load_groups / _reset_groups) go through the same image and the same bodies: an
+// image of "these n groups, in this order" is the image of an n-group store, read and written through a group list
+// (PsSnapGroupList below): image cell row * n + j is store cell row * G + list[j].  A group image holds zero counters.
 #pragma once
 #include "snapshot_common.h"
 
@@ -68,6 +71,30 @@ SMR_HD PsSnapGeom pssnap_geom(uint32_t G, uint32_t W, uint32_t planes) {
     return q;
 }
 
+// ---- what a new store holds for a group ---------------------------------------------------------------------------------
+// The one place that says it: ps_create fills its arrays from here, and smr_rsp_pstore_reset_groups (the unpack of nothing,
+// below) returns a listed group's cells to the same values -- every cell's token null, length 0, no shards, no alias.  Row bytes
+// are not state where no shard is present and are not touched.
+constexpr uint8_t PS_INIT_TOK_BYTE = 0xFF;                   // create fills bytes
+constexpr uint32_t PS_INIT_TOK = 0x01010101u * PS_INIT_TOK_BYTE, PS_INIT_WORD = 0;
+static_assert(PS_INIT_TOK == PS_NULL && PS_INIT_WORD == 0, "a new cell is a null cell");
+
+// ---- which group of the store an image position holds -------------------------------------------------------------------
+// An image has its own group index (position x, stride A.geo.G = its n_groups) and the store has its own (group g, stride
+// A.v.G).  For a whole-store image they are one and the same; an image of "these n groups, in this order" is the image of an
+// n-group store whose group x is group list[x] of this one: the same format, tiles, bases, lane prefix and cell_off run over list
+// positions, and the store side is a gather or scatter.  The bodies below take the map as a parameter; with PsSnapAllGroups they
+// are what they were.  WHOLE = false: the five counters do not travel (zero in the image, the target's left alone).
+struct PsSnapAllGroups {
+    static constexpr bool WHOLE = true;
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
+};
+struct PsSnapGroupList {
+    static constexpr bool WHOLE = false;
+    const uint32_t *__restrict__ list;                           // [n], every entry < v.G, none twice (the host has checked)
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
+};
+
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // Two launches each way, no host read-back between them.
 //   (1) ps_snap_head: snapshot_common.h's tiles and bases, summing the groups' byte totals; inside a tile, per
@@ -79,14 +106,14 @@ SMR_HD PsSnapGeom pssnap_geom(uint32_t G, uint32_t W, uint32_t planes) {
 struct PsSnapArgs {
     PsView v;
     uint8_t *img;
-    uint64_t *cell_off;      // [planes][W][G]
+    uint64_t *cell_off;      // [planes][W][geo.G]: image geometry
     uint64_t cap_bytes;      // room of the shard section
     uint32_t craft;
-    PsSnapGeom geo;
+    PsSnapGeom geo;          // of the image: geo.G = v.G for a whole store, the list's length for chosen groups
 };
 
 struct PsSnapCell { uint32_t tok, dlen, avail, alias; };
-// cell i of plane P: the store's own, canonical (PACK), or the image's
+// a cell of plane P: the store's own at i = row * v.G + g, canonical (PACK), or the image's at i = row * geo.G + x
 template <bool PACK, int P>
 __device__ __forceinline__ PsSnapCell pssnap_cell(const PsSnapArgs &A, size_t i) {
     PsSnapCell c;
@@ -106,10 +133,11 @@ __device__ __forceinline__ PsSnapCell pssnap_cell(const PsSnapArgs &A, size_t i)
 // what the launch sums over groups: the shard bytes (a cell's offset), and for a save's header the cells with a token, the shards
 // stored and (mx[]) the longest payload; a load has those in the image and sums the bytes alone
 enum { PS_BYTES = 0, PS_CELLS = 1, PS_SHARDS = 2 };
+// (g, G: the group and stride of the side that is read -- the store's for PACK, the image's otherwise)
 template <bool PACK, int P>
-__device__ __forceinline__ void pssnap_add_group(const PsSnapArgs &A, uint32_t g, uint64_t (&sum)[PACK ? 3 : 1], uint32_t (&mx)[1]) {
+__device__ __forceinline__ void pssnap_add_group(const PsSnapArgs &A, uint32_t g, size_t G, uint64_t (&sum)[PACK ? 3 : 1], uint32_t (&mx)[1]) {
     for (uint32_t r = 0; r < A.geo.W; r++) {
-        const PsSnapCell c = pssnap_cell<PACK, P>(A, (size_t)r * A.geo.G + g);
+        const PsSnapCell c = pssnap_cell<PACK, P>(A, (size_t)r * G + g);
         const uint32_t st = pssnap_stored(c.avail, c.alias);
         sum[PS_BYTES] += pssnap_cell_bytes(st, c.dlen, A.v.d);
         if constexpr (PACK) {
@@ -119,22 +147,31 @@ __device__ __forceinline__ void pssnap_add_group(const PsSnapArgs &A, uint32_t g
     }
 }
 
-// one (plane, row) of a tile: the headers across, the cells' offsets from a prefix over the lanes
-template <bool PACK, int P>
-__device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r, uint32_t g, bool in, uint32_t lane, uint64_t &run_bytes, uint64_t (&mine)[3], uint32_t (&mine_mx)[1]) {
+// one (plane, row) of a tile: the headers across, the cells' offsets from a prefix over the lanes.  xi: the lane's position in the
+// image, g: its group in the store.  FRESH (unpack only): no image is read, the cell becomes what ps_create leaves
+template <bool PACK, int P, bool FRESH = false>
+__device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r, uint32_t xi, uint32_t g, bool in, uint32_t lane, uint64_t &run_bytes, uint64_t (&mine)[3], uint32_t (&mine_mx)[1]) {
     const PsSnapGeom &Q = A.geo;
-    const size_t i = (size_t)r * Q.G + (in ? g : 0u);
+    const size_t i = (size_t)r * Q.G + (in ? xi : 0u), si = (size_t)r * A.v.G + g;
+    if constexpr (FRESH) {
+        if (in) {
+            const PsPlane &pl = A.v.pl[P];
+            pl.tok[si] = PS_INIT_TOK; pl.dlen[si] = PS_INIT_WORD; pl.avail[si] = (uint8_t)PS_INIT_WORD;
+            if (P == 1 && pl.alias) pl.alias[si] = (uint8_t)PS_INIT_WORD;
+        }
+        return;
+    }
     uint64_t c = 0;
     if (in) {
-        const PsSnapCell x = pssnap_cell<PACK, P>(A, i);
+        const PsSnapCell x = pssnap_cell<PACK, P>(A, PACK ? si : i);
         if (PACK) {
             ((uint32_t *)(A.img + Q.o_tok[P]))[i] = x.tok; ((uint32_t *)(A.img + Q.o_dlen[P]))[i] = x.dlen;
             A.img[Q.o_avail[P] + i] = (uint8_t)x.avail;
             if (P == 1) A.img[Q.o_alias + i] = (uint8_t)x.alias;
         } else {
             const PsPlane &pl = A.v.pl[P];
-            pl.tok[i] = x.tok; pl.dlen[i] = x.dlen; pl.avail[i] = (uint8_t)x.avail;
-            if (P == 1 && pl.alias) pl.alias[i] = (uint8_t)x.alias;
+            pl.tok[si] = x.tok; pl.dlen[si] = x.dlen; pl.avail[si] = (uint8_t)x.avail;
+            if (P == 1 && pl.alias) pl.alias[si] = (uint8_t)x.alias;
         }
         const uint32_t st = pssnap_stored(x.avail, x.alias);
         c = pssnap_cell_bytes(st, x.dlen, A.v.d);
@@ -148,33 +185,40 @@ __device__ __forceinline__ void pssnap_head_row(const PsSnapArgs &A, uint32_t r,
         const uint64_t y = __shfl(incl, (int)(lane >= off ? lane - off : lane));
         if (lane >= off) incl += y;
     }
-    if (in) A.cell_off[((size_t)P * Q.W + r) * Q.G + g] = run_bytes + (incl - c);
+    if (in) A.cell_off[((size_t)P * Q.W + r) * Q.G + xi] = run_bytes + (incl - c);
     run_bytes += __shfl(incl, 63);
 }
 
-template <bool PACK>
-__global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) {
+// the head launch of a whole store (ps_snap_head) or of the listed groups (ps_snap_head_groups); tiles are 64 image positions
+template <bool PACK, class Map, bool FRESH = false>
+__device__ __forceinline__ void pssnap_head_all(const PsSnapArgs &A, const Map &M) {
     const PsSnapGeom &Q = A.geo;
     const PsView &v = A.v;
     const SnapWave w = snap_wave(Q.tiles, Q.G);
     constexpr int NS = PACK ? 3 : 1;
     uint64_t run[NS], mine[3] = {0, 0, 0};                       // in front of this wavefront's tiles; inside them (bytes: in run)
     uint32_t run_mx[1], mine_mx[1] = {0};
-    snap_bases(
-        [&](uint32_t g, uint64_t (&add)[NS], uint32_t (&m)[1]) {
-            pssnap_add_group<PACK, 0>(A, g, add, m);
-            if (A.geo.planes == 2) pssnap_add_group<PACK, 1>(A, g, add, m);
-        },
-        w.gb0, w.gw0, run, run_mx);
+    if constexpr (FRESH) run[PS_BYTES] = 0;
+    else
+        snap_bases(
+            [&](uint32_t x, uint64_t (&add)[NS], uint32_t (&m)[1]) {
+                const uint32_t g = PACK ? M.group(x, true) : x;
+                const size_t G = PACK ? v.G : Q.G;
+                pssnap_add_group<PACK, 0>(A, g, G, add, m);
+                if (A.geo.planes == 2) pssnap_add_group<PACK, 1>(A, g, G, add, m);
+            },
+            w.gb0, w.gw0, run, run_mx);
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
-        const bool in = g < Q.G;
-        for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 0>(A, r, g, in, w.lane, run[PS_BYTES], mine, mine_mx);
+        const uint32_t x = t * 64 + w.lane;
+        const bool in = x < Q.G;
+        const uint32_t g = M.group(x, in);
+        for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 0, FRESH>(A, r, x, g, in, w.lane, run[PS_BYTES], mine, mine_mx);
         if (Q.planes == 2)
-            for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 1>(A, r, g, in, w.lane, run[PS_BYTES], mine, mine_mx);
+            for (uint32_t r = 0; r < Q.W; r++) pssnap_head_row<PACK, 1, FRESH>(A, r, x, g, in, w.lane, run[PS_BYTES], mine, mine_mx);
     }
     if constexpr (PACK) {
-        snap_counters_save<5>(v.counters, (uint64_t *)(A.img + Q.off_ctr));
+        if (Map::WHOLE) snap_counters_save<5>(v.counters, (uint64_t *)(A.img + Q.off_ctr));
+        else if (blockIdx.x == 0 && threadIdx.x < 5) ((uint64_t *)(A.img + Q.off_ctr))[threadIdx.x] = 0;   // a group image carries no counters
         if (w.last) {                                            // the wavefront of the last tile knows the totals
             const uint64_t cells = run[PS_CELLS] + snap_wave_sum(mine[PS_CELLS]), shards = run[PS_SHARDS] + snap_wave_sum(mine[PS_SHARDS]);
             const uint32_t mdl = snap_wave_max(mine_mx[0]);
@@ -193,16 +237,27 @@ __global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) {
                 for (uint64_t b = Q.hdr_end; b < Q.fixed; b++) A.img[b] = 0;     // (up to the shard section's multiple of 16)
             }
         }
-    } else {
+    } else if (Map::WHOLE) {
         snap_counters_load<5>((const uint64_t *)(A.img + Q.off_ctr), v.counters);
     }
+}
+template <bool PACK>
+__global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) { pssnap_head_all<PACK>(A, PsSnapAllGroups{}); }
+// group x of the image (A.geo.G = n groups) <-> group list[x] of the store; fresh (a load only): no image, the listed groups'
+// cells as a new store holds them (A carries the geometry of n groups and no buffers)
+template <bool PACK>
+__global__ __launch_bounds__(256) void ps_snap_head_groups(const PsSnapArgs A, const uint32_t *list, int fresh) {
+    if constexpr (PACK) pssnap_head_all<true>(A, PsSnapGroupList{list});
+    else if (fresh) pssnap_head_all<false, PsSnapGroupList, true>(A, PsSnapGroupList{list});
+    else pssnap_head_all<false>(A, PsSnapGroupList{list});
 }
 
 // the low nb bytes of a word, the rest zero
 __device__ __forceinline__ uint32_t pssnap_keep(uint32_t w, uint32_t nb) { return nb >= 4u ? w : (nb ? (w & ((1u << (8u * nb)) - 1u)) : 0u); }
 
-template <bool PACK>
-__global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) {
+// the byte launch: the image's (plane, cell, shard) items, so chosen groups cost a launch of their own length
+template <bool PACK, class Map>
+__device__ __forceinline__ void pssnap_bytes_all(const PsSnapArgs &A, const Map &M) {
     const PsSnapGeom &Q = A.geo;
     const PsView &v = A.v;
     const uint32_t lane = threadIdx.x & 63u;
@@ -221,8 +276,8 @@ __global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) {
         const uint32_t sl = pssnap_shard_len(dlen, v.d), sl16 = (uint32_t)snap_a16(sl);
         const uint64_t off = A.cell_off[ci64] + (uint64_t)__popc(stored & ((1u << k) - 1u)) * sl16;
         if (sl16 > v.cap_sl || off + sl16 > A.cap_bytes) continue;                    // (refused by the host / cannot happen)
-        const uint32_t row = (uint32_t)(i / Q.G), g = (uint32_t)(i - (size_t)row * Q.G);
-        const size_t ro = ps_off(v, row, k, g);
+        const uint32_t row = (uint32_t)(i / Q.G), g = M.group((uint32_t)(i - (size_t)row * Q.G), true);   // (the item is the wavefront's: a uniform load)
+        const size_t ro = ps_off(v, row, k, g);                  // 64-bit, in the store's geometry
         uint8_t *const ip = A.img + Q.fixed + off;
         for (uint32_t c0 = lane * 16u; c0 < sl16; c0 += 1024u) {
             if (PACK) {
@@ -245,5 +300,9 @@ __global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) {
         }
     }
 }
+template <bool PACK>
+__global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) { pssnap_bytes_all<PACK>(A, PsSnapAllGroups{}); }
+template <bool PACK>
+__global__ __launch_bounds__(256) void ps_snap_bytes_groups(const PsSnapArgs A, const uint32_t *list) { pssnap_bytes_all<PACK>(A, PsSnapGroupList{list}); }
 
 }  // namespace smr

@@ -645,6 +645,8 @@ struct smr_rsp_replica {
     smr_rsp_cfg cfg;
     RspView v;
     Arena arena;
+    int device = -1;
+    SnapGroupListBuf glist;          // smr_rsp_reset_groups' list on the device
 };
 
 namespace smr {
@@ -697,10 +699,12 @@ int smr_rsp_replica_create(const smr_rsp_cfg *cfg, smr_rsp_replica **out) {
     RspView &v = e->v;
     v.G = cfg->n_groups; v.W = cfg->window; v.Wmask = cfg->window - 1; v.R = cfg->population; v.me = cfg->me;
     v.majority = majority; v.ft = cfg->fault_tolerance;
-    err = hipMemset(e->arena.base, 0, e->arena.size);
-    if (err == hipSuccess) err = hipMemset(v.leader, 0xFF, v.G);
-    if (err == hipSuccess) err = hipMemset(v.s_val, 0xFF, (size_t)v.W * v.G * 4);
-    if (err == hipSuccess) err = hipMemset(v.s_vval, 0xFF, (size_t)v.W * v.G * 4);
+    // a group's initial values are rsp_snapshot.h's RSP_INIT_* (shared with smr_rsp_reset_groups)
+    err = hipMemset(e->arena.base, (int)RSP_INIT_WORD, e->arena.size);
+    if (err == hipSuccess) err = hipMemset(v.leader, RSP_INIT_LEADER, v.G);
+    if (err == hipSuccess) err = hipMemset(v.s_val, RSP_INIT_VAL_BYTE, (size_t)v.W * v.G * 4);
+    if (err == hipSuccess) err = hipMemset(v.s_vval, RSP_INIT_VAL_BYTE, (size_t)v.W * v.G * 4);
+    if (err == hipSuccess) err = hipGetDevice(&e->device);
     if (err != hipSuccess) {
         (void)hipFree(e->arena.base); delete e;
         return fail(SMR_ERR_DEVICE, std::string("rspaxos: init: ") + hipGetErrorString(err));
@@ -712,6 +716,7 @@ int smr_rsp_replica_create(const smr_rsp_cfg *cfg, smr_rsp_replica **out) {
 void smr_rsp_replica_destroy(smr_rsp_replica *e) {
     if (!e) return;
     if (e->arena.base) (void)hipFree(e->arena.base);
+    snap_glist_free(e->glist);
     delete e;
 }
 
@@ -947,6 +952,7 @@ struct smr_rsp_snapshot {
     SnapBuf buf;
     uint64_t cap_s = 0, cap_x = 0;                               // records the device buffer's sections have room for
     RspSnapHdr hdr;                                              // the image's header, once buf.hdr_known
+    SnapGroupListBuf glist;                                      // smr_rsp_save_groups / smr_rsp_load_groups: the list on the device
 };
 
 namespace smr {
@@ -976,9 +982,11 @@ static int rspsnap_copy(const smr_rsp_snapshot *s, uint8_t *host, const RspSnapH
     return snap_copy_sections(s->buf.dev, host, q.fixed, to_host, {{q.fixed, h.n_slots * sizeof(RspSnapSlot), h.n_slots * sizeof(RspSnapSlot)},
                                                                   {rspsnap_off_exec(q, rspsnap_img(s)), h.n_exec * 4, snap_a8(h.n_exec * 4)}});
 }
-static bool rspsnap_like(const smr_rsp_snapshot *s, const smr_rsp_replica *e) {
-    return s->G == e->cfg.n_groups && s->R == e->cfg.population && s->me == e->cfg.me && s->ft == e->cfg.fault_tolerance;
+// made for a replica like e, whatever its n_groups (a snapshot of chosen groups has its own)
+static bool rspsnap_like_kind(const smr_rsp_snapshot *s, const smr_rsp_replica *e) {
+    return s->R == e->cfg.population && s->me == e->cfg.me && s->ft == e->cfg.fault_tolerance;
 }
+static bool rspsnap_like(const smr_rsp_snapshot *s, const smr_rsp_replica *e) { return s->G == e->cfg.n_groups && rspsnap_like_kind(s, e); }
 static bool rspsnap_hdr_like(const RspSnapHdr &h, const smr_rsp_snapshot *s) {
     return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.fault_tolerance == s->ft;
 }
@@ -1009,24 +1017,135 @@ static int rspsnap_setup(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snaps
     for (uint32_t k = 0; k < n; k++) { A.v[k] = reps[k]->v; A.img[k] = snaps[k]->buf.dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
     return SMR_OK;
 }
+
+// ---- chosen groups between replica objects (rsp_snapshot.h: the same image, the same bodies, through a group list) -----------
+static const char *const RSPGROUPS = "rspaxos groups: ";
+enum RspGroupsCall { RSPG_SAVE, RSPG_LOAD, RSPG_RESET };
+// the arguments of the one launch over n_reps replicas for the n listed groups (one list for all of them); every check before
+// anything is written, allocated or launched.  A reset has no snapshots
+static int rspgroups_setup(uint32_t n_reps, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, const uint32_t *groups, uint32_t n,
+                           RspGroupsCall call, RspSnapArgs &A) {
+    if (!groups) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
+    const auto replica = [&](uint32_t k) {
+        const smr_rsp_replica *e = reps[k];
+        if (e->v.G != reps[0]->v.G || e->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, "rspaxos groups: the replicas differ in groups / population");
+        if (e->device != reps[0]->device) return fail(SMR_ERR_ARG, "rspaxos groups: a replica lives on another device");
+        return (int)SMR_OK;
+    };
+    if (call == RSPG_RESET) {                                    // (no snapshots: the replicas stand in for them in the pairs' check)
+        if (int rc = snap_pairs_check(n_reps, reps, reps, RSPGROUPS, replica)) return rc;
+    } else if (int rc = snap_pairs_check(n_reps, reps, snaps, RSPGROUPS, [&](uint32_t k) {
+                   if (int rc2 = replica(k)) return rc2;
+                   const smr_rsp_snapshot *s = snaps[k];
+                   if (s->buf.device != reps[k]->device) return fail(SMR_ERR_ARG, "rspaxos groups: a snapshot lives on another device");
+                   if (!rspsnap_like_kind(s, reps[k])) return fail(SMR_ERR_ARG, "rspaxos groups: the snapshot was made for another population / replica id / fault_tolerance");
+                   if (s->G != n) return fail(SMR_ERR_ARG, "rspaxos groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
+                   return (int)SMR_OK;
+               })) return rc;
+    if (int rc = snap_glist_check(groups, n, reps[0]->v.G, RSPGROUPS)) return rc;
+    if (call == RSPG_LOAD)
+        for (uint32_t k = 0; k < n_reps; k++) {
+            smr_rsp_snapshot *s = snaps[k];
+            if (int rc = rspsnap_header(s)) return rc;
+            if (!rspsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string("rspaxos groups: the image is of ") + RSPSNAP_OTHER);
+            // there is no ring_lo beside len: a slot is held iff slot + W >= len, so the window must be the image's
+            if (s->hdr.window != reps[k]->cfg.window)
+                return fail(SMR_ERR_ARG, "rspaxos groups: an image of window " + std::to_string(s->hdr.window) + " does not load into window " +
+                                             std::to_string(reps[k]->cfg.window));
+        }
+    if (call == RSPG_SAVE)
+        for (uint32_t k = 0; k < n_reps; k++)
+            if (int rc = rspsnap_room(snaps[k], reps[k])) return rc;
+    memset(&A, 0, sizeof(A));
+    A.geo = rspsnap_geom(n, reps[0]->v.R);                       // the geometry of an n-group replica
+    for (uint32_t k = 0; k < n_reps; k++) {
+        A.v[k] = reps[k]->v;
+        if (call != RSPG_RESET) { A.img[k] = snaps[k]->buf.dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
+    }
+    return SMR_OK;
+}
 }  // namespace smr
 
 extern "C" {
 
-int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+// a snapshot object for n groups of a replica like `like` (n = its n_groups: the whole replica)
+static int rspsnap_create(const smr_rsp_replica *like, uint32_t n, smr_rsp_snapshot **out) {
     smr_rsp_snapshot *s = new smr_rsp_snapshot();
-    s->G = like->cfg.n_groups; s->R = like->cfg.population; s->me = like->cfg.me; s->ft = like->cfg.fault_tolerance;
+    s->G = n; s->R = like->cfg.population; s->me = like->cfg.me; s->ft = like->cfg.fault_tolerance;
+    s->buf.device = like->device;
     memset(&s->hdr, 0, sizeof(s->hdr));
     if (int rc = rspsnap_room(s, like)) { delete s; return rc; }
     *out = s;
     return SMR_OK;
 }
 
+int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
+    return rspsnap_create(like, like->cfg.n_groups, out);
+}
+
 void smr_rsp_snapshot_destroy(smr_rsp_snapshot *s) {
     if (!s) return;
     snap_buf_free(s->buf);
+    snap_glist_free(s->glist);
     delete s;
+}
+
+int smr_rsp_snapshot_create_groups(const smr_rsp_replica *like, uint32_t n, smr_rsp_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
+    if (n == 0 || n > like->cfg.n_groups)
+        return fail(SMR_ERR_ARG, "rspaxos groups: a snapshot of " + std::to_string(n) + " groups of a replica of " + std::to_string(like->cfg.n_groups));
+    smr_rsp_snapshot *s = nullptr;
+    if (int rc = rspsnap_create(like, n, &s)) return rc;
+    if (int rc = snap_glist_room(s->glist, n, RSPGROUPS)) { smr_rsp_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
+    *out = s;
+    return SMR_OK;
+}
+
+int smr_rsp_cluster_save_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const uint32_t *groups_host, uint32_t n, smr_rsp_snapshot *const *snaps,
+                                void *stream) {
+    RspSnapArgs A;
+    if (int rc = rspgroups_setup(n_reps, reps, snaps, groups_host, n, RSPG_SAVE, A)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RSPGROUPS)) return rc;
+    hipLaunchKernelGGL(rsp_snap_pack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)snaps[0]->glist.dev);
+    SMR_HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < n_reps; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    return SMR_OK;
+}
+
+int smr_rsp_cluster_load_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *csnaps, const uint32_t *groups_host, uint32_t n,
+                                void *stream) {
+    smr_rsp_snapshot *const *snaps = const_cast<smr_rsp_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
+    RspSnapArgs A;
+    if (int rc = rspgroups_setup(n_reps, reps, snaps, groups_host, n, RSPG_LOAD, A)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RSPGROUPS)) return rc;
+    hipLaunchKernelGGL(rsp_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)snaps[0]->glist.dev, 0);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_rsp_cluster_reset_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const uint32_t *groups_host, uint32_t n, void *stream) {
+    RspSnapArgs A;
+    if (int rc = rspgroups_setup(n_reps, reps, nullptr, groups_host, n, RSPG_RESET, A)) return rc;
+    if (int rc = snap_glist_upload(reps[0]->glist, groups_host, n, (hipStream_t)stream, RSPGROUPS)) return rc;
+    hipLaunchKernelGGL(rsp_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)reps[0]->glist.dev, 1);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_rsp_save_groups(smr_rsp_replica *e, const uint32_t *groups_host, uint32_t n, smr_rsp_snapshot *s, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
+    return smr_rsp_cluster_save_groups(1, &e, groups_host, n, &s, stream);
+}
+
+int smr_rsp_load_groups(smr_rsp_replica *e, const smr_rsp_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
+    return smr_rsp_cluster_load_groups(1, &e, &s, groups_host, n, stream);
+}
+
+int smr_rsp_reset_groups(smr_rsp_replica *e, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!e) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
+    return smr_rsp_cluster_reset_groups(1, &e, groups_host, n, stream);
 }
 
 int smr_rsp_cluster_save_state(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, void *stream) {

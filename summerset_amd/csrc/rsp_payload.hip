@@ -923,6 +923,7 @@ struct smr_rsp_pstore {
     void *plane_alloc[2];  // the planes' allocations (v.pl[p].bytes lies at their start)
     int planes;            // 2; 1 for a CRaft store (a log entry has one codeword: no VOTED bytes are allocated)
     bool craft_store;      // made by smr_craft_pstore_create
+    SnapGroupListBuf glist;   // smr_rsp_pstore_reset_groups' list on the device
 };
 
 extern "C" {
@@ -972,11 +973,12 @@ static int ps_create(uint32_t n_groups, uint32_t n_shards, uint32_t n_data_shard
     }
     if (err == hipSuccess) layout();
     for (int p = 0; p < 2 && err == hipSuccess; p++) v.pl[p].bytes = pa[p].at<uint8_t>(o_bytes[p]);
-    if (err == hipSuccess) err = hipMemset(a.base, 0, a.size);
+    // a cell's initial values are ps_snapshot.h's PS_INIT_* (shared with smr_rsp_pstore_reset_groups)
+    if (err == hipSuccess) err = hipMemset(a.base, (int)PS_INIT_WORD, a.size);
     for (int p = 0; p < 2 && err == hipSuccess; p++) {
         v.pl[p].tok = a.at<uint32_t>(o_tok[p]); v.pl[p].avail = a.at<uint8_t>(o_av[p]); v.pl[p].dlen = a.at<uint32_t>(o_len[p]);
         v.it_src[p] = a.at<uint64_t>(o_src[p]); v.it_sl[p] = a.at<uint32_t>(o_sl[p]);
-        err = hipMemset(v.pl[p].tok, 0xFF, cells * 4);
+        err = hipMemset(v.pl[p].tok, PS_INIT_TOK_BYTE, cells * 4);
         if (err == hipSuccess) err = hipMemset(v.pl[p].bytes, 0, p < planes ? s->plane_bytes : 256);
     }
     if (err == hipSuccess) err = hipMemcpy(a.base + o_mat, tab.data(), tab.size(), hipMemcpyHostToDevice);
@@ -1020,6 +1022,7 @@ void smr_rsp_pstore_destroy(smr_rsp_pstore *s) {
     if (!s) return;
     for (int p = 0; p < 2; p++) if (s->plane_alloc[p]) (void)hipFree(s->plane_alloc[p]);
     if (s->meta) (void)hipFree(s->meta);
+    snap_glist_free(s->glist);
     delete s;
 }
 
@@ -1458,6 +1461,7 @@ struct smr_rsp_pstore_snapshot {
     uint64_t *d_off = nullptr;                                   // [planes][W][G] where a cell's stored shards begin (scratch of the two launches)
     uint64_t cap_bytes = 0;                                      // room of the shard section
     PsSnapHdr hdr;                                               // the image's header, once buf.hdr_known
+    SnapGroupListBuf glist;                                      // smr_rsp_pstore_save_groups / _load_groups: the list on the device
 };
 
 namespace smr {
@@ -1467,10 +1471,11 @@ static int pssnap_alloc(smr_rsp_pstore_snapshot *s, uint64_t cap_bytes) {
     s->cap_bytes = cap_bytes;
     return snap_buf_alloc(s->buf, pssnap_geom_of(s).fixed + cap_bytes + 16, PSSNAP);
 }
-// room for the worst case of store `st`: every cell holding every shard at max_data_len -- the planes' own size.  A save can then
-// never find the snapshot too small, so it only enqueues.  Grows (host-known sizes) when a store with a larger max_data_len is saved.
+// room for the worst case of the snapshot's groups in store `st`: every cell holding every shard at max_data_len -- for a whole
+// store the planes' own size.  A save can then never find the snapshot too small, so it only enqueues.  Grows (host-known sizes)
+// when a store with a larger max_data_len is saved.
 static int pssnap_room(smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
-    const uint64_t need = (uint64_t)st->planes * st->plane_bytes;
+    const uint64_t need = (uint64_t)st->planes * st->v.W * st->v.n * s->G * st->v.cap_sl;
     if (s->buf.dev && need <= s->cap_bytes) return SMR_OK;
     s->buf.filled = false; s->buf.hdr_known = false;
     return pssnap_alloc(s, need > s->cap_bytes ? need : s->cap_bytes);
@@ -1478,9 +1483,11 @@ static int pssnap_room(smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
 static int pssnap_header(smr_rsp_pstore_snapshot *s) {
     return snap_buf_header(s->buf, s->hdr, PSSNAP, [s](const PsSnapHdr &h) { return h.shard_bytes <= s->cap_bytes; });
 }
-static bool pssnap_like(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
-    return s->G == st->v.G && s->W == st->v.W && s->n == st->v.n && s->d == st->v.d && s->planes == st->planes && (s->craft != 0) == st->craft_store;
+// made for a store like st, whatever its n_groups (a snapshot of chosen groups has its own)
+static bool pssnap_like_kind(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
+    return s->W == st->v.W && s->n == st->v.n && s->d == st->v.d && s->planes == st->planes && (s->craft != 0) == st->craft_store;
 }
+static bool pssnap_like(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) { return s->G == st->v.G && pssnap_like_kind(s, st); }
 static bool pssnap_hdr_like(const PsSnapHdr &h, const smr_rsp_pstore_snapshot *s) {
     return h.n_groups == s->G && h.window == s->W && h.n_shards == s->n && h.n_data_shards == s->d && h.planes == s->planes && h.craft == s->craft;
 }
@@ -1492,17 +1499,45 @@ static PsSnapArgs pssnap_args(const smr_rsp_pstore *st, const smr_rsp_pstore_sna
     return A;
 }
 static uint32_t pssnap_byte_blocks(const PsSnapArgs &A) {
-    const uint64_t items = (uint64_t)A.geo.planes * A.geo.cells * A.v.n, want = (items + 3) / 4;
+    const uint64_t items = (uint64_t)A.geo.planes * A.geo.cells * A.v.n, want = (items + 3) / 4;   // (the image's items: a short list, a short launch)
     return (uint32_t)(want < PSSNAP_BYTE_BLOCKS ? (want ? want : 1) : PSSNAP_BYTE_BLOCKS);
+}
+
+// ---- chosen groups between stores (ps_snapshot.h: the same image, the same bodies, through a group list) ---------------------
+static const char *const PSGROUPS = "pstore groups: ";
+enum PsGroupsCall { PSG_SAVE, PSG_LOAD, PSG_RESET };
+// every check of a listed-groups call before anything is written, allocated or launched, then the launches' arguments.  A reset
+// has no snapshot: A carries the geometry of n groups and no buffers
+static int psgroups_setup(smr_rsp_pstore *st, smr_rsp_pstore_snapshot *s, const uint32_t *groups, uint32_t n, PsGroupsCall call, PsSnapArgs &A) {
+    if (!st || !groups || (call != PSG_RESET && !s)) return fail(SMR_ERR_ARG, "pstore groups: null argument");
+    if (call != PSG_RESET) {
+        if (!pssnap_like_kind(s, st)) return fail(SMR_ERR_ARG, "pstore groups: the snapshot was made for another n_shards / n_data_shards / window / kind (RSPaxos or CRaft store)");
+        if (s->G != n) return fail(SMR_ERR_ARG, "pstore groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
+    }
+    if (int rc = snap_glist_check(groups, n, st->v.G, PSGROUPS)) return rc;
+    if (call == PSG_LOAD) {
+        if (int rc = pssnap_header(s)) return rc;
+        const PsSnapHdr &h = s->hdr;
+        if (!pssnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("pstore groups: the image is of ") + PSSNAP_OTHER);
+        if (h.max_dlen > st->max_data_len)
+            return fail(SMR_ERR_ARG, "pstore groups: a payload of " + std::to_string(h.max_dlen) + " bytes does not fit max_data_len " + std::to_string(st->max_data_len));
+    }
+    if (call == PSG_SAVE)
+        if (int rc = pssnap_room(s, st)) return rc;
+    if (call == PSG_RESET) {
+        memset(&A, 0, sizeof(A));
+        A.v = st->v; A.geo = pssnap_geom(n, st->v.W, (uint32_t)st->planes);
+    } else A = pssnap_args(st, s);
+    return SMR_OK;
 }
 }  // namespace smr
 
 extern "C" {
 
-int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+// a snapshot object for n groups of a store like `like` (n = its n_groups: the whole store)
+static int pssnap_create(const smr_rsp_pstore *like, uint32_t n, smr_rsp_pstore_snapshot **out) {
     smr_rsp_pstore_snapshot *s = new smr_rsp_pstore_snapshot();
-    s->G = like->v.G; s->W = like->v.W; s->n = (uint8_t)like->v.n; s->d = (uint8_t)like->v.d; s->planes = (uint8_t)like->planes;
+    s->G = n; s->W = like->v.W; s->n = (uint8_t)like->v.n; s->d = (uint8_t)like->v.d; s->planes = (uint8_t)like->planes;
     s->craft = like->craft_store ? 1 : 0;
     memset(&s->hdr, 0, sizeof(s->hdr));
     hipError_t e = hipMalloc((void **)&s->d_off, (size_t)s->planes * s->G * s->W * 8 + 8);
@@ -1512,11 +1547,62 @@ int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_sn
     return SMR_OK;
 }
 
+int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
+    return pssnap_create(like, like->v.G, out);
+}
+
+int smr_rsp_pstore_snapshot_create_groups(const smr_rsp_pstore *like, uint32_t n, smr_rsp_pstore_snapshot **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, "pstore groups: null argument");
+    if (n == 0 || n > like->v.G)
+        return fail(SMR_ERR_ARG, "pstore groups: a snapshot of " + std::to_string(n) + " groups of a store of " + std::to_string(like->v.G));
+    smr_rsp_pstore_snapshot *s = nullptr;
+    if (int rc = pssnap_create(like, n, &s)) return rc;
+    if (int rc = snap_glist_room(s->glist, n, PSGROUPS)) { smr_rsp_pstore_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
+    *out = s;
+    return SMR_OK;
+}
+
+int smr_rsp_pstore_save_groups(smr_rsp_pstore *st, const uint32_t *groups_host, uint32_t n, smr_rsp_pstore_snapshot *s, void *stream) {
+    PsSnapArgs A;
+    if (int rc = psgroups_setup(st, s, groups_host, n, PSG_SAVE, A)) return rc;
+    if (int rc = snap_glist_upload(s->glist, groups_host, n, (hipStream_t)stream, PSGROUPS)) return rc;
+    const uint32_t *list = s->glist.dev;
+    hipLaunchKernelGGL(ps_snap_head_groups<true>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A, list, 0);
+    hipLaunchKernelGGL(ps_snap_bytes_groups<true>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A, list);
+    SMR_HIP_TRY(hipGetLastError());
+    s->buf.filled = true; s->buf.hdr_known = false;
+    return SMR_OK;
+}
+
+int smr_rsp_pstore_load_groups(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *cs, const uint32_t *groups_host, uint32_t n, void *stream) {
+    smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);   // (the header is read back and cached on first use)
+    PsSnapArgs A;
+    if (int rc = psgroups_setup(st, s, groups_host, n, PSG_LOAD, A)) return rc;
+    if (int rc = snap_glist_upload(s->glist, groups_host, n, (hipStream_t)stream, PSGROUPS)) return rc;
+    const uint32_t *list = s->glist.dev;
+    hipLaunchKernelGGL(ps_snap_head_groups<false>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A, list, 0);
+    hipLaunchKernelGGL(ps_snap_bytes_groups<false>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A, list);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_rsp_pstore_reset_groups(smr_rsp_pstore *st, const uint32_t *groups_host, uint32_t n, void *stream) {
+    PsSnapArgs A;
+    if (int rc = psgroups_setup(st, nullptr, groups_host, n, PSG_RESET, A)) return rc;
+    if (int rc = snap_glist_upload(st->glist, groups_host, n, (hipStream_t)stream, PSGROUPS)) return rc;
+    const uint32_t *list = st->glist.dev;
+    hipLaunchKernelGGL(ps_snap_head_groups<false>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A, list, 1);   // cell headers only: row bytes are not touched
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
 void smr_rsp_pstore_snapshot_destroy(smr_rsp_pstore_snapshot *s) {
     if (!s) return;
     if (s->buf.dev || s->d_off) (void)hipDeviceSynchronize();
     if (s->buf.dev) (void)hipFree(s->buf.dev);
     if (s->d_off) (void)hipFree(s->d_off);
+    snap_glist_free(s->glist);
     delete s;
 }
 

@@ -22,6 +22,10 @@
 // The live span of a group is [len > W ? len - W : 0, len) (rsp_live_lo): a slot is held iff slot + W >= len, there is no ring_lo
 // beside len, so an image loads only into a replica of the window it came from.  On the device the record sections sit at fixed
 // capacities behind the fixed part; export closes the gaps.
+// Chosen groups (smr_rsp_save_groups / smr_rsp_load_groups / smr_rsp_reset_groups and their cluster forms) go through the same
+// image and the same bodies: an image of "these n groups, in this order" is the image of an n-group replica, read and written
+// through a group list (RspSnapGroupList below).  A group image holds zero counters; the unpolled execution list is per-group
+// rows and travels like every other section.
 #pragma once
 #include "snapshot_common.h"
 
@@ -97,6 +101,37 @@ SMR_HD RspSnapScal rspsnap_scal(uint8_t *b, const RspSnapGeom &q) {
     return s;
 }
 
+// ---- what a new replica object holds for a group ----------------------------------------------------------------------
+// The one place that says it: smr_rsp_replica_create fills its arrays from here, and smr_rsp_reset_groups (the unpack of
+// nothing, below) returns a listed group to the same values -- no leader known, every other word of the group (its scalars, the
+// peers' exec bars, the digest, all W ring rows, the execution list's rows) RSP_INIT_WORD, except the two value ids of every ring
+// row, which are null.  (smr_rsp_preset_leader is a step after create, not part of it.)
+constexpr uint32_t RSP_INIT_WORD = 0;
+constexpr uint8_t RSP_INIT_LEADER = RSP_NO_REP;
+constexpr uint8_t RSP_INIT_VAL_BYTE = 0xFF;                  // create fills bytes: s_val / s_vval of every ring row
+constexpr uint32_t RSP_INIT_VAL = 0x01010101u * RSP_INIT_VAL_BYTE;
+static_assert(RSP_INIT_WORD == 0 && RSP_INIT_LEADER == 0xFF, "create fills bytes");
+
+// ---- which group of the replica an image position holds -----------------------------------------------------------------
+// An image has its own group index (position x, stride n = its n_groups, lane = x & 63) and the replica has its own (group g,
+// stride v.G).  For a whole-replica image they are one and the same; an image of "these n groups, in this order" is the image of
+// an n-group replica whose group x is group list[x] of this one: the same format, the same tiles, bases and placement run over
+// list positions, and the replica side a gather or scatter.  The bodies below take the map as a parameter; with
+// RspSnapAllGroups they are what they were.
+// What a group image does not carry (WHOLE = false): the four counters.  Events stay counted where they happened, so the sum over
+// objects is conserved.  The image's counters are zero, and a load through a list leaves the target's alone.
+struct RspSnapAllGroups {
+    static constexpr bool WHOLE = true;
+    __device__ __forceinline__ uint32_t n(const RspView &v, const RspSnapGeom &) const { return v.G; }
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
+};
+struct RspSnapGroupList {
+    static constexpr bool WHOLE = false;
+    const uint32_t *__restrict__ list;                           // [n], every entry < v.G, none twice (the host has checked)
+    __device__ __forceinline__ uint32_t n(const RspView &, const RspSnapGeom &Q) const { return Q.G; }
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
+};
+
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1).  An RSPaxos replica keeps no device
 // copy of its view: the views travel by value and are indexed only by the block-uniform blockIdx.y, so they stay in the kernarg
@@ -109,45 +144,52 @@ struct RspSnapArgs {
     RspSnapGeom geo;
 };
 
-// live instances and unpolled executions in front of a wavefront: the replica's own (PACK) or the image's (of the same window: the
-// host has refused any other)
-template <bool PACK>
-__device__ __forceinline__ void rspsnap_bases(const RspView &v, const RspSnapScal &sc, const SnapWave &w, uint64_t (&base)[2], uint32_t (&mx)[2]) {
+// live instances and unpolled executions in front of a wavefront, over image positions: the replica's own (PACK: of the group
+// the map puts there) or the image's (of the same window: the host has refused any other)
+template <bool PACK, class Map>
+__device__ __forceinline__ void rspsnap_bases(const RspView &v, const RspSnapScal &sc, const Map &M, const SnapWave &w, uint64_t (&base)[2], uint32_t (&mx)[2]) {
     snap_bases(
-        [&](uint32_t g, uint64_t (&add)[2], uint32_t (&m)[2]) {
-            const uint32_t ns = rsp_live_n(PACK ? v.len[g] : sc.len[g], v.W);
-            uint32_t nx = PACK ? v.xn[g] : sc.xn[g];
+        [&](uint32_t x, uint64_t (&add)[2], uint32_t (&m)[2]) {
+            const uint32_t g = PACK ? M.group(x, true) : x;
+            const uint32_t ns = rsp_live_n(PACK ? v.len[g] : sc.len[x], v.W);
+            uint32_t nx = PACK ? v.xn[g] : sc.xn[x];
             if (nx > v.W) nx = v.W;                              // (smr_rsp_exec_poll reads no more)
             add[0] += ns; add[1] += nx; m[0] = ns > m[0] ? ns : m[0]; m[1] = nx > m[1] ? nx : m[1];
         },
         w.gb0, w.gw0, base, mx);
 }
 
-__global__ __launch_bounds__(256) void rsp_snap_pack(const RspSnapArgs A) {
+// save: the whole replica (rsp_snap_pack) or the listed groups (rsp_snap_pack_groups).  x: the lane's position in the image
+// (stride ni), g: its group in the replica (stride G)
+template <class Map>
+__device__ __forceinline__ void rspsnap_pack_all(const RspSnapArgs &A, const Map &M) {
     const RspSnapGeom &Q = A.geo;
     const uint32_t rep = blockIdx.y < SMR_MAX_REPLICAS ? blockIdx.y : 0u;
     const RspView &v = A.v[rep];
     const RspSnapImg S{A.img[rep], A.cap_s[rep], A.cap_x[rep]};
     const RspSnapScal sc = rspsnap_scal(S.base, Q);
-    const SnapWave w = snap_wave(Q.tiles, v.G);
-    const size_t G = v.G;
+    const uint32_t ni = M.n(v, Q);
+    const SnapWave w = snap_wave(Q.tiles, ni);
+    const size_t G = v.G, NX = ni;
     uint64_t base[2];                                            // slot records, exec entries in front
     uint32_t mx[2];
-    rspsnap_bases<true>(v, sc, w, base, mx);
+    rspsnap_bases<true>(v, sc, M, w, base, mx);
     RspSnapSlot *const recs = (RspSnapSlot *)(S.base + Q.fixed);
     uint32_t *const execs = (uint32_t *)(S.base + rspsnap_off_exec(Q, S));
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
+        const uint32_t x = t * 64 + w.lane;
+        const bool in = x < ni;
+        const uint32_t g = M.group(x, in);
         uint32_t n = 0, lo = 0, nx = 0;
-        if (g < v.G) {
+        if (in) {
             const uint32_t len = v.len[g];
             lo = rsp_live_lo(len, v.W); n = len - lo;
             nx = v.xn[g];
             if (nx > v.W) nx = v.W;
-            sc.leader[g] = v.leader[g]; sc.bps[g] = v.bps[g]; sc.bpd[g] = v.bpd[g]; sc.bms[g] = v.bms[g];
-            sc.len[g] = len; sc.cbar[g] = v.cbar[g]; sc.ebar[g] = v.ebar[g]; sc.snap[g] = v.snap[g];
-            sc.digest[g] = v.digest[g]; sc.xn[g] = nx;
-            for (uint32_t p = 0; p < v.R; p++) sc.peb[(size_t)p * G + g] = v.peb[(size_t)p * G + g];
+            sc.leader[x] = v.leader[g]; sc.bps[x] = v.bps[g]; sc.bpd[x] = v.bpd[g]; sc.bms[x] = v.bms[g];
+            sc.len[x] = len; sc.cbar[x] = v.cbar[g]; sc.ebar[x] = v.ebar[g]; sc.snap[x] = v.snap[g];
+            sc.digest[x] = v.digest[g]; sc.xn[x] = nx;
+            for (uint32_t p = 0; p < v.R; p++) sc.peb[(size_t)p * NX + x] = v.peb[(size_t)p * G + g];
         }
         const uint32_t maxn = snap_place(n, base[0], S.cap_s, w.lane, [&](uint32_t k, uint64_t pos) {
             const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
@@ -162,50 +204,73 @@ __global__ __launch_bounds__(256) void rsp_snap_pack(const RspSnapArgs A) {
         const uint32_t maxx = snap_place(nx, base[1], S.cap_x, w.lane, [&](uint32_t j, uint64_t pos) { execs[pos] = v.xq[(size_t)j * G + g]; });
         mx[0] = maxn > mx[0] ? maxn : mx[0]; mx[1] = maxx > mx[1] ? maxx : mx[1];
     }
-    snap_counters_save<4>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
+    if (Map::WHOLE) snap_counters_save<4>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
+    else if (blockIdx.x == 0 && threadIdx.x < 4) ((uint64_t *)(S.base + Q.off_ctr))[threadIdx.x] = 0;   // a group image carries no counters
     if (w.last && w.lane == 0) {                                 // the wavefront of the last tile knows the totals
         RspSnapHdr h;
         h.magic = RSPSNAP_MAGIC; h.version = RSPSNAP_VERSION;
-        h.n_groups = v.G; h.population = (uint8_t)v.R; h.me = (uint8_t)v.me; h.fault_tolerance = (uint8_t)v.ft; h.reserved0 = 0;
+        h.n_groups = ni; h.population = (uint8_t)v.R; h.me = (uint8_t)v.me; h.fault_tolerance = (uint8_t)v.ft; h.reserved0 = 0;
         h.window = v.W; h.max_live = mx[0];
         h.n_slots = base[0]; h.n_exec = base[1]; h.bytes = rspsnap_bytes(Q, base[0], base[1]);
         h.max_exec = mx[1]; h.reserved1 = 0; h.reserved2 = 0;
         *(RspSnapHdr *)S.base = h;
-        snap_zero_pad(S.base, Q.o_leader, G);                    // padding is zero
-        snap_zero_pad(S.base, Q.o_len, 4 * G); snap_zero_pad(S.base, Q.o_cbar, 4 * G); snap_zero_pad(S.base, Q.o_ebar, 4 * G);
-        snap_zero_pad(S.base, Q.o_snap, 4 * G); snap_zero_pad(S.base, Q.o_peb, 4 * G * v.R); snap_zero_pad(S.base, Q.o_xn, 4 * G);
+        snap_zero_pad(S.base, Q.o_leader, NX);                   // padding is zero
+        snap_zero_pad(S.base, Q.o_len, 4 * NX); snap_zero_pad(S.base, Q.o_cbar, 4 * NX); snap_zero_pad(S.base, Q.o_ebar, 4 * NX);
+        snap_zero_pad(S.base, Q.o_snap, 4 * NX); snap_zero_pad(S.base, Q.o_peb, 4 * NX * v.R); snap_zero_pad(S.base, Q.o_xn, 4 * NX);
         snap_zero_pad(S.base, rspsnap_off_exec(Q, S), 4 * (base[1] < S.cap_x ? base[1] : S.cap_x));
     }
 }
 
 // Load re-establishes: every scalar and peer row, the live instances' ring cells (at slot & Wmask), the unpolled execution
-// list, the counters as one shard.  Ring cells outside the live span keep what they held: no handler reads them (RspLane::held,
-// ring_lo) and the dump gives null instances there.
-__global__ __launch_bounds__(256) void rsp_snap_unpack(const RspSnapArgs A) {
+// list, the counters as one shard (the whole replica only).  Ring cells outside the live span keep what they held: no handler
+// reads them (RspLane::held, ring_lo) and the dump gives null instances there.
+// FRESH: the unpack of nothing -- no image is read, the listed groups become what smr_rsp_replica_create leaves (RSP_INIT_*
+// above), all W ring rows and the execution list's rows included, which is how smr_rsp_reset_groups empties a slot
+template <class Map, bool FRESH>
+__device__ __forceinline__ void rspsnap_unpack_all(const RspSnapArgs &A, const Map &M) {
     const RspSnapGeom &Q = A.geo;
     const uint32_t rep = blockIdx.y < SMR_MAX_REPLICAS ? blockIdx.y : 0u;
     const RspView &v = A.v[rep];
     const RspSnapImg S{A.img[rep], A.cap_s[rep], A.cap_x[rep]};
     const RspSnapScal sc = rspsnap_scal(S.base, Q);
-    const SnapWave w = snap_wave(Q.tiles, v.G);
-    const size_t G = v.G;
-    uint64_t base[2];
+    const uint32_t ni = M.n(v, Q);
+    const SnapWave w = snap_wave(Q.tiles, ni);
+    const size_t G = v.G, NX = ni;
+    uint64_t base[2] = {0, 0};
     uint32_t mx[2];
-    rspsnap_bases<false>(v, sc, w, base, mx);
+    if (!FRESH) rspsnap_bases<false>(v, sc, M, w, base, mx);
     const RspSnapSlot *const recs = (const RspSnapSlot *)(S.base + Q.fixed);
     const uint32_t *const execs = (const uint32_t *)(S.base + rspsnap_off_exec(Q, S));
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
+        const uint32_t x = t * 64 + w.lane;
+        const bool in = x < ni;
+        const uint32_t g = M.group(x, in);
         uint32_t n = 0, lo = 0, nx = 0;
-        if (g < v.G) {
-            const uint32_t len = sc.len[g];
+        if (in && FRESH) {
+            v.leader[g] = RSP_INIT_LEADER; v.bps[g] = RSP_INIT_WORD; v.bpd[g] = RSP_INIT_WORD; v.bms[g] = RSP_INIT_WORD;
+            v.len[g] = RSP_INIT_WORD; v.cbar[g] = RSP_INIT_WORD; v.ebar[g] = RSP_INIT_WORD; v.snap[g] = RSP_INIT_WORD;
+            v.digest[g] = RSP_INIT_WORD; v.xn[g] = RSP_INIT_WORD;
+            for (uint32_t p = 0; p < v.R; p++) v.peb[(size_t)p * G + g] = RSP_INIT_WORD;
+            for (uint32_t k = 0; k < v.W; k++) {
+                const size_t i = (size_t)k * G + g;
+                v.s_bal[i] = RSP_INIT_WORD; v.s_vbal[i] = RSP_INIT_WORD; v.s_pmax[i] = RSP_INIT_WORD;
+                v.s_val[i] = RSP_INIT_VAL; v.s_vval[i] = RSP_INIT_VAL; v.s_ltrig[i] = RSP_INIT_WORD; v.s_lendp[i] = RSP_INIT_WORD;
+                v.s_rtrig[i] = RSP_INIT_WORD; v.s_rendp[i] = RSP_INIT_WORD;
+                v.s_st[i] = (uint8_t)RSP_INIT_WORD; v.s_mask[i] = (uint8_t)RSP_INIT_WORD; v.s_vmask[i] = (uint8_t)RSP_INIT_WORD;
+                v.s_fl[i] = (uint8_t)RSP_INIT_WORD; v.s_packs[i] = (uint8_t)RSP_INIT_WORD; v.s_aacks[i] = (uint8_t)RSP_INIT_WORD;
+                v.s_rsrc[i] = (uint8_t)RSP_INIT_WORD; v.xq[i] = RSP_INIT_WORD;
+            }
+        }
+        if (FRESH) continue;
+        if (in) {
+            const uint32_t len = sc.len[x];
             lo = rsp_live_lo(len, v.W); n = len - lo;
-            nx = sc.xn[g];
+            nx = sc.xn[x];
             if (nx > v.W) nx = v.W;                              // (refused by the host: max_exec <= window)
-            v.leader[g] = sc.leader[g]; v.bps[g] = sc.bps[g]; v.bpd[g] = sc.bpd[g]; v.bms[g] = sc.bms[g];
-            v.len[g] = len; v.cbar[g] = sc.cbar[g]; v.ebar[g] = sc.ebar[g]; v.snap[g] = sc.snap[g];
-            v.digest[g] = sc.digest[g]; v.xn[g] = nx;
-            for (uint32_t p = 0; p < v.R; p++) v.peb[(size_t)p * G + g] = sc.peb[(size_t)p * G + g];
+            v.leader[g] = sc.leader[x]; v.bps[g] = sc.bps[x]; v.bpd[g] = sc.bpd[x]; v.bms[g] = sc.bms[x];
+            v.len[g] = len; v.cbar[g] = sc.cbar[x]; v.ebar[g] = sc.ebar[x]; v.snap[g] = sc.snap[x];
+            v.digest[g] = sc.digest[x]; v.xn[g] = nx;
+            for (uint32_t p = 0; p < v.R; p++) v.peb[(size_t)p * G + g] = sc.peb[(size_t)p * NX + x];
         }
         snap_place(n, base[0], S.cap_s, w.lane, [&](uint32_t k, uint64_t pos) {
             const size_t i = (size_t)((lo + k) & v.Wmask) * G + g;
@@ -217,7 +282,17 @@ __global__ __launch_bounds__(256) void rsp_snap_unpack(const RspSnapArgs A) {
         });
         snap_place(nx, base[1], S.cap_x, w.lane, [&](uint32_t j, uint64_t pos) { v.xq[(size_t)j * G + g] = execs[pos]; });
     }
-    snap_counters_load<4>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
+    if (Map::WHOLE) snap_counters_load<4>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
+}
+
+__global__ __launch_bounds__(256) void rsp_snap_pack(const RspSnapArgs A) { rspsnap_pack_all(A, RspSnapAllGroups{}); }
+__global__ __launch_bounds__(256) void rsp_snap_unpack(const RspSnapArgs A) { rspsnap_unpack_all<RspSnapAllGroups, false>(A, RspSnapAllGroups{}); }
+// group x of the image (A.geo.G = n groups) <-> group list[x] of the replica, one list for all replicas of the call; fresh: no
+// image, the listed groups as a new replica object holds them (A carries the geometry of n groups and no buffers)
+__global__ __launch_bounds__(256) void rsp_snap_pack_groups(const RspSnapArgs A, const uint32_t *list) { rspsnap_pack_all(A, RspSnapGroupList{list}); }
+__global__ __launch_bounds__(256) void rsp_snap_unpack_groups(const RspSnapArgs A, const uint32_t *list, int fresh) {
+    if (fresh) rspsnap_unpack_all<RspSnapGroupList, true>(A, RspSnapGroupList{list});
+    else rspsnap_unpack_all<RspSnapGroupList, false>(A, RspSnapGroupList{list});
 }
 
 }  // namespace smr

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .snapshot import DeviceSnapshot
+from .snapshot import DeviceSnapshot, group_list as _group_list
 from ._lib import MpCfg, MpDumpBufs, MpGroupState, MpTickIn, SummersetError, check, stream_ptr
 
 _DUMP_T = {"leader": np.uint8, "bal_prep_sent": np.uint64, "bal_prepared": np.uint64, "bal_max_seen": np.uint64,
@@ -27,27 +27,13 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _group_list(groups):
-    return np.ascontiguousarray(np.asarray(groups, dtype=np.int64).astype(np.uint32))
-
-
 class MpSnapshot(DeviceSnapshot):
     """A cluster's state between two ticks, held on the device (`smr_mp_snapshot`): what `MultiPaxosCluster.save_state`
     fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any two clusters that hold the
     same logical state -- and `from_bytes` takes one back.  `info()`: bytes, n_slots, n_outbox, n_groups, max_live, max_outbox,
-    population, commit_extra, live_mask"""
+    population, commit_extra, live_mask.  `MpSnapshot(like, n_groups)`: for that many of its groups only
+    (`smr_mp_snapshot_create_groups`: what `save_groups` fills and `load_groups` takes -- the image of an n_groups cluster)"""
     _STEM, _INFO = "smr_mp_snapshot", _lib.MpSnapshotInfo
-
-    def __init__(self, like, n_groups=None):
-        """room for the worst case of `like`; n_groups: for that many of its groups only (`smr_mp_snapshot_create_groups`:
-        what `save_groups` fills and `load_groups` takes -- the image of an n_groups cluster)"""
-        if n_groups is None:
-            super().__init__(like)
-            return
-        self._L = _lib.load()
-        h = C.c_void_p()
-        check(self._L.smr_mp_snapshot_create_groups(like._h, int(n_groups), C.byref(h)))
-        self._h = h
 
     @classmethod
     def from_bytes(cls, data, like, n_groups=None):

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .snapshot import DeviceSnapshot
+from .snapshot import DeviceSnapshot, group_list as _group_list
 from ._lib import RaftAppendEntries, RaftAppendReply, RaftCfg, RaftDumpBufs, check, stream_ptr
 
 _T = {"role": np.uint8, "leader": np.uint8, "curr_term": np.uint64, "entry_term": np.uint64}
@@ -20,10 +20,6 @@ _T = {"role": np.uint8, "leader": np.uint8, "curr_term": np.uint64, "entry_term"
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
-
-
-def _group_list(groups):
-    return np.ascontiguousarray(np.asarray(groups, dtype=np.int64).astype(np.uint32))
 
 
 def _handles(xs):
@@ -35,19 +31,10 @@ class RaftSnapshot(DeviceSnapshot):
     `RaftLeaderGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
     two replicas that hold the same logical state -- and `import_` takes one back (of a replica like the one this snapshot was
     made for; its window does not matter).  `info()`: bytes, n_entries, n_reconstructs, n_groups, max_live, max_reconstructs,
-    population, replica_id, commit_extra, craft, fault_tolerance, repeat_threshold"""
+    population, replica_id, commit_extra, craft, fault_tolerance, repeat_threshold.  `RaftSnapshot(like, n_groups)`: for that
+    many of its groups only (`smr_raft_snapshot_create_groups`: what `save_groups` fills and `load_groups` takes -- the image of
+    an n_groups replica)"""
     _STEM, _INFO = "smr_raft_snapshot", _lib.RaftSnapshotInfo
-
-    def __init__(self, like, n_groups=None):
-        """room for the worst case of `like`; n_groups: for that many of its groups only (`smr_raft_snapshot_create_groups`:
-        what `save_groups` fills and `load_groups` takes -- the image of an n_groups replica)"""
-        if n_groups is None:
-            super().__init__(like)
-            return
-        self._L = _lib.load()
-        h = C.c_void_p()
-        check(self._L.smr_raft_snapshot_create_groups(like._h, int(n_groups), C.byref(h)))
-        self._h = h
 
 
 def save_cluster_state(reps, snaps=None, stream=None):

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, stream_ptr
-from .snapshot import DeviceSnapshot
+from .snapshot import DeviceSnapshot, group_list as _group_list
 
 REQS, VOTED = 0, 1
 NULL = 0xFFFFFFFF
@@ -37,7 +37,9 @@ class PayloadStoreSnapshot(DeviceSnapshot):
     plane's alias bytes, every present shard that is no alias, the counters -- for an `RSPaxosPayloadStore` or a `CRaftPayloadStore`.
     `export()` gives the canonical image as bytes, equal for two stores of the same content whatever their `max_data_len`.
     `create_like`: room for every cell holding every shard at max_data_len.  `info()`: bytes, n_cells, n_shards_stored,
-    shard_bytes, n_groups, window, max_dlen, n_shards, n_data_shards, planes, craft"""
+    shard_bytes, n_groups, window, max_dlen, n_shards, n_data_shards, planes, craft.
+    `PayloadStoreSnapshot(like, n_groups)`: for that many of its groups only (`smr_rsp_pstore_snapshot_create_groups`) -- what
+    `save_groups` fills and `load_groups` takes, the image of an n_groups store"""
     _STEM, _INFO = "smr_rsp_pstore_snapshot", _lib.PstoreSnapshotInfo
 
     def save(self, store, stream=None):
@@ -196,6 +198,25 @@ class RSPaxosPayloadStore:
         max_data_len at least the snapshot's max_dlen"""
         snap.load(self, stream)
 
+    def save_groups(self, groups, snap=None, stream=None):
+        """the listed groups' headers, alias bytes and present shards as the image of a len(groups) store, group i of it =
+        groups[i] (`smr_rsp_pstore_save_groups`); the counters stay here"""
+        g = _group_list(groups)
+        snap = PayloadStoreSnapshot(self, len(g)) if snap is None else snap
+        check(self._L.smr_rsp_pstore_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
+        return snap
+
+    def load_groups(self, snap, groups, stream=None):
+        """group i of a len(groups) image overwrites the cells of group groups[i]; every other group, the counters and the row
+        bytes behind a shard's length are left alone (`smr_rsp_pstore_load_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_rsp_pstore_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+    def reset_groups(self, groups, stream=None):
+        """the listed groups' cells back to what a new store holds (`smr_rsp_pstore_reset_groups`); row bytes are not touched"""
+        g = _group_list(groups)
+        check(self._L.smr_rsp_pstore_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
     def delivered(self):
         """of `counters()["copied"]`: shards a sender's `put_follow_all` wrote here from its put launch (no copy out of its row)"""
         c = np.zeros(1, np.uint64)
@@ -255,6 +276,53 @@ class CRaftPayloadStore(RSPaxosPayloadStore):
         raise _lib.SummersetError(_lib.SMR_ERR_STATE, "Accept frames are RSPaxos'")
 
 
+def move_store_groups(src_stores, src_groups, dst_stores, dst_groups, snaps=None, reset=True):
+    """groups src_groups[i] of the stores `src_stores` become groups dst_groups[i] of `dst_stores` (store k to store k, between
+    two calls on both), shard bytes included; the source's cells then back to what a new store holds.  Either kind of store.
+    The counters stay where the events happened.  Returns the snapshots, for the next move of as many groups"""
+    snaps = [None] * len(src_stores) if snaps is None else list(snaps)
+    if not (len(src_stores) == len(dst_stores) == len(snaps)):
+        raise ValueError("move_store_groups: %d source stores, %d target stores, %d snapshots" % (len(src_stores), len(dst_stores), len(snaps)))
+    snaps = [s.save_groups(src_groups, sn) for s, sn in zip(src_stores, snaps)]
+    for d, sn in zip(dst_stores, snaps):
+        d.load_groups(sn, dst_groups)
+    if reset:
+        for s in src_stores:
+            s.reset_groups(src_groups)
+    return snaps
+
+
+def move_rsp_groups(src, src_groups, dst, dst_groups, snaps=None, reset=True):
+    """groups src_groups[i] of the RSPaxos objects `src` become groups dst_groups[i] of `dst` (replica k to replica k, between
+    two handler calls of both).  Lists of `RSPaxosReplicaGroup`: one cluster save, one cluster load, the source's slots back to
+    what a new object holds; returns the replica snapshots.  Lists of `RSPaxosReplicaWithPayload`: the stores move too (a moved
+    group is useless without its bytes); returns (replica snapshots, store snapshots), which `snaps` takes back for the next
+    move of as many groups.  Which job group sits in which slot is the caller's table"""
+    from . import rspaxos
+    with_payload = len(src) > 0 and isinstance(src[0], RSPaxosReplicaWithPayload)
+    rs, ps = (snaps if snaps is not None else (None, None)) if with_payload else (snaps, None)
+    sreps = [x.replica for x in src] if with_payload else list(src)
+    dreps = [x.replica for x in dst] if with_payload else list(dst)
+    rs = rspaxos.save_cluster_groups(sreps, src_groups, rs)
+    rspaxos.load_cluster_groups(dreps, rs, dst_groups)
+    if reset:
+        rspaxos.reset_cluster_groups(sreps, src_groups)
+    if not with_payload:
+        return rs
+    ps = move_store_groups([x.store for x in src], src_groups, [x.store for x in dst], dst_groups, ps, reset)
+    return rs, ps
+
+
+def move_craft_groups(src_reps, src_stores, src_groups, dst_reps, dst_stores, dst_groups, snaps=None, reset=True):
+    """`raft.move_groups` of the CRaft replica objects followed by `move_store_groups` of their stores: a moved group's rows are
+    present at once, nothing is refilled by follow / Reconstruct.  Returns (replica snapshots, store snapshots)"""
+    from . import raft
+    rs, ps = (None, None) if snaps is None else snaps
+    rs = raft.move_groups(src_reps, src_groups, dst_reps, dst_groups, rs, reset)
+    ps = move_store_groups(src_stores, src_groups, dst_stores, dst_groups, ps, reset)
+    return rs, ps
+
+
 class RSPaxosReplicaWithPayload:
     """An `RSPaxosReplicaGroup` and its payload store as one object: the replica's handlers, each followed by `store.follow`,
     and `req_batch` by the `put` of the serialized batches.  A handler that consumes a message carrying shards names where
@@ -291,6 +359,20 @@ class RSPaxosReplicaWithPayload:
     def load_state(self, snaps, stream=None):
         self.replica.load_state(snaps[0], stream=stream)
         self.store.load(snaps[1], stream=stream)
+
+    def save_groups(self, groups, snaps=None, stream=None):
+        """the listed groups of the replica and of its store, both halves on one stream: (RSPaxosSnapshot, PayloadStoreSnapshot)
+        of len(groups) groups -- new ones, or `snaps` filled again"""
+        rs, ps = (None, None) if snaps is None else snaps
+        return self.replica.save_groups(groups, rs, stream=stream), self.store.save_groups(groups, ps, stream=stream)
+
+    def load_groups(self, snaps, groups, stream=None):
+        self.replica.load_groups(snaps[0], groups, stream=stream)
+        self.store.load_groups(snaps[1], groups, stream=stream)
+
+    def reset_groups(self, groups, stream=None):
+        self.replica.reset_groups(groups, stream=stream)
+        self.store.reset_groups(groups, stream=stream)
 
     def req_batch(self, val, data=None, lens=None, stream=None, out=None):
         acc = self.replica.req_batch(val, stream=stream, out=out)

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .snapshot import DeviceSnapshot
+from .snapshot import DeviceSnapshot, group_list as _group_list
 from ._lib import RspAccepts, RspCfg, RspDumpBufs, RspHeartbeat, RspPrepareReply, RspShards, check, stream_ptr
 
 NULL, NO_REP = 0xFFFFFFFF, 0xFF
@@ -29,7 +29,9 @@ class RSPaxosSnapshot(DeviceSnapshot):
     `RSPaxosReplicaGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
     two replicas that hold the same logical state -- and `import_` takes one back (of a replica like the one this snapshot was
     made for; any window).  `create_like`: room for every ring row live and a full execution list.  `info()`: bytes, n_slots,
-    n_exec, n_groups, window, max_live, max_exec, population, replica_id, fault_tolerance"""
+    n_exec, n_groups, window, max_live, max_exec, population, replica_id, fault_tolerance.
+    `RSPaxosSnapshot(like, n_groups)`: for that many of its groups only (`smr_rsp_snapshot_create_groups`) -- what `save_groups`
+    fills and `load_groups` takes, the image of an n_groups replica"""
     _STEM, _INFO = "smr_rsp_snapshot", _lib.RspSnapshotInfo
 
     def save(self, rep, stream=None):
@@ -61,6 +63,32 @@ def load_cluster_state(reps, snaps, stream=None):
     if len(snaps) != len(reps):
         raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
     check(_lib.load().smr_rsp_cluster_load_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+
+
+def save_cluster_groups(reps, groups, snaps=None, stream=None):
+    """`reps[k].save_groups(groups, snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch, one list for all of
+    them (`smr_rsp_cluster_save_groups`); returns the snapshots (new ones without `snaps`)"""
+    g = _group_list(groups)
+    snaps = [RSPaxosSnapshot(r, len(g)) for r in reps] if snaps is None else list(snaps)
+    if len(snaps) != len(reps):
+        raise ValueError("save_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_rsp_cluster_save_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), _handles(snaps), stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_groups(reps, snaps, groups, stream=None):
+    """`reps[k].load_groups(snaps[k], groups)` for up to 8 replicas of one co-located cluster in ONE launch
+    (`smr_rsp_cluster_load_groups`)"""
+    g = _group_list(groups)
+    if len(snaps) != len(reps):
+        raise ValueError("load_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
+    check(_lib.load().smr_rsp_cluster_load_groups(len(reps), _handles(reps), _handles(snaps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+
+def reset_cluster_groups(reps, groups, stream=None):
+    """`reps[k].reset_groups(groups)` for up to 8 replicas of one co-located cluster in ONE launch (`smr_rsp_cluster_reset_groups`)"""
+    g = _group_list(groups)
+    check(_lib.load().smr_rsp_cluster_reset_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
 
 
 class RSPaxosReplicaGroup:
@@ -201,6 +229,25 @@ class RSPaxosReplicaGroup:
         """overwrite my whole logical state with a snapshot's (`smr_rsp_load_state`): same n_groups, population, replica id,
         fault_tolerance and window"""
         snap.load(self, stream)
+
+    def save_groups(self, groups, snap=None, stream=None):
+        """the listed groups' state as the image of a len(groups) replica, group i of it = groups[i] (`smr_rsp_save_groups`),
+        the unpolled execution list included; the counters stay here"""
+        g = _group_list(groups)
+        snap = RSPaxosSnapshot(self, len(g)) if snap is None else snap
+        check(self._L.smr_rsp_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
+        return snap
+
+    def load_groups(self, snap, groups, stream=None):
+        """group i of a len(groups) image overwrites group groups[i]; every other group and the counters are left alone
+        (`smr_rsp_load_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_rsp_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+
+    def reset_groups(self, groups, stream=None):
+        """the listed groups back to what a new replica object holds (`smr_rsp_reset_groups`)"""
+        g = _group_list(groups)
+        check(self._L.smr_rsp_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
 
     def dump(self):
         G, R, W = self.G, self.R, self.W

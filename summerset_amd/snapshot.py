@@ -5,18 +5,31 @@ struct; what a snapshot object does on the host -- make, close, ask its sizes, e
 """
 import ctypes as C
 
+import numpy as np
+
 from . import _lib
 from ._lib import check
+
+
+def group_list(groups):
+    """a list of groups as the contiguous uint32 host array the `*_groups` calls take (an id that does not fit stays out of
+    range, so the library refuses it)"""
+    return np.ascontiguousarray(np.asarray(groups, dtype=np.int64).astype(np.uint32))
 
 
 class DeviceSnapshot:
     _STEM = None       # the C symbols are <stem>_create, _destroy, _info_get, _export, _import
     _INFO = None       # the ctypes struct <stem>_info_get fills
 
-    def __init__(self, like):
+    def __init__(self, like, n_groups=None):
+        """room for the worst case of `like`; n_groups (MultiPaxos, Raft, RSPaxos, the payload stores: <stem>_create_groups): for
+        that many of its groups only -- what `save_groups` fills and `load_groups` takes, the image of an n_groups object"""
         self._L = _lib.load()
         h = C.c_void_p()
-        check(self._call("create")(like._h, C.byref(h)))
+        if n_groups is None:
+            check(self._call("create")(like._h, C.byref(h)))
+        else:
+            check(self._call("create_groups")(like._h, int(n_groups), C.byref(h)))
         self._h = h
 
     def _call(self, what):
