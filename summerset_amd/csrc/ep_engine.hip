@@ -3524,43 +3524,14 @@ int smr_ep_cluster_tick(smr_ep_cluster *c, const uint8_t *const *keys_dev, const
 /* ---- save / load of one replica's state on the device (ep_snapshot.h: the image and its two kernels) ----------------------------
  * A batched replica object is saved and brought back whole, between two handler calls, by one kernel each, while the other
  * replicas of its cluster go on: a checkpoint, the restart of one replica, the way back from an aborted L2 tick. */
-struct smr_ep_snapshot {
+struct smr_ep_snapshot : SnapObj<EpSnapHdr, 3> {                 // cap: cells, reply records, submission-list entries
     uint32_t G = 0, K = 0;
     uint8_t R = 0, me = 0, oq = 0, execute = 0, recovery = 0;
-    SnapBuf buf;
-    uint64_t cap_c = 0, cap_r = 0, cap_x = 0;                    // records the device buffer's sections have room for
-    EpSnapHdr hdr;                                               // the image's header, once buf.hdr_known
 };
 
 namespace smr {
-static const char *const EPSNAP = "epaxos snapshot: ";
 static EpSnapGeom epsnap_geom_of(const smr_ep_snapshot *s) { return epsnap_geom(s->G, s->R, s->K, s->execute, s->recovery); }
-static EpSnapImg epsnap_img(const smr_ep_snapshot *s) { return EpSnapImg{s->buf.dev, s->cap_c, s->cap_r, s->cap_x}; }
-static int epsnap_alloc(smr_ep_snapshot *s, uint64_t cap_c, uint64_t cap_r, uint64_t cap_x) {
-    s->cap_c = cap_c; s->cap_r = cap_r; s->cap_x = cap_x;
-    return snap_buf_alloc(s->buf, epsnap_dev_bytes(epsnap_geom_of(s), epsnap_img(s)), EPSNAP);
-}
-// room for the worst case of a replica with window W: every ring cell live, the submission list full.  A save can then never find
-// the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica with a
-// larger window is saved into it.
-static int epsnap_room_for(smr_ep_snapshot *s, uint64_t W) {
-    const uint64_t c = (uint64_t)s->G * s->R * W, r = (uint64_t)s->G * (s->recovery ? s->R : 1) * W, x = s->execute ? 2 * c : 0;
-    if (s->buf.dev && c <= s->cap_c && r <= s->cap_r && x <= s->cap_x) return SMR_OK;
-    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
-    return epsnap_alloc(s, std::max(c, s->cap_c), std::max(r, s->cap_r), std::max(x, s->cap_x));
-}
-// the image's header on the host (synchronises once after a save)
-static int epsnap_header(smr_ep_snapshot *s) {
-    return snap_buf_header(s->buf, s->hdr, EPSNAP,
-                           [s](const EpSnapHdr &h) { return h.n_cells <= s->cap_c && h.n_replies <= s->cap_r && h.n_exec <= s->cap_x; });
-}
-// the image of header h between the device buffer (sections at their capacities) and packed host bytes
-static int epsnap_copy(const smr_ep_snapshot *s, uint8_t *host, const EpSnapHdr &h, bool to_host) {
-    const EpSnapGeom q = epsnap_geom_of(s);
-    const uint64_t bc = h.n_cells * sizeof(EpSnapCell), br = (uint64_t)h.n_replies * q.r_stride, bx = h.n_exec * sizeof(EpSnapExec);
-    return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
-                              {{q.fixed, bc, bc}, {epsnap_off_rep(q, epsnap_img(s)), br, br}, {epsnap_off_exec(q, epsnap_img(s)), bx, bx}});
-}
+static EpSnapImg epsnap_img(const smr_ep_snapshot *s) { return EpSnapImg{s->buf.dev, s->cap[0], s->cap[1], s->cap[2]}; }
 static bool epsnap_like(const smr_ep_snapshot *s, const smr_ep_cfg &c) {
     return s->G == c.n_groups && s->R == c.population && s->me == c.me && s->oq == (c.optimized_quorum ? 1 : 0) && s->execute == c.execute &&
            s->recovery == c.recovery && s->K == c.n_keys;
@@ -3571,70 +3542,76 @@ static bool epsnap_hdr_like(const EpSnapHdr &h, const smr_ep_snapshot *s) {
 }
 static const char *const EPSNAP_OTHER = "another n_groups / population / replica id / optimized_quorum / execute / recovery / n_keys";
 
-// the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
-static int epsnap_setup(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, bool load, EpSnapArgs &A) {
-    if (int rc = snap_pairs_check(n, reps, snaps, EPSNAP, [&](uint32_t k) {
-            const smr_ep_cfg &c = reps[k]->cfg, &c0 = reps[0]->cfg;
-            if (c.n_groups != c0.n_groups || c.population != c0.population || c.n_keys != c0.n_keys || c.execute != c0.execute || c.recovery != c0.recovery)
-                return fail(SMR_ERR_ARG, "epaxos snapshot: the replicas differ in groups / population / n_keys / execute / recovery");
-            if (!epsnap_like(snaps[k], c)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: made for ") + EPSNAP_OTHER);
-            return (int)SMR_OK;
-        })) return rc;
-    memset(&A, 0, sizeof(A));
-    for (uint32_t k = 0; k < n; k++) {
-        smr_ep_replica *e = reps[k];
-        smr_ep_snapshot *s = snaps[k];
-        if (load) {
-            if (int rc = epsnap_header(s)) return rc;
-            const EpSnapHdr &h = s->hdr;
-            if (!epsnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: the image is of ") + EPSNAP_OTHER);
-            // a cell is held iff column + W >= len: in another ring the cells around the saved span would count as held or lost
-            if (h.window != e->cfg.window)
-                return fail(SMR_ERR_ARG, "epaxos snapshot: an image of window " + std::to_string(h.window) + " does not load into window " + std::to_string(e->cfg.window));
-        } else if (int rc = epsnap_room_for(s, e->cfg.window)) return rc;   // (only a failed hipMalloc: the snapshots that grew before it are
-                                                                            //  then empty, SMR_ERR_STATE on use, and none holds a partial image)
+// what is EPaxos's own of a snapshot object and its calls (snapshot_common.h: SnapObj); it has no listed-groups calls
+struct EpSnap {
+    static constexpr const char *WHAT = "epaxos snapshot: ";
+    static uint32_t groups_of(const smr_ep_replica *e) { return e->cfg.n_groups; }
+    static int init(smr_ep_snapshot *s, const smr_ep_replica *like) {
+        const smr_ep_cfg &c = like->cfg;
+        s->K = c.n_keys; s->R = c.population; s->me = c.me; s->oq = c.optimized_quorum ? 1 : 0; s->execute = c.execute; s->recovery = c.recovery;
+        return SMR_OK;
     }
+    // every ring cell live, the submission list full
+    static void need(const smr_ep_snapshot *s, const smr_ep_replica *e, uint64_t (&n)[3]) {
+        const uint64_t W = e->cfg.window;
+        n[0] = (uint64_t)s->G * s->R * W; n[1] = (uint64_t)s->G * (s->recovery ? s->R : 1) * W; n[2] = s->execute ? 2 * n[0] : 0;
+    }
+    static void counts(const EpSnapHdr &h, uint64_t (&n)[3]) { n[0] = h.n_cells; n[1] = h.n_replies; n[2] = h.n_exec; }
+    static uint64_t dev_bytes(const smr_ep_snapshot *s) { return epsnap_dev_bytes(epsnap_geom_of(s), epsnap_img(s)); }
+    static int copy(const smr_ep_snapshot *s, uint8_t *host, const EpSnapHdr &h, bool to_host) {
+        const EpSnapGeom q = epsnap_geom_of(s);
+        const uint64_t bc = h.n_cells * sizeof(EpSnapCell), br = (uint64_t)h.n_replies * q.r_stride, bx = h.n_exec * sizeof(EpSnapExec);
+        return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
+                                  {{q.fixed, bc, bc}, {epsnap_off_rep(q, epsnap_img(s)), br, br}, {epsnap_off_exec(q, epsnap_img(s)), bx, bx}});
+    }
+    static int load_fits(const smr_ep_snapshot *s, const smr_ep_replica *e, const char *what, bool) {
+        if (!epsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + EPSNAP_OTHER);
+        // a cell is held iff column + W >= len: in another ring the cells around the saved span would count as held or lost
+        if (s->hdr.window != e->cfg.window)
+            return fail(SMR_ERR_ARG, std::string(what) + "an image of window " + std::to_string(s->hdr.window) + " does not load into window " + std::to_string(e->cfg.window));
+        return SMR_OK;
+    }
+    static int pair_check(smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, uint32_t k) {
+        const smr_ep_cfg &c = reps[k]->cfg, &c0 = reps[0]->cfg;
+        if (c.n_groups != c0.n_groups || c.population != c0.population || c.n_keys != c0.n_keys || c.execute != c0.execute || c.recovery != c0.recovery)
+            return fail(SMR_ERR_ARG, "epaxos snapshot: the replicas differ in groups / population / n_keys / execute / recovery");
+        if (!epsnap_like(snaps[k], c)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: made for ") + EPSNAP_OTHER);
+        return SMR_OK;
+    }
+};
+
+// the arguments of the one launch for n replicas and their snapshots
+static void epsnap_args(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, EpSnapArgs &A) {
+    memset(&A, 0, sizeof(A));
     const smr_ep_cfg &c0 = reps[0]->cfg;
     A.geo = epsnap_geom(c0.n_groups, c0.population, c0.n_keys, c0.execute, c0.recovery);
     for (uint32_t k = 0; k < n; k++) {
         A.v[k] = reps[k]->v; A.x[k] = reps[k]->x; A.img[k] = snaps[k]->buf.dev;
-        A.cap_c[k] = snaps[k]->cap_c; A.cap_r[k] = snaps[k]->cap_r; A.cap_x[k] = snaps[k]->cap_x; A.oq[k] = snaps[k]->oq;
+        A.cap_c[k] = snaps[k]->cap[0]; A.cap_r[k] = snaps[k]->cap[1]; A.cap_x[k] = snaps[k]->cap[2]; A.oq[k] = snaps[k]->oq;
     }
-    return SMR_OK;
 }
 }  // namespace smr
 
 extern "C" {
 
-int smr_ep_snapshot_create(const smr_ep_replica *like, smr_ep_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
-    smr_ep_snapshot *s = new smr_ep_snapshot();
-    const smr_ep_cfg &c = like->cfg;
-    s->G = c.n_groups; s->K = c.n_keys; s->R = c.population; s->me = c.me; s->oq = c.optimized_quorum ? 1 : 0; s->execute = c.execute; s->recovery = c.recovery;
-    memset(&s->hdr, 0, sizeof(s->hdr));
-    if (int rc = epsnap_room_for(s, c.window)) { delete s; return rc; }
-    *out = s;
-    return SMR_OK;
-}
-
-void smr_ep_snapshot_destroy(smr_ep_snapshot *s) {
-    if (!s) return;
-    snap_buf_free(s->buf);
-    delete s;
-}
+int smr_ep_snapshot_create(const smr_ep_replica *like, smr_ep_snapshot **out) { return snap_obj_create<EpSnap>(like, out); }
+void smr_ep_snapshot_destroy(smr_ep_snapshot *s) { snap_obj_destroy(s); }
 
 int smr_ep_cluster_save_state(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, void *stream) {
     EpSnapArgs A;
-    if (int rc = epsnap_setup(n, reps, snaps, false, A)) return rc;
+    if (int rc = snap_cluster_setup<EpSnap>(n, reps, snaps, false)) return rc;
+    epsnap_args(n, reps, snaps, A);
     hipLaunchKernelGGL(ep_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    for (uint32_t k = 0; k < n; k++) snap_obj_saved(snaps[k]);
     return SMR_OK;
 }
 
-int smr_ep_cluster_load_state(uint32_t n, smr_ep_replica *const *reps, const smr_ep_snapshot *const *snaps, void *stream) {
-    EpSnapArgs A;                                                // (a snapshot's header is read back and cached on first use)
-    if (int rc = epsnap_setup(n, reps, const_cast<smr_ep_snapshot *const *>(snaps), true, A)) return rc;
+int smr_ep_cluster_load_state(uint32_t n, smr_ep_replica *const *reps, const smr_ep_snapshot *const *csnaps, void *stream) {
+    smr_ep_snapshot *const *snaps = const_cast<smr_ep_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
+    EpSnapArgs A;
+    if (int rc = snap_cluster_setup<EpSnap>(n, reps, snaps, true)) return rc;
+    epsnap_args(n, reps, snaps, A);
     hipLaunchKernelGGL(ep_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -3657,31 +3634,20 @@ int smr_ep_debug_arena_view(smr_ep_replica *e, void **base_dev, uint64_t *n_byte
 }
 
 int smr_ep_snapshot_info_get(const smr_ep_snapshot *cs, smr_ep_snapshot_info *out) {
-    if (!cs || !out) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
-    smr_ep_snapshot *s = const_cast<smr_ep_snapshot *>(cs);
-    if (int rc = epsnap_header(s)) return rc;
-    const EpSnapHdr &h = s->hdr;
-    memset(out, 0, sizeof(*out));
+    if (int rc = snap_obj_info<EpSnap>(cs, out)) return rc;
+    const EpSnapHdr &h = cs->hdr;
     out->bytes = h.bytes; out->n_cells = h.n_cells; out->n_exec = h.n_exec;
     out->n_groups = h.n_groups; out->window = h.window; out->n_keys = h.n_keys; out->max_live = h.max_live; out->max_exec = h.max_exec;
     out->population = h.population; out->me = h.me; out->optimized_quorum = h.optimized_quorum; out->execute = h.execute; out->recovery = h.recovery;
     return SMR_OK;
 }
 
-int64_t smr_ep_snapshot_export(const smr_ep_snapshot *cs, uint8_t *host, uint64_t cap) {
-    if (!cs || !host) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
-    smr_ep_snapshot *s = const_cast<smr_ep_snapshot *>(cs);
-    if (int rc = epsnap_header(s)) return rc;
-    const EpSnapHdr &h = s->hdr;
-    if (cap < h.bytes) return fail(SMR_ERR_ARG, "epaxos snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    if (int rc = epsnap_copy(s, host, h, true)) return rc;
-    return (int64_t)h.bytes;
-}
+int64_t smr_ep_snapshot_export(const smr_ep_snapshot *cs, uint8_t *host, uint64_t cap) { return snap_obj_export<EpSnap>(cs, host, cap); }
 
 int smr_ep_snapshot_import(smr_ep_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "epaxos snapshot: null argument");
     EpSnapHdr h;
-    if (int rc = snap_import_prologue(host, len, EPSNAP_MAGIC, EPSNAP_VERSION, EPSNAP, h)) return rc;
+    if (int rc = snap_import_prologue(host, len, EPSNAP_MAGIC, EPSNAP_VERSION, EpSnap::WHAT, h)) return rc;
     if (!epsnap_hdr_like(h, s) || h.reserved0[0] || h.reserved0[1] || h.reserved0[2])
         return fail(SMR_ERR_ARG, std::string("epaxos snapshot: the image is of ") + EPSNAP_OTHER);
     const uint32_t W = h.window, R = s->R, G = s->G, K = s->K;
@@ -3753,14 +3719,7 @@ int smr_ep_snapshot_import(smr_ep_snapshot *s, const uint8_t *host, uint64_t len
                 }
         }
     }
-    const uint64_t c = std::max<uint64_t>(h.n_cells, s->cap_c), r = std::max<uint64_t>(h.n_replies, s->cap_r), x = std::max<uint64_t>(h.n_exec, s->cap_x);
-    if (c != s->cap_c || r != s->cap_r || x != s->cap_x)
-        if (int rc = epsnap_alloc(s, c, r, x)) return rc;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    s->buf.filled = false;
-    if (int rc = epsnap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
-    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
-    return SMR_OK;
+    return snap_obj_import_bytes<EpSnap>(s, host, h);
 }
 
 }  // extern "C"

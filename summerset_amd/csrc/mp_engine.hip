@@ -2131,10 +2131,6 @@ __global__ __launch_bounds__(256) void mp_round_heartbeat_multi(const MpMulti M)
 
 using namespace smr;
 
-// a list of groups on the device (smr_mp_save_groups / _load_groups / _reset_groups): owned by the snapshot object the call
-// works on (reset: by the cluster), made once and grown only when a longer list comes
-struct GroupListBuf { uint32_t *dev = nullptr; uint32_t cap = 0; };
-
 struct smr_mp_cluster {
     smr_mp_cfg cfg;
     MpParams hp;            // host copy (device pointers inside)
@@ -2165,7 +2161,7 @@ struct smr_mp_cluster {
     const uint32_t *rest_ackctl = nullptr;
     uint32_t lead_hint = 0;          // the replica most groups are led by (smr_mp_preset_leader): the tally's speculative loads
     bool spread_open = false;        // a smr_mp_spread tick is open on this block (between its segment 0 and its end / abort): no save, no load
-    GroupListBuf glist;              // smr_mp_reset_groups' list
+    SnapGroupListBuf glist;          // smr_mp_reset_groups' list
     bool profile = false;
     std::vector<ProfEv> evs;
     double prof_ms[5] = {0, 0, 0, 0, 0};
@@ -3262,95 +3258,102 @@ int smr_mp_spread_tick(smr_mp_spread *s, const smr_mp_tick_in *in, int heartbeat
 /* ---- save / load of a cluster's state on the device (mp_snapshot.h: the image and its two kernels) ------------------------------
  * The crash-restart loop of summerset_server/src/main.rs:124-167 brings a replica back from its snapshot file and WAL
  * (snapshot.rs:121-186, recovery.rs); a batched cluster is saved and brought back whole, between two ticks, by one kernel each. */
-struct smr_mp_snapshot {
+struct smr_mp_snapshot : SnapObj<SnapHdr, 3> {                   // cap: slots, outbox entries, commit-list entries
     uint32_t G = 0;
     uint8_t R = 0, commit_extra = 0, live = 0;
-    SnapBuf buf;
-    uint64_t cap_slots = 0, cap_ob = 0, cap_cl = 0;              // records the device buffer's three sections have room for
-    SnapHdr hdr;                                                 // the image's header, once buf.hdr_known
     uint32_t lead_hint = 0;                                      // (scheduling only: not part of the image)
-    GroupListBuf glist;                                          // smr_mp_save_groups / smr_mp_load_groups: the list on the device
 };
 
-static const char *const MPSNAP = "mp snapshot: ";
 static SnapImg snap_img(const smr_mp_snapshot *s) {
     SnapImg S;
-    S.base = s->buf.dev; S.cap_slots = s->cap_slots; S.cap_ob = s->cap_ob; S.cap_cl = s->cap_cl;
+    S.base = s->buf.dev; S.cap_slots = s->cap[0]; S.cap_ob = s->cap[1]; S.cap_cl = s->cap[2];
     S.geo = snap_geom(s->G, s->R, s->live); S.commit_extra = s->commit_extra;
     return S;
 }
-static int snap_alloc(smr_mp_snapshot *s, uint64_t cap_slots, uint64_t cap_ob, uint64_t cap_cl) {
-    s->cap_slots = cap_slots; s->cap_ob = cap_ob; s->cap_cl = cap_cl;
-    return snap_buf_alloc(s->buf, snap_off_clist(snap_img(s)) + cap_cl * 8, MPSNAP);
+// made for a cluster like c, whatever its n_groups (a snapshot of chosen groups has its own)
+static bool snap_like_kind(const smr_mp_snapshot *s, const smr_mp_cluster *c) {
+    return s->R == c->cfg.population && s->commit_extra == c->cfg.commit_extra && s->live == (uint8_t)c->hp.live;
 }
-// room for the worst case of a cluster with c's window, outbox_cap and commit_list_cap: every ring row live, every outbox
-// full.  A save can then never find the snapshot too small, so it stays a call that only enqueues and whose result needs no
-// confirmation before the state moves on (the abort-restore path loads it after the cluster has).  The worst case is a
-// fraction of the arena (56 B of its ~150 B per ring row, no ack matrix, no scratch); untouched pages cost nothing but
-// address space.  Grows (host-known sizes: no read-back) when a cluster with larger capacities is saved into it.
-static int snap_room(smr_mp_snapshot *s, const smr_mp_cluster *c) {
-    const SnapGeom q = snap_geom(s->G, s->R, s->live);
-    const uint64_t GL = (uint64_t)s->G * q.L;
-    const uint64_t ns = GL * c->cfg.window, no = GL * c->cfg.outbox_cap, nc = (uint64_t)q.L * c->cfg.commit_list_cap;
-    if (s->buf.dev && ns <= s->cap_slots && no <= s->cap_ob && nc <= s->cap_cl) return SMR_OK;
-    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
-    return snap_alloc(s, ns > s->cap_slots ? ns : s->cap_slots, no > s->cap_ob ? no : s->cap_ob, nc > s->cap_cl ? nc : s->cap_cl);
+static bool snap_like(const smr_mp_snapshot *s, const smr_mp_cluster *c) { return s->G == c->cfg.n_groups && snap_like_kind(s, c); }
+static bool snap_hdr_like(const SnapHdr &h, const smr_mp_snapshot *s) {
+    return h.n_groups == s->G && h.population == s->R && h.commit_extra == s->commit_extra && h.live_mask == s->live;
 }
-// the image's header on the host (synchronises once after a save)
-static int snap_header(smr_mp_snapshot *s) {
-    return snap_buf_header(s->buf, s->hdr, MPSNAP, [s](const SnapHdr &h) { return h.n_slots <= s->cap_slots && h.n_outbox <= s->cap_ob && h.n_commits <= s->cap_cl; });
-}
-// the image of header h between the device buffer (sections at their capacities) and packed host bytes
-static int snap_copy(const smr_mp_snapshot *s, uint8_t *host, const SnapHdr &h, bool to_host) {
-    const SnapImg S = snap_img(s);
-    const uint64_t ns = h.n_slots * sizeof(SnapSlot), no = h.n_outbox * sizeof(SnapMsg), nc = h.n_commits * 8;
-    return snap_copy_sections(s->buf.dev, host, S.geo.fixed, to_host, {{S.geo.fixed, ns, ns}, {snap_off_msgs(S), no, no}, {snap_off_clist(S), nc, nc}});
-}
-static bool snap_like(const smr_mp_snapshot *s, const smr_mp_cluster *c) {
-    return s->G == c->cfg.n_groups && s->R == c->cfg.population && s->commit_extra == c->cfg.commit_extra && s->live == (uint8_t)c->hp.live;
-}
+static bool mp_open_tick(const smr_mp_cluster *c) { return c->forked || c->marked || c->spread_open; }
 
-// a snapshot object for n groups of a cluster like `like` (n = its n_groups: the whole cluster)
-static int snap_create(const smr_mp_cluster *like, uint32_t n, smr_mp_snapshot **out) {
-    if (like->hp.live == 0) return fail(SMR_ERR_ARG, "mp snapshot: the cluster has no live replica");
-    smr_mp_snapshot *s = new smr_mp_snapshot();
-    s->G = n; s->R = like->cfg.population; s->commit_extra = like->cfg.commit_extra; s->live = (uint8_t)like->hp.live;
-    memset(&s->hdr, 0, sizeof(s->hdr));
-    if (int rc = snap_room(s, like)) { delete s; return rc; }
-    *out = s;
+// what is MultiPaxos's own of a snapshot object and its calls (snapshot_common.h: SnapObj)
+struct MpSnap {
+    static constexpr const char *WHAT = "mp snapshot: ", *GWHAT = "mp groups: ", *NOUN = "cluster", *LIST_OF = "a cluster of ";
+    static constexpr bool LIST_FIRST = true;
+    static uint32_t groups_of(const smr_mp_cluster *c) { return c->cfg.n_groups; }
+    static int init(smr_mp_snapshot *s, const smr_mp_cluster *like) {
+        if (like->hp.live == 0) return fail(SMR_ERR_ARG, "mp snapshot: the cluster has no live replica");
+        s->R = like->cfg.population; s->commit_extra = like->cfg.commit_extra; s->live = (uint8_t)like->hp.live;
+        return SMR_OK;
+    }
+    // every ring row live, every outbox full, c's commit_list_cap.  A save's result then needs no confirmation before the state
+    // moves on (the abort-restore path loads it after the cluster has).  The worst case is a fraction of the arena (56 B of its
+    // ~150 B per ring row, no ack matrix, no scratch); untouched pages cost nothing but address space
+    static void need(const smr_mp_snapshot *s, const smr_mp_cluster *c, uint64_t (&n)[3]) {
+        const uint64_t L = snap_geom(s->G, s->R, s->live).L, GL = (uint64_t)s->G * L;
+        n[0] = GL * c->cfg.window; n[1] = GL * c->cfg.outbox_cap; n[2] = L * c->cfg.commit_list_cap;
+    }
+    static void counts(const SnapHdr &h, uint64_t (&n)[3]) { n[0] = h.n_slots; n[1] = h.n_outbox; n[2] = h.n_commits; }
+    static uint64_t dev_bytes(const smr_mp_snapshot *s) { return snap_off_clist(snap_img(s)) + s->cap[2] * 8; }
+    static int copy(const smr_mp_snapshot *s, uint8_t *host, const SnapHdr &h, bool to_host) {
+        const SnapImg S = snap_img(s);
+        const uint64_t ns = h.n_slots * sizeof(SnapSlot), no = h.n_outbox * sizeof(SnapMsg), nc = h.n_commits * 8;
+        return snap_copy_sections(s->buf.dev, host, S.geo.fixed, to_host, {{S.geo.fixed, ns, ns}, {snap_off_msgs(S), no, no}, {snap_off_clist(S), nc, nc}});
+    }
+    static int load_fits(const smr_mp_snapshot *s, const smr_mp_cluster *c, const char *what, bool groups) {
+        const SnapHdr &h = s->hdr;
+        if (!snap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of another n_groups / population / commit_extra / live mask");
+        if (h.max_live > c->cfg.window)
+            return fail(SMR_ERR_ARG, std::string(what) + "a log of " + std::to_string(h.max_live) + " live slots does not fit window " + std::to_string(c->cfg.window));
+        if (h.max_outbox > c->cfg.outbox_cap)
+            return fail(SMR_ERR_ARG, std::string(what) + std::to_string(h.max_outbox) + " pending outbox entries do not fit outbox_cap " + std::to_string(c->cfg.outbox_cap));
+        if (groups && h.n_commits != 0)                          // they are the source's reporting, under the source's group ids
+            return fail(SMR_ERR_ARG, std::string(what) + "the image carries " + std::to_string(h.n_commits) + " unpolled commits: poll the source first");
+        if (!groups && h.max_commits > c->cfg.commit_list_cap)
+            return fail(SMR_ERR_ARG, std::string(what) + std::to_string(h.max_commits) + " unpolled commits do not fit commit_list_cap " + std::to_string(c->cfg.commit_list_cap));
+        return SMR_OK;
+    }
+    static int groups_pair_check(smr_mp_cluster *const *cs, smr_mp_snapshot *const *snaps, uint32_t, uint32_t n, SnapGroupsCall call) {
+        if (call != SNAP_GROUPS_RESET) {
+            if (int rc = snap_groups_len_check(n, snaps[0]->G, GWHAT)) return rc;
+            if (!snap_like_kind(snaps[0], cs[0])) return fail(SMR_ERR_ARG, "mp groups: the snapshot was made for another population / commit_extra / live mask");
+        }
+        static const char *const verb[3] = {"save", "load", "reset"};
+        if (mp_open_tick(cs[0])) return fail(SMR_ERR_STATE, std::string("mp groups: ") + verb[call] + " inside an open tick");
+        return SMR_OK;
+    }
+};
+
+// A deferred R3 rest of the WHOLE cluster holds the caller's ackctl pointer and must not outlive a save, nor run after single
+// groups were read or replaced.  Defence only: today smr_mp_run_ticks never defers the rest of a batch's last tick and flushes
+// what is left before it returns, so no boundary a caller can see has one pending and the launch does not run.
+static int flush_rest(smr_mp_cluster *c, hipStream_t st) {
+    if (!c->rest_pending) return SMR_OK;
+    c->rest_pending = false;
+    hipLaunchKernelGGL(mp_round_replies, mp_grid(c), dim3(MP_BLOCK), 0, st, c->dp, c->rest_par, c->rest_ackctl, 0, 0);
+    SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
 }
 
-int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
-    return snap_create(like, like->cfg.n_groups, out);
-}
-
-void smr_mp_snapshot_destroy(smr_mp_snapshot *s) {
-    if (!s) return;
-    snap_buf_free(s->buf);
-    if (s->glist.dev) (void)hipFree(s->glist.dev);               // (snap_buf_free has synchronised)
-    delete s;
-}
+int smr_mp_snapshot_create(const smr_mp_cluster *like, smr_mp_snapshot **out) { return snap_obj_create<MpSnap>(like, out); }
+int smr_mp_snapshot_create_groups(const smr_mp_cluster *like, uint32_t n, smr_mp_snapshot **out) { return snap_obj_create_groups<MpSnap>(like, n, out); }
+void smr_mp_snapshot_destroy(smr_mp_snapshot *s) { snap_obj_destroy(s); }
 
 int smr_mp_save_state(smr_mp_cluster *c, smr_mp_snapshot *s, void *stream) {
     if (!c || !s) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
     if (!snap_like(s, c)) return fail(SMR_ERR_ARG, "mp snapshot: made for another n_groups / population / commit_extra / live mask");
-    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, "mp snapshot: save inside an open tick");
-    if (int rc = snap_room(s, c)) return rc;
+    if (mp_open_tick(c)) return fail(SMR_ERR_STATE, "mp snapshot: save inside an open tick");
+    if (int rc = snap_obj_room_for<MpSnap>(s, c)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    // A deferred R3 rest holds the caller's ackctl pointer and must not outlive the boundary.  Defence only: today
-    // smr_mp_run_ticks never defers the rest of a batch's last tick and flushes what is left before it returns, so no boundary
-    // a caller can see has one pending and this branch does not run.
-    if (c->rest_pending) {
-        c->rest_pending = false;
-        hipLaunchKernelGGL(mp_round_replies, mp_grid(c), dim3(MP_BLOCK), 0, st, c->dp, c->rest_par, c->rest_ackctl, 0, 0);
-        SMR_HIP_TRY(hipGetLastError());
-    }
+    if (int rc = flush_rest(c, st)) return rc;
     const SnapImg S = snap_img(s);
     hipLaunchKernelGGL(mp_snap_pack, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S);
     SMR_HIP_TRY(hipGetLastError());
-    s->buf.filled = true; s->buf.hdr_known = false;
+    snap_obj_saved(s);
     s->lead_hint = c->lead_hint;
     return SMR_OK;
 }
@@ -3359,17 +3362,8 @@ int smr_mp_load_state(smr_mp_cluster *c, const smr_mp_snapshot *cs, void *stream
     if (!c || !cs) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
     smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);      // (the header is read back and cached on first use)
     if (!snap_like(s, c)) return fail(SMR_ERR_ARG, "mp snapshot: made for another n_groups / population / commit_extra / live mask");
-    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, "mp snapshot: load inside an open tick");
-    if (int rc = snap_header(s)) return rc;
-    const SnapHdr &h = s->hdr;
-    if (h.n_groups != c->cfg.n_groups || h.population != c->cfg.population || h.commit_extra != c->cfg.commit_extra || h.live_mask != (uint8_t)c->hp.live)
-        return fail(SMR_ERR_ARG, "mp snapshot: the image is of another n_groups / population / commit_extra / live mask");
-    if (h.max_live > c->cfg.window)
-        return fail(SMR_ERR_ARG, "mp snapshot: a log of " + std::to_string(h.max_live) + " live slots does not fit window " + std::to_string(c->cfg.window));
-    if (h.max_outbox > c->cfg.outbox_cap)
-        return fail(SMR_ERR_ARG, "mp snapshot: " + std::to_string(h.max_outbox) + " pending outbox entries do not fit outbox_cap " + std::to_string(c->cfg.outbox_cap));
-    if (h.max_commits > c->cfg.commit_list_cap)
-        return fail(SMR_ERR_ARG, "mp snapshot: " + std::to_string(h.max_commits) + " unpolled commits do not fit commit_list_cap " + std::to_string(c->cfg.commit_list_cap));
+    if (mp_open_tick(c)) return fail(SMR_ERR_STATE, "mp snapshot: load inside an open tick");
+    if (int rc = snap_obj_load_ready<MpSnap>(s, c, MpSnap::WHAT, false)) return rc;
     c->rest_pending = false;                                     // whatever the cluster had pending belongs to the state that goes
     c->lead_hint = s->lead_hint < c->cfg.population ? s->lead_hint : 0u;
     const SnapImg S = snap_img(s);
@@ -3380,97 +3374,27 @@ int smr_mp_load_state(smr_mp_cluster *c, const smr_mp_snapshot *cs, void *stream
 
 /* ---- chosen groups between clusters (mp_snapshot.h: the same image, the same unit bodies, through a group list) ---------------
  * A group is one lane and talks to no other group, so its state travels on its own: an image of "these n groups, in this order"
- * is the image of an n-group cluster.  The list is a host array -- a move is a rare host decision -- checked here before
- * anything is launched. */
-static int glist_room(GroupListBuf &b, uint32_t n) {
-    if (b.dev && n <= b.cap) return SMR_OK;
-    if (b.dev) { SMR_HIP_TRY(hipDeviceSynchronize()); (void)hipFree(b.dev); b.dev = nullptr; b.cap = 0; }   // (a launch may still read it)
-    hipError_t e = hipMalloc((void **)&b.dev, (size_t)n * 4);
-    if (e != hipSuccess) { b.dev = nullptr; return fail(SMR_ERR_DEVICE, std::string("mp groups: hipMalloc of the list: ") + hipGetErrorString(e)); }
-    b.cap = n;
-    return SMR_OK;
-}
-// n in 1 .. n_groups, every id below n_groups, none twice (a bitmap: O(n))
-static int glist_check(const smr_mp_cluster *c, const uint32_t *groups, uint32_t n) {
-    const uint32_t G = c->cfg.n_groups;
-    if (n == 0 || n > G) return fail(SMR_ERR_ARG, "mp groups: a list of " + std::to_string(n) + " groups for a cluster of " + std::to_string(G));
-    std::vector<uint64_t> seen(((size_t)G + 63) / 64, 0ull);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t g = groups[i];
-        if (g >= G) return fail(SMR_ERR_ARG, "mp groups: list entry " + std::to_string(i) + " is group " + std::to_string(g) + " of " + std::to_string(G));
-        if ((seen[g >> 6] >> (g & 63u)) & 1ull) return fail(SMR_ERR_ARG, "mp groups: group " + std::to_string(g) + " is listed twice");
-        seen[g >> 6] |= 1ull << (g & 63u);
-    }
-    return SMR_OK;
-}
-// what save and load through a list ask of (cluster, snapshot, list) before they look at the image
-static int groups_check(const smr_mp_cluster *c, const smr_mp_snapshot *s, const uint32_t *groups, uint32_t n, const char *verb) {
-    if (!c || !s || !groups) return fail(SMR_ERR_ARG, "mp groups: null argument");
-    if (int rc = glist_check(c, groups, n)) return rc;
-    if (n != s->G) return fail(SMR_ERR_ARG, "mp groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
-    if (s->R != c->cfg.population || s->commit_extra != c->cfg.commit_extra || s->live != (uint8_t)c->hp.live)
-        return fail(SMR_ERR_ARG, "mp groups: the snapshot was made for another population / commit_extra / live mask");
-    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, std::string("mp groups: ") + verb + " inside an open tick");
-    return SMR_OK;
-}
-// The list in front of the kernel, on its stream.  The caller's array is pageable memory, which the runtime has read (staged)
-// by the time the copy call returns: the caller may reuse it at once, and the next call may overwrite the device buffer, in
-// stream order
-static int glist_upload(GroupListBuf &b, const uint32_t *groups, uint32_t n, hipStream_t st) {
-    if (int rc = glist_room(b, n)) return rc;
-    SMR_HIP_TRY(hipMemcpyAsync(b.dev, groups, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    return SMR_OK;
-}
-// a deferred R3 rest of the WHOLE cluster must run before single groups are read or replaced (defence only, as in save)
-static int flush_rest(smr_mp_cluster *c, hipStream_t st) {
-    if (!c->rest_pending) return SMR_OK;
-    c->rest_pending = false;
-    hipLaunchKernelGGL(mp_round_replies, mp_grid(c), dim3(MP_BLOCK), 0, st, c->dp, c->rest_par, c->rest_ackctl, 0, 0);
-    SMR_HIP_TRY(hipGetLastError());
-    return SMR_OK;
-}
-
-int smr_mp_snapshot_create_groups(const smr_mp_cluster *like, uint32_t n, smr_mp_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "mp groups: null argument");
-    if (n == 0 || n > like->cfg.n_groups)
-        return fail(SMR_ERR_ARG, "mp groups: a snapshot of " + std::to_string(n) + " groups of a cluster of " + std::to_string(like->cfg.n_groups));
-    smr_mp_snapshot *s = nullptr;
-    if (int rc = snap_create(like, n, &s)) return rc;
-    if (int rc = glist_room(s->glist, n)) { smr_mp_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
-    *out = s;
-    return SMR_OK;
-}
-
+ * is the image of an n-group cluster.  The checks are snapshot_common.h's snap_groups_setup; the open-tick refusal and the
+ * flush of a deferred rest are the cluster's own. */
 int smr_mp_save_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, smr_mp_snapshot *s, void *stream) {
-    if (int rc = groups_check(c, s, groups_host, n, "save")) return rc;
-    if (int rc = snap_room(s, c)) return rc;
+    if (int rc = snap_groups_setup<MpSnap>(1, &c, &s, groups_host, n, SNAP_GROUPS_SAVE)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = flush_rest(c, st)) return rc;
-    if (int rc = glist_upload(s->glist, groups_host, n, st)) return rc;
+    if (int rc = snap_glist_upload(s->glist, groups_host, n, st, MpSnap::GWHAT)) return rc;
     const SnapImg S = snap_img(s);
     hipLaunchKernelGGL(mp_snap_pack_groups, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S, (const uint32_t *)s->glist.dev);
     SMR_HIP_TRY(hipGetLastError());
-    s->buf.filled = true; s->buf.hdr_known = false;
+    snap_obj_saved(s);
     s->lead_hint = c->lead_hint;
     return SMR_OK;
 }
 
 int smr_mp_load_groups(smr_mp_cluster *c, const smr_mp_snapshot *cs, const uint32_t *groups_host, uint32_t n, void *stream) {
     smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);      // (the header is read back and cached on first use)
-    if (int rc = groups_check(c, s, groups_host, n, "load")) return rc;
-    if (int rc = snap_header(s)) return rc;
-    const SnapHdr &h = s->hdr;
-    if (h.n_groups != n || h.population != c->cfg.population || h.commit_extra != c->cfg.commit_extra || h.live_mask != (uint8_t)c->hp.live)
-        return fail(SMR_ERR_ARG, "mp groups: the image is of another n_groups / population / commit_extra / live mask");
-    if (h.max_live > c->cfg.window)
-        return fail(SMR_ERR_ARG, "mp groups: a log of " + std::to_string(h.max_live) + " live slots does not fit window " + std::to_string(c->cfg.window));
-    if (h.max_outbox > c->cfg.outbox_cap)
-        return fail(SMR_ERR_ARG, "mp groups: " + std::to_string(h.max_outbox) + " pending outbox entries do not fit outbox_cap " + std::to_string(c->cfg.outbox_cap));
-    if (h.n_commits != 0)                                        // they are the source's reporting, under the source's group ids
-        return fail(SMR_ERR_ARG, "mp groups: the image carries " + std::to_string(h.n_commits) + " unpolled commits: poll the source first");
+    if (int rc = snap_groups_setup<MpSnap>(1, &c, &s, groups_host, n, SNAP_GROUPS_LOAD)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = flush_rest(c, st)) return rc;
-    if (int rc = glist_upload(s->glist, groups_host, n, st)) return rc;
+    if (int rc = snap_glist_upload(s->glist, groups_host, n, st, MpSnap::GWHAT)) return rc;
     const SnapImg S = snap_img(s);
     hipLaunchKernelGGL(mp_snap_unpack_groups, dim3(S.geo.tiles.nblock), dim3(256), 0, st, c->dp, c->par, S, (const uint32_t *)s->glist.dev, 0);
     SMR_HIP_TRY(hipGetLastError());
@@ -3478,12 +3402,10 @@ int smr_mp_load_groups(smr_mp_cluster *c, const smr_mp_snapshot *cs, const uint3
 }
 
 int smr_mp_reset_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, void *stream) {
-    if (!c || !groups_host) return fail(SMR_ERR_ARG, "mp groups: null argument");
-    if (int rc = glist_check(c, groups_host, n)) return rc;
-    if (c->forked || c->marked || c->spread_open) return fail(SMR_ERR_STATE, "mp groups: reset inside an open tick");
+    if (int rc = snap_groups_setup<MpSnap>(1, &c, (smr_mp_snapshot *const *)nullptr, groups_host, n, SNAP_GROUPS_RESET)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = flush_rest(c, st)) return rc;
-    if (int rc = glist_upload(c->glist, groups_host, n, st)) return rc;
+    if (int rc = snap_glist_upload(c->glist, groups_host, n, st, MpSnap::GWHAT)) return rc;
     SnapImg S;                                                   // no image: the geometry of n groups alone
     S.base = nullptr; S.cap_slots = S.cap_ob = S.cap_cl = 0;
     S.geo = snap_geom(n, c->cfg.population, c->hp.live); S.commit_extra = c->cfg.commit_extra;
@@ -3493,11 +3415,8 @@ int smr_mp_reset_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t
 }
 
 int smr_mp_snapshot_info_get(const smr_mp_snapshot *cs, smr_mp_snapshot_info *out) {
-    if (!cs || !out) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
-    smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);
-    if (int rc = snap_header(s)) return rc;
-    const SnapHdr &h = s->hdr;
-    memset(out, 0, sizeof(*out));
+    if (int rc = snap_obj_info<MpSnap>(cs, out)) return rc;
+    const SnapHdr &h = cs->hdr;
     out->bytes = h.bytes; out->n_slots = h.n_slots; out->n_outbox = h.n_outbox;
     out->n_groups = h.n_groups; out->max_live = h.max_live; out->max_outbox = h.max_outbox;
     out->population = h.population; out->commit_extra = h.commit_extra; out->live_mask = h.live_mask;
@@ -3505,12 +3424,10 @@ int smr_mp_snapshot_info_get(const smr_mp_snapshot *cs, smr_mp_snapshot_info *ou
 }
 
 int64_t smr_mp_snapshot_export(const smr_mp_snapshot *cs, uint8_t *host, uint64_t cap) {
-    if (!cs || !host) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
-    smr_mp_snapshot *s = const_cast<smr_mp_snapshot *>(cs);
-    if (int rc = snap_header(s)) return rc;
+    const int64_t got = snap_obj_export<MpSnap>(cs, host, cap);
+    if (got < 0) return got;
+    const smr_mp_snapshot *s = cs;
     const SnapHdr &h = s->hdr;
-    if (cap < h.bytes) return fail(SMR_ERR_ARG, "mp snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    if (int rc = snap_copy(s, host, h, true)) return rc;
     const SnapGeom q = snap_geom(s->G, s->R, s->live);
     uint8_t *p = host + h.bytes - h.n_commits * 8;
     // the list's order across groups is the order the wavefronts' appends happened to land in (smr_mp_poll_commits: unspecified):
@@ -3533,8 +3450,8 @@ int64_t smr_mp_snapshot_export(const smr_mp_snapshot *cs, uint8_t *host, uint64_
 int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "mp snapshot: null argument");
     SnapHdr h;
-    if (int rc = snap_import_prologue(host, len, SNAP_MAGIC, SNAP_VERSION, MPSNAP, h)) return rc;
-    if (h.n_groups != s->G || h.population != s->R || h.commit_extra != s->commit_extra || h.live_mask != s->live || h.reserved0 || h.reserved1)
+    if (int rc = snap_import_prologue(host, len, SNAP_MAGIC, SNAP_VERSION, MpSnap::WHAT, h)) return rc;
+    if (!snap_hdr_like(h, s) || h.reserved0 || h.reserved1)
         return fail(SMR_ERR_ARG, "mp snapshot: the image is of another n_groups / population / commit_extra / live mask");
     const SnapGeom q = snap_geom(s->G, s->R, s->live);
     if (snap_truncated(len, q.fixed, h.bytes)) return fail(SMR_ERR_ARG, "mp snapshot: truncated image");
@@ -3588,14 +3505,8 @@ int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len
         memcpy(&e, p, 8);
         if ((e >> 32) >= s->G) return bad("commit entry of a group beyond n_groups");
     }
-    if (h.n_slots > s->cap_slots || h.n_outbox > s->cap_ob || h.n_commits > s->cap_cl)
-        if (int rc = snap_alloc(s, h.n_slots > s->cap_slots ? h.n_slots : s->cap_slots, h.n_outbox > s->cap_ob ? h.n_outbox : s->cap_ob,
-                                h.n_commits > s->cap_cl ? h.n_commits : s->cap_cl)) return rc;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    s->buf.filled = false;
-    if (int rc = snap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
-    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true; s->lead_hint = 0;
-    return SMR_OK;
+    s->lead_hint = 0;
+    return snap_obj_import_bytes<MpSnap>(s, host, h);
 }
 
 }  // extern "C"

@@ -150,29 +150,11 @@ SMR_HD SnapScal snap_scal(uint8_t *base, const SnapGeom &q, uint32_t i) {
     return s;
 }
 
-// ---- which group of the cluster an image position holds ------------------------------------------------------------------
-// An image has its own group index (position i, stride n = its n_groups, lane = i & 63) and the cluster has its own (group g,
-// stride P.G, rows at tix(W, row, g)).  For a whole-cluster image they are one and the same; an image of "these n groups, in
-// this order" (smr_mp_save_groups / smr_mp_load_groups) is the image of an n-group cluster whose group i is group list[i] of
-// this one -- the same format, the same tiles, bases and placement run over list positions, and the cluster side a gather or
-// scatter: two listed groups share a line of a ring row only where they sit in the same 64-group tile.  The unit bodies below
-// take the map as a parameter; with SnapAllGroups they are what they were.
+// ---- which group of the cluster an image position holds: snapshot_common.h's SnapAllGroups / SnapGroupList ------------------
 // What a group image does not carry (WHOLE = false): the counters and the unpolled commit list.  They are the cluster's
-// reporting, not a group's state -- events stay counted where they happened, so the sum over clusters is conserved, and a moved
-// group's unpolled entries stay on the source's list under the source's group id (the host polls the source before it reuses
-// the slot).  The image's counters and commit-list words are zero and n_commits = 0; a load through a list leaves the
-// target's counters, commit list, straggler list, role_rot and the host's scheduling state alone.
-struct SnapAllGroups {
-    static constexpr bool WHOLE = true;
-    __device__ __forceinline__ uint32_t n(const MpParams &P, const SnapGeom &) const { return P.G; }
-    __device__ __forceinline__ uint32_t group(uint32_t i, bool) const { return i; }
-};
-struct SnapGroupList {
-    static constexpr bool WHOLE = false;
-    const uint32_t *__restrict__ list;                           // [n], every entry < P.G, none twice (the host has checked)
-    __device__ __forceinline__ uint32_t n(const MpParams &, const SnapGeom &Q) const { return Q.G; }
-    __device__ __forceinline__ uint32_t group(uint32_t i, bool in) const { return in ? list[i] : 0u; }
-};
+// reporting, not a group's state: a moved group's unpolled entries stay on the source's list under the source's group id (the
+// host polls the source before it reuses the slot).  The image's counters and commit-list words are zero and n_commits = 0; a
+// load through a list leaves the target's counters, commit list, straggler list, role_rot and the host's scheduling state alone.
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // A wavefront's tiles carry all their live replicas.  Tiles, bases and placement are snapshot_common.h's; a
@@ -246,7 +228,7 @@ template <class Map>
 __device__ __forceinline__ void snap_pack_unit(const MpParams &P, int par, const SnapImg &S, const Map &M, uint32_t r, uint32_t i, uint32_t tile,
                                                uint64_t (&base)[2], uint32_t (&mx)[2]) {
     const SnapGeom &Q = S.geo;
-    const uint32_t lane = threadIdx.x & 63u, x = tile * 64 + lane, nx = M.n(P, Q);
+    const uint32_t lane = threadIdx.x & 63u, x = tile * 64 + lane, nx = M.n(P.G, Q.G);
     const bool in = x < nx;
     const uint32_t g = M.group(x, in);
     const RepView v{P.rep[0], (size_t)r * P.rep_stride};
@@ -299,7 +281,7 @@ template <class Map, bool FRESH>
 __device__ __forceinline__ void snap_unpack_unit(const MpParams &P, int par, const SnapImg &S, const Map &M, uint32_t r, uint32_t i, uint32_t tile,
                                                  uint64_t (&base)[2]) {
     const SnapGeom &Q = S.geo;
-    const uint32_t lane = threadIdx.x & 63u, x = tile * 64 + lane, nx = M.n(P, Q);
+    const uint32_t lane = threadIdx.x & 63u, x = tile * 64 + lane, nx = M.n(P.G, Q.G);
     const bool in = x < nx;
     const uint32_t g = M.group(x, in);
     const RepView v{P.rep[0], (size_t)r * P.rep_stride};
@@ -387,7 +369,7 @@ __device__ __forceinline__ void snap_lists(const MpParams &P, const SnapImg &S, 
 template <class Map>
 __device__ __forceinline__ void snap_pack_all(const MpParams &P, int par, const SnapImg &S, const Map &M) {
     const SnapGeom &Q = S.geo;
-    const uint32_t nx = M.n(P, Q);
+    const uint32_t nx = M.n(P.G, Q.G);
     const SnapWave w = snap_wave(Q.tiles, nx);
     uint64_t base[2];                                            // slot, outbox records in front
     uint32_t mx[2];
@@ -422,7 +404,7 @@ __device__ __forceinline__ void snap_pack_all(const MpParams &P, int par, const 
 template <class Map, bool FRESH>
 __device__ __forceinline__ void snap_unpack_all(const MpParams &P, int par, const SnapImg &S, const Map &M) {
     const SnapGeom &Q = S.geo;
-    const SnapWave w = snap_wave(Q.tiles, M.n(P, Q));
+    const SnapWave w = snap_wave(Q.tiles, M.n(P.G, Q.G));
     uint64_t base[2] = {0, 0};
     uint32_t mx[2];
     if (!FRESH) mp_snap_bases<false>(P, par, S, M, w, base, mx);

@@ -21,7 +21,7 @@
 // The image is dense: the device buffer holds exactly the exported bytes.
 // Chosen groups (smr_rsp_pstore_save_groups / _load_groups / _reset_groups) go through the same image and the same bodies: an
 // image of "these n groups, in this order" is the image of an n-group store, read and written through a group list
-// (PsSnapGroupList below): image cell row * n + j is store cell row * G + list[j].  A group image holds zero counters.
+// (SnapGroupList below): image cell row * n + j is store cell row * G + list[j].  A group image holds zero counters.
 #pragma once
 #include "snapshot_common.h"
 
@@ -79,21 +79,9 @@ constexpr uint8_t PS_INIT_TOK_BYTE = 0xFF;                   // create fills byt
 constexpr uint32_t PS_INIT_TOK = 0x01010101u * PS_INIT_TOK_BYTE, PS_INIT_WORD = 0;
 static_assert(PS_INIT_TOK == PS_NULL && PS_INIT_WORD == 0, "a new cell is a null cell");
 
-// ---- which group of the store an image position holds -------------------------------------------------------------------
-// An image has its own group index (position x, stride A.geo.G = its n_groups) and the store has its own (group g, stride
-// A.v.G).  For a whole-store image they are one and the same; an image of "these n groups, in this order" is the image of an
-// n-group store whose group x is group list[x] of this one: the same format, tiles, bases, lane prefix and cell_off run over list
-// positions, and the store side is a gather or scatter.  The bodies below take the map as a parameter; with PsSnapAllGroups they
-// are what they were.  WHOLE = false: the five counters do not travel (zero in the image, the target's left alone).
-struct PsSnapAllGroups {
-    static constexpr bool WHOLE = true;
-    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
-};
-struct PsSnapGroupList {
-    static constexpr bool WHOLE = false;
-    const uint32_t *__restrict__ list;                           // [n], every entry < v.G, none twice (the host has checked)
-    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
-};
+// ---- which group of the store an image position holds: snapshot_common.h's SnapAllGroups / SnapGroupList (here the lane
+// prefix and cell_off run over list positions too; the positions are always A.geo.G, so the bodies do not ask the map for n) ----
+// What a group image does not carry (WHOLE = false): the five counters (zero in the image, the target's left alone).
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // Two launches each way, no host read-back between them.
@@ -242,14 +230,14 @@ __device__ __forceinline__ void pssnap_head_all(const PsSnapArgs &A, const Map &
     }
 }
 template <bool PACK>
-__global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) { pssnap_head_all<PACK>(A, PsSnapAllGroups{}); }
+__global__ __launch_bounds__(256) void ps_snap_head(const PsSnapArgs A) { pssnap_head_all<PACK>(A, SnapAllGroups{}); }
 // group x of the image (A.geo.G = n groups) <-> group list[x] of the store; fresh (a load only): no image, the listed groups'
 // cells as a new store holds them (A carries the geometry of n groups and no buffers)
 template <bool PACK>
 __global__ __launch_bounds__(256) void ps_snap_head_groups(const PsSnapArgs A, const uint32_t *list, int fresh) {
-    if constexpr (PACK) pssnap_head_all<true>(A, PsSnapGroupList{list});
-    else if (fresh) pssnap_head_all<false, PsSnapGroupList, true>(A, PsSnapGroupList{list});
-    else pssnap_head_all<false>(A, PsSnapGroupList{list});
+    if constexpr (PACK) pssnap_head_all<true>(A, SnapGroupList{list});
+    else if (fresh) pssnap_head_all<false, SnapGroupList, true>(A, SnapGroupList{list});
+    else pssnap_head_all<false>(A, SnapGroupList{list});
 }
 
 // the low nb bytes of a word, the rest zero
@@ -301,8 +289,8 @@ __device__ __forceinline__ void pssnap_bytes_all(const PsSnapArgs &A, const Map 
     }
 }
 template <bool PACK>
-__global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) { pssnap_bytes_all<PACK>(A, PsSnapAllGroups{}); }
+__global__ __launch_bounds__(256) void ps_snap_bytes(const PsSnapArgs A) { pssnap_bytes_all<PACK>(A, SnapAllGroups{}); }
 template <bool PACK>
-__global__ __launch_bounds__(256) void ps_snap_bytes_groups(const PsSnapArgs A, const uint32_t *list) { pssnap_bytes_all<PACK>(A, PsSnapGroupList{list}); }
+__global__ __launch_bounds__(256) void ps_snap_bytes_groups(const PsSnapArgs A, const uint32_t *list) { pssnap_bytes_all<PACK>(A, SnapGroupList{list}); }
 
 }  // namespace smr

@@ -1737,180 +1737,122 @@ int smr_raft_cluster_tick(smr_raft_leader *leader, const uint32_t *n_new_dev, ui
  * two handler calls, by one kernel each, while the other replicas of its cluster go on. */
 }  // extern "C"
 
-struct smr_raft_snapshot {
+struct smr_raft_snapshot : SnapObj<RaftSnapHdr, 2> {             // cap: entries, Reconstruct queue records
     uint32_t G = 0;
     uint8_t R = 0, me = 0, commit_extra = 0, craft = 0, ft = 0, rep_thr = 0;
-    SnapBuf buf;
-    uint64_t cap_e = 0, cap_rq = 0;                              // records the device buffer's sections have room for
-    RaftSnapHdr hdr;                                             // the image's header, once buf.hdr_known
-    SnapGroupListBuf glist;                                      // smr_raft_save_groups / smr_raft_load_groups: the list on the device
 };
 
 namespace smr {
-static const char *const RSNAP = "raft snapshot: ";
 static RaftSnapGeom rsnap_geom_of(const smr_raft_snapshot *s) { return rsnap_geom(s->G, s->R, s->craft != 0); }
-static RaftSnapImg rsnap_img(const smr_raft_snapshot *s) { return RaftSnapImg{s->buf.dev, s->cap_e, s->cap_rq}; }
-static int rsnap_alloc(smr_raft_snapshot *s, uint64_t cap_e, uint64_t cap_rq) {
-    s->cap_e = cap_e; s->cap_rq = cap_rq;
-    return snap_buf_alloc(s->buf, rsnap_dev_bytes(rsnap_geom_of(s), rsnap_img(s)), RSNAP);
-}
-// room for the worst case of a replica with l's window: every ring row live, a full Reconstruct queue.  A save can then never
-// find the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica
-// with a larger window is saved into it.
-static int rsnap_room(smr_raft_snapshot *s, const smr_raft_leader *l) {
-    const uint64_t ne = (uint64_t)s->G * l->cfg.window, nq = s->craft ? (uint64_t)s->G * CRAFT_RQ : 0;
-    if (s->buf.dev && ne <= s->cap_e && nq <= s->cap_rq) return SMR_OK;
-    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
-    return rsnap_alloc(s, ne > s->cap_e ? ne : s->cap_e, nq > s->cap_rq ? nq : s->cap_rq);
-}
-// the image's header on the host (synchronises once after a save)
-static int rsnap_header(smr_raft_snapshot *s) {
-    return snap_buf_header(s->buf, s->hdr, RSNAP, [s](const RaftSnapHdr &h) { return h.n_entries <= s->cap_e && h.n_rq <= s->cap_rq; });
-}
-// the image of header h between the device buffer (sections at their capacities) and packed host bytes; plain Raft has the
-// entry terms alone
-static int rsnap_copy(const smr_raft_snapshot *s, uint8_t *host, const RaftSnapHdr &h, bool to_host) {
-    const RaftSnapGeom q = rsnap_geom_of(s);
-    const RaftSnapImg S = rsnap_img(s);
-    const uint64_t rq = s->craft ? h.n_rq * sizeof(RaftSnapRq) : 0, mask = s->craft ? h.n_entries : 0;
-    return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
-                              {{q.fixed, h.n_entries * 8, h.n_entries * 8}, {rsnap_off_rq(q, S), rq, rq}, {rsnap_off_mask(q, S), mask, snap_a8(mask)}});
-}
+static RaftSnapImg rsnap_img(const smr_raft_snapshot *s) { return RaftSnapImg{s->buf.dev, s->cap[0], s->cap[1]}; }
 // made for a replica like l, whatever its n_groups (a snapshot of chosen groups has its own)
 static bool rsnap_like_kind(const smr_raft_snapshot *s, const smr_raft_leader *l) {
     return s->R == l->cfg.population && s->me == l->cfg.leader_id && s->commit_extra == l->cfg.commit_extra &&
            (s->craft != 0) == l->craft && (!l->craft || (s->ft == l->cv.ft && s->rep_thr == l->cv.rep_thr));
 }
-static bool rsnap_like(const smr_raft_snapshot *s, const smr_raft_leader *l) { return s->G == l->cfg.n_groups && rsnap_like_kind(s, l); }
 static bool rsnap_hdr_like(const RaftSnapHdr &h, const smr_raft_snapshot *s) {
     return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.commit_extra == s->commit_extra && h.variant == s->craft &&
            h.fault_tolerance == s->ft && h.repeat_threshold == s->rep_thr;
 }
 static const char *const RSNAP_OTHER = "another n_groups / population / replica id / commit_extra / variant (plain or CRaft, fault_tolerance, repeat_threshold)";
 
-// the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
-static int rsnap_setup(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, bool load, RaftSnapArgs &A) {
-    if (int rc = snap_pairs_check(n, reps, snaps, RSNAP, [&](uint32_t k) {
-            const smr_raft_leader *l = reps[k];
-            const smr_raft_snapshot *s = snaps[k];
-            if (l->v.G != reps[0]->v.G || l->v.R != reps[0]->v.R || l->craft != reps[0]->craft)
-                return fail(SMR_ERR_ARG, "raft snapshot: the replicas differ in groups / population / variant");
-            if (l->device != reps[0]->device || s->buf.device != l->device) return fail(SMR_ERR_ARG, "raft snapshot: a replica or snapshot lives on another device");
-            if (!rsnap_like(s, l)) return fail(SMR_ERR_ARG, std::string("raft snapshot: made for ") + RSNAP_OTHER);
-            if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, "raft snapshot: a replica has no device copy of its view");
-            return (int)SMR_OK;
-        })) return rc;
-    memset(&A, 0, sizeof(A));
-    for (uint32_t k = 0; k < n; k++) {
-        smr_raft_leader *l = reps[k];
-        smr_raft_snapshot *s = snaps[k];
-        if (load) {
-            if (int rc = rsnap_header(s)) return rc;
-            const RaftSnapHdr &h = s->hdr;
-            if (!rsnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("raft snapshot: the image is of ") + RSNAP_OTHER);
-            if (h.max_live > l->cfg.window)
-                return fail(SMR_ERR_ARG, "raft snapshot: a log of " + std::to_string(h.max_live) + " live entries does not fit window " + std::to_string(l->cfg.window));
-        } else if (int rc = rsnap_room(s, l)) return rc;
+// what is Raft's own of a snapshot object and its calls (snapshot_common.h: SnapObj)
+struct RaftSnap {
+    static constexpr const char *WHAT = "raft snapshot: ", *GWHAT = "raft groups: ", *NOUN = "replica", *LIST_OF = "";
+    static constexpr bool LIST_FIRST = false;
+    static uint32_t groups_of(const smr_raft_leader *l) { return l->cfg.n_groups; }
+    static int init(smr_raft_snapshot *s, const smr_raft_leader *like) {
+        s->R = like->cfg.population; s->me = like->cfg.leader_id; s->commit_extra = like->cfg.commit_extra;
+        s->craft = like->craft ? 1 : 0; s->ft = like->craft ? (uint8_t)like->cv.ft : 0; s->rep_thr = like->craft ? (uint8_t)like->cv.rep_thr : 0;
+        s->buf.device = like->device;
+        return SMR_OK;
     }
-    A.geo = rsnap_geom(reps[0]->v.G, reps[0]->v.R, reps[0]->craft);
-    for (uint32_t k = 0; k < n; k++) {
-        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.img[k] = snaps[k]->buf.dev; A.cap_e[k] = snaps[k]->cap_e; A.cap_rq[k] = snaps[k]->cap_rq;
-        A.commit_extra[k] = reps[k]->cfg.commit_extra;
+    // every ring row live, a full Reconstruct queue
+    static void need(const smr_raft_snapshot *s, const smr_raft_leader *l, uint64_t (&n)[2]) {
+        n[0] = (uint64_t)s->G * l->cfg.window; n[1] = s->craft ? (uint64_t)s->G * CRAFT_RQ : 0;
     }
-    return SMR_OK;
-}
-
-// ---- chosen groups between replica objects (raft_snapshot.h: the same image, the same bodies, through a group list) ----------
-static const char *const RGROUPS = "raft groups: ";
-enum RGroupsCall { RG_SAVE, RG_LOAD, RG_RESET };
-// the arguments of the one launch over n_reps replicas for the n listed groups (one list for all of them); every check before
-// anything is written, allocated or launched.  A reset has no snapshots
-static int rgroups_setup(uint32_t n_reps, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, const uint32_t *groups, uint32_t n,
-                         RGroupsCall call, RaftSnapArgs &A, RaftSnapGroups &L) {
-    if (!groups) return fail(SMR_ERR_ARG, "raft groups: null argument");
-    const auto replica = [&](uint32_t k) {
+    static void counts(const RaftSnapHdr &h, uint64_t (&n)[2]) { n[0] = h.n_entries; n[1] = h.n_rq; }
+    static uint64_t dev_bytes(const smr_raft_snapshot *s) { return rsnap_dev_bytes(rsnap_geom_of(s), rsnap_img(s)); }
+    // plain Raft has the entry terms alone
+    static int copy(const smr_raft_snapshot *s, uint8_t *host, const RaftSnapHdr &h, bool to_host) {
+        const RaftSnapGeom q = rsnap_geom_of(s);
+        const RaftSnapImg S = rsnap_img(s);
+        const uint64_t rq = s->craft ? h.n_rq * sizeof(RaftSnapRq) : 0, mask = s->craft ? h.n_entries : 0;
+        return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
+                                  {{q.fixed, h.n_entries * 8, h.n_entries * 8}, {rsnap_off_rq(q, S), rq, rq}, {rsnap_off_mask(q, S), mask, snap_a8(mask)}});
+    }
+    static int load_fits(const smr_raft_snapshot *s, const smr_raft_leader *l, const char *what, bool) {
+        if (!rsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + RSNAP_OTHER);
+        if (s->hdr.max_live > l->cfg.window)
+            return fail(SMR_ERR_ARG, std::string(what) + "a log of " + std::to_string(s->hdr.max_live) + " live entries does not fit window " + std::to_string(l->cfg.window));
+        return SMR_OK;
+    }
+    static int replica_check(smr_raft_leader *const *reps, uint32_t k, const char *what) {
         const smr_raft_leader *l = reps[k];
         if (l->v.G != reps[0]->v.G || l->v.R != reps[0]->v.R || l->craft != reps[0]->craft)
-            return fail(SMR_ERR_ARG, "raft groups: the replicas differ in groups / population / variant");
-        if (l->device != reps[0]->device) return fail(SMR_ERR_ARG, "raft groups: a replica lives on another device");
-        if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, "raft groups: a replica has no device copy of its view");
-        return (int)SMR_OK;
-    };
-    if (call == RG_RESET) {                                      // (no snapshots: the replicas stand in for them in the pairs' check)
-        if (int rc = snap_pairs_check(n_reps, reps, reps, RGROUPS, replica)) return rc;
-    } else if (int rc = snap_pairs_check(n_reps, reps, snaps, RGROUPS, [&](uint32_t k) {
-                   if (int rc2 = replica(k)) return rc2;
-                   const smr_raft_snapshot *s = snaps[k];
-                   if (s->buf.device != reps[k]->device) return fail(SMR_ERR_ARG, "raft groups: a snapshot lives on another device");
-                   if (!rsnap_like_kind(s, reps[k])) return fail(SMR_ERR_ARG, "raft groups: the snapshot was made for another population / replica id / commit_extra / variant (plain or CRaft, fault_tolerance, repeat_threshold)");
-                   if (s->G != n) return fail(SMR_ERR_ARG, "raft groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
-                   return (int)SMR_OK;
-               })) return rc;
-    if (int rc = snap_glist_check(groups, n, reps[0]->v.G, RGROUPS)) return rc;
-    if (call == RG_LOAD)
-        for (uint32_t k = 0; k < n_reps; k++) {
-            smr_raft_snapshot *s = snaps[k];
-            if (int rc = rsnap_header(s)) return rc;
-            if (!rsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string("raft groups: the image is of ") + RSNAP_OTHER);
-            if (s->hdr.max_live > reps[k]->cfg.window)
-                return fail(SMR_ERR_ARG, "raft groups: a log of " + std::to_string(s->hdr.max_live) + " live entries does not fit window " +
-                                             std::to_string(reps[k]->cfg.window));
-        }
-    if (call == RG_SAVE)
-        for (uint32_t k = 0; k < n_reps; k++)
-            if (int rc = rsnap_room(snaps[k], reps[k])) return rc;
-    memset(&A, 0, sizeof(A));
-    memset(&L, 0, sizeof(L));
-    A.geo = rsnap_geom(n, reps[0]->v.R, reps[0]->craft);        // the geometry of an n-group replica
-    for (uint32_t k = 0; k < n_reps; k++) {
-        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.commit_extra[k] = reps[k]->cfg.commit_extra;
-        if (call != RG_RESET) { A.img[k] = snaps[k]->buf.dev; A.cap_e[k] = snaps[k]->cap_e; A.cap_rq[k] = snaps[k]->cap_rq; }
-        L.init_term[k] = reps[k]->cfg.term;
+            return fail(SMR_ERR_ARG, std::string(what) + "the replicas differ in groups / population / variant");
+        return SMR_OK;
     }
+    static int view_check(const smr_raft_leader *l, const char *what) {
+        if (!l->d_view || !l->d_view_ok || !l->d_cv) return fail(SMR_ERR_STATE, std::string(what) + "a replica has no device copy of its view");
+        return SMR_OK;
+    }
+    static int pair_check(smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, uint32_t k) {
+        const smr_raft_leader *l = reps[k];
+        const smr_raft_snapshot *s = snaps[k];
+        if (int rc = replica_check(reps, k, WHAT)) return rc;
+        if (l->device != reps[0]->device || s->buf.device != l->device) return fail(SMR_ERR_ARG, "raft snapshot: a replica or snapshot lives on another device");
+        if (s->G != l->cfg.n_groups || !rsnap_like_kind(s, l)) return fail(SMR_ERR_ARG, std::string("raft snapshot: made for ") + RSNAP_OTHER);
+        return view_check(l, WHAT);
+    }
+    static int groups_pair_check(smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, uint32_t k, uint32_t n, SnapGroupsCall call) {
+        if (int rc = replica_check(reps, k, GWHAT)) return rc;
+        if (reps[k]->device != reps[0]->device) return fail(SMR_ERR_ARG, "raft groups: a replica lives on another device");
+        if (int rc = view_check(reps[k], GWHAT)) return rc;
+        if (call == SNAP_GROUPS_RESET) return SMR_OK;
+        const smr_raft_snapshot *s = snaps[k];
+        if (s->buf.device != reps[k]->device) return fail(SMR_ERR_ARG, "raft groups: a snapshot lives on another device");
+        if (!rsnap_like_kind(s, reps[k])) return fail(SMR_ERR_ARG, "raft groups: the snapshot was made for another population / replica id / commit_extra / variant (plain or CRaft, fault_tolerance, repeat_threshold)");
+        return snap_groups_len_check(n, s->G, GWHAT);
+    }
+};
+
+// the arguments of the one launch over n replicas (snaps = nullptr: a reset); G: the geometry's groups
+static void rsnap_args(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, uint32_t G, RaftSnapArgs &A) {
+    memset(&A, 0, sizeof(A));
+    A.geo = rsnap_geom(G, reps[0]->v.R, reps[0]->craft);
+    for (uint32_t k = 0; k < n; k++) {
+        A.rv[k] = reps[k]->d_view; A.cv[k] = reps[k]->d_cv; A.commit_extra[k] = reps[k]->cfg.commit_extra;
+        if (snaps) { A.img[k] = snaps[k]->buf.dev; A.cap_e[k] = snaps[k]->cap[0]; A.cap_rq[k] = snaps[k]->cap[1]; }
+    }
+}
+// ---- chosen groups between replica objects (raft_snapshot.h: the same image, the same bodies, through a group list) ----------
+// the list on its way, and the launch's second argument: the list and the terms a reset starts from
+static int rgroups_list(uint32_t n_reps, smr_raft_leader *const *reps, SnapGroupListBuf &b, const uint32_t *groups, uint32_t n, hipStream_t st, RaftSnapGroups &L) {
+    if (int rc = snap_glist_upload(b, groups, n, st, RaftSnap::GWHAT)) return rc;
+    memset(&L, 0, sizeof(L));
+    L.list = b.dev;
+    for (uint32_t k = 0; k < n_reps; k++) L.init_term[k] = reps[k]->cfg.term;
     return SMR_OK;
 }
 }  // namespace smr
 
 extern "C" {
 
-// a snapshot object for n groups of a replica like `like` (n = its n_groups: the whole replica)
-static int rsnap_create(const smr_raft_leader *like, uint32_t n, smr_raft_snapshot **out) {
-    smr_raft_snapshot *s = new smr_raft_snapshot();
-    s->G = n; s->R = like->cfg.population; s->me = like->cfg.leader_id; s->commit_extra = like->cfg.commit_extra;
-    s->craft = like->craft ? 1 : 0; s->ft = like->craft ? (uint8_t)like->cv.ft : 0; s->rep_thr = like->craft ? (uint8_t)like->cv.rep_thr : 0;
-    s->buf.device = like->device;
-    memset(&s->hdr, 0, sizeof(s->hdr));
-    if (int rc = rsnap_room(s, like)) { delete s; return rc; }
-    *out = s;
-    return SMR_OK;
-}
-
-int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
-    return rsnap_create(like, like->cfg.n_groups, out);
-}
-
-int smr_raft_snapshot_create_groups(const smr_raft_leader *like, uint32_t n, smr_raft_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "raft groups: null argument");
-    if (n == 0 || n > like->cfg.n_groups)
-        return fail(SMR_ERR_ARG, "raft groups: a snapshot of " + std::to_string(n) + " groups of a replica of " + std::to_string(like->cfg.n_groups));
-    smr_raft_snapshot *s = nullptr;
-    if (int rc = rsnap_create(like, n, &s)) return rc;
-    if (int rc = snap_glist_room(s->glist, n, RGROUPS)) { smr_raft_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
-    *out = s;
-    return SMR_OK;
-}
+int smr_raft_snapshot_create(const smr_raft_leader *like, smr_raft_snapshot **out) { return snap_obj_create<RaftSnap>(like, out); }
+int smr_raft_snapshot_create_groups(const smr_raft_leader *like, uint32_t n, smr_raft_snapshot **out) { return snap_obj_create_groups<RaftSnap>(like, n, out); }
+void smr_raft_snapshot_destroy(smr_raft_snapshot *s) { snap_obj_destroy(s); }
 
 int smr_raft_cluster_save_groups(uint32_t n_reps, smr_raft_leader *const *reps, const uint32_t *groups_host, uint32_t n, smr_raft_snapshot *const *snaps,
                                  void *stream) {
     RaftSnapArgs A;
     RaftSnapGroups L;
-    if (int rc = rgroups_setup(n_reps, reps, snaps, groups_host, n, RG_SAVE, A, L)) return rc;
-    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RGROUPS)) return rc;
-    L.list = snaps[0]->glist.dev;
+    if (int rc = snap_groups_setup<RaftSnap>(n_reps, reps, snaps, groups_host, n, SNAP_GROUPS_SAVE)) return rc;
+    if (int rc = rgroups_list(n_reps, reps, snaps[0]->glist, groups_host, n, (hipStream_t)stream, L)) return rc;
+    rsnap_args(n_reps, reps, snaps, n, A);
     hipLaunchKernelGGL(raft_snap_pack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, L);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n_reps; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    for (uint32_t k = 0; k < n_reps; k++) snap_obj_saved(snaps[k]);
     return SMR_OK;
 }
 
@@ -1919,9 +1861,9 @@ int smr_raft_cluster_load_groups(uint32_t n_reps, smr_raft_leader *const *reps, 
     smr_raft_snapshot *const *snaps = const_cast<smr_raft_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
     RaftSnapArgs A;
     RaftSnapGroups L;
-    if (int rc = rgroups_setup(n_reps, reps, snaps, groups_host, n, RG_LOAD, A, L)) return rc;
-    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RGROUPS)) return rc;
-    L.list = snaps[0]->glist.dev;
+    if (int rc = snap_groups_setup<RaftSnap>(n_reps, reps, snaps, groups_host, n, SNAP_GROUPS_LOAD)) return rc;
+    if (int rc = rgroups_list(n_reps, reps, snaps[0]->glist, groups_host, n, (hipStream_t)stream, L)) return rc;
+    rsnap_args(n_reps, reps, snaps, n, A);
     hipLaunchKernelGGL(raft_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, L, 0);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1930,9 +1872,9 @@ int smr_raft_cluster_load_groups(uint32_t n_reps, smr_raft_leader *const *reps, 
 int smr_raft_cluster_reset_groups(uint32_t n_reps, smr_raft_leader *const *reps, const uint32_t *groups_host, uint32_t n, void *stream) {
     RaftSnapArgs A;
     RaftSnapGroups L;
-    if (int rc = rgroups_setup(n_reps, reps, nullptr, groups_host, n, RG_RESET, A, L)) return rc;
-    if (int rc = snap_glist_upload(reps[0]->glist, groups_host, n, (hipStream_t)stream, RGROUPS)) return rc;
-    L.list = reps[0]->glist.dev;
+    if (int rc = snap_groups_setup<RaftSnap>(n_reps, reps, (smr_raft_snapshot *const *)nullptr, groups_host, n, SNAP_GROUPS_RESET)) return rc;
+    if (int rc = rgroups_list(n_reps, reps, reps[0]->glist, groups_host, n, (hipStream_t)stream, L)) return rc;
+    rsnap_args(n_reps, reps, nullptr, n, A);
     hipLaunchKernelGGL(raft_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, L, 1);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1953,25 +1895,21 @@ int smr_raft_reset_groups(smr_raft_leader *l, const uint32_t *groups_host, uint3
     return smr_raft_cluster_reset_groups(1, &l, groups_host, n, stream);
 }
 
-void smr_raft_snapshot_destroy(smr_raft_snapshot *s) {
-    if (!s) return;
-    snap_buf_free(s->buf);
-    if (s->glist.dev) (void)hipFree(s->glist.dev);               // (snap_buf_free has synchronised)
-    delete s;
-}
-
 int smr_raft_cluster_save_state(uint32_t n, smr_raft_leader *const *reps, smr_raft_snapshot *const *snaps, void *stream) {
     RaftSnapArgs A;
-    if (int rc = rsnap_setup(n, reps, snaps, false, A)) return rc;
+    if (int rc = snap_cluster_setup<RaftSnap>(n, reps, snaps, false)) return rc;
+    rsnap_args(n, reps, snaps, reps[0]->v.G, A);
     hipLaunchKernelGGL(raft_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    for (uint32_t k = 0; k < n; k++) snap_obj_saved(snaps[k]);
     return SMR_OK;
 }
 
-int smr_raft_cluster_load_state(uint32_t n, smr_raft_leader *const *reps, const smr_raft_snapshot *const *snaps, void *stream) {
-    RaftSnapArgs A;                                              // (a snapshot's header is read back and cached on first use)
-    if (int rc = rsnap_setup(n, reps, const_cast<smr_raft_snapshot *const *>(snaps), true, A)) return rc;
+int smr_raft_cluster_load_state(uint32_t n, smr_raft_leader *const *reps, const smr_raft_snapshot *const *csnaps, void *stream) {
+    smr_raft_snapshot *const *snaps = const_cast<smr_raft_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
+    RaftSnapArgs A;
+    if (int rc = snap_cluster_setup<RaftSnap>(n, reps, snaps, true)) return rc;
+    rsnap_args(n, reps, snaps, reps[0]->v.G, A);
     hipLaunchKernelGGL(raft_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1995,11 +1933,8 @@ int smr_raft_debug_arena_view(smr_raft_leader *l, void **base_dev, uint64_t *n_b
 }
 
 int smr_raft_snapshot_info_get(const smr_raft_snapshot *cs, smr_raft_snapshot_info *out) {
-    if (!cs || !out) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
-    smr_raft_snapshot *s = const_cast<smr_raft_snapshot *>(cs);
-    if (int rc = rsnap_header(s)) return rc;
-    const RaftSnapHdr &h = s->hdr;
-    memset(out, 0, sizeof(*out));
+    if (int rc = snap_obj_info<RaftSnap>(cs, out)) return rc;
+    const RaftSnapHdr &h = cs->hdr;
     out->bytes = h.bytes; out->n_entries = h.n_entries; out->n_reconstructs = h.n_rq;
     out->n_groups = h.n_groups; out->max_live = h.max_live; out->max_reconstructs = h.max_rq;
     out->population = h.population; out->replica_id = h.me; out->commit_extra = h.commit_extra; out->craft = h.variant;
@@ -2007,20 +1942,12 @@ int smr_raft_snapshot_info_get(const smr_raft_snapshot *cs, smr_raft_snapshot_in
     return SMR_OK;
 }
 
-int64_t smr_raft_snapshot_export(const smr_raft_snapshot *cs, uint8_t *host, uint64_t cap) {
-    if (!cs || !host) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
-    smr_raft_snapshot *s = const_cast<smr_raft_snapshot *>(cs);
-    if (int rc = rsnap_header(s)) return rc;
-    const RaftSnapHdr &h = s->hdr;
-    if (cap < h.bytes) return fail(SMR_ERR_ARG, "raft snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    if (int rc = rsnap_copy(s, host, h, true)) return rc;
-    return (int64_t)h.bytes;
-}
+int64_t smr_raft_snapshot_export(const smr_raft_snapshot *cs, uint8_t *host, uint64_t cap) { return snap_obj_export<RaftSnap>(cs, host, cap); }
 
 int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "raft snapshot: null argument");
     RaftSnapHdr h;
-    if (int rc = snap_import_prologue(host, len, RSNAP_MAGIC, RSNAP_VERSION, RSNAP, h)) return rc;
+    if (int rc = snap_import_prologue(host, len, RSNAP_MAGIC, RSNAP_VERSION, RaftSnap::WHAT, h)) return rc;
     if (h.me >= h.population) return fail(SMR_ERR_ARG, "raft snapshot: the image's replica id is not below its population");
     bool res = h.reserved1 != 0;
     for (int k = 0; k < 6; k++) res = res || h.reserved0[k];
@@ -2066,13 +1993,7 @@ int smr_raft_snapshot_import(smr_raft_snapshot *s, const uint8_t *host, uint64_t
         for (uint64_t k = 0; k < h.n_entries; k++) if (p[k] >> s->R) return bad("shard bitmap of replicas beyond the population");
         if (!snap_pad_is_zero(p, 0, h.n_entries)) return bad("padding is not zero");
     }
-    if (h.n_entries > s->cap_e || h.n_rq > s->cap_rq)
-        if (int rc = rsnap_alloc(s, h.n_entries > s->cap_e ? h.n_entries : s->cap_e, h.n_rq > s->cap_rq ? h.n_rq : s->cap_rq)) return rc;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    s->buf.filled = false;
-    if (int rc = rsnap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
-    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
-    return SMR_OK;
+    return snap_obj_import_bytes<RaftSnap>(s, host, h);
 }
 
 }  // extern "C"

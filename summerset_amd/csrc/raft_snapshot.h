@@ -12,7 +12,7 @@
 // Reconstruct as after any restart).
 // Chosen groups (smr_raft_save_groups / smr_raft_load_groups / smr_raft_reset_groups and their cluster forms) go through the
 // same image and the same bodies: an image of "these n groups, in this order" is the image of an n-group replica, read and
-// written through a group list (RaftSnapGroupList below).  A group image holds zero counters, and like every image none of
+// written through a group list (SnapGroupList below).  A group image holds zero counters, and like every image none of
 // the CRaft payload store's shard bytes.
 //
 // Image (little-endian; every section starts on a multiple of 8; padding bytes are zero):
@@ -140,26 +140,9 @@ SMR_HD uint64_t craft_init_hb_replied(bool peer) { return peer ? 1ull : 0ull; }
 SMR_HD uint8_t craft_init_bits(uint32_t R) { return (uint8_t)((1u << R) - 1u); }   // alive, and a ring row's shard bitmap
 static_assert(RAFT_INIT_WORD == 0, "create fills bytes");
 
-// ---- which group of the replica an image position holds -----------------------------------------------------------------
-// An image has its own group index (position x, stride n = its n_groups, lane = x & 63) and the replica has its own (group g,
-// stride v.G).  For a whole-replica image they are one and the same; an image of "these n groups, in this order"
-// (smr_raft_save_groups / smr_raft_load_groups) is the image of an n-group replica whose group x is group list[x] of this one:
-// the same format, the same tiles, bases and placement run over list positions, and the replica side a gather or scatter.
-// The bodies below take the map as a parameter; with RaftSnapAllGroups they are what they were.
-// What a group image does not carry (WHOLE = false): the eight counters.  They are the replica object's reporting, not a
-// group's state -- events stay counted where they happened, so the sum over objects is conserved.  The image's counters are
-// zero, and a load through a list leaves the target's alone.
-struct RaftSnapAllGroups {
-    static constexpr bool WHOLE = true;
-    __device__ __forceinline__ uint32_t n(const RaftView &v, const RaftSnapGeom &) const { return v.G; }
-    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
-};
-struct RaftSnapGroupList {
-    static constexpr bool WHOLE = false;
-    const uint32_t *__restrict__ list;                           // [n], every entry < v.G, none twice (the host has checked)
-    __device__ __forceinline__ uint32_t n(const RaftView &, const RaftSnapGeom &Q) const { return Q.G; }
-    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
-};
+// ---- which group of the replica an image position holds: snapshot_common.h's SnapAllGroups / SnapGroupList -----------------
+// What a group image does not carry (WHOLE = false): the eight counters.  The image's counters are zero, and a load through a
+// list leaves the target's alone.
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1); the replicas are reached
@@ -236,7 +219,7 @@ __device__ __forceinline__ void rsnap_pack_all(const RaftSnapArgs &A, const Map 
     const RaftSnapImg &S = X.S;
     const bool craft = Q.craft != 0;
     const RaftSnapScal sc = rsnap_scal(S.base, Q);
-    const uint32_t nx = M.n(v, Q);
+    const uint32_t nx = M.n(v.G, Q.G);
     const SnapWave w = snap_wave(Q.tiles, nx);
     const size_t G = v.G, NX = nx;
     uint64_t base[2];                                            // entries, queue records in front
@@ -320,7 +303,7 @@ __device__ __forceinline__ void rsnap_unpack_all(const RaftSnapArgs &A, const Ma
     const RaftSnapImg &S = X.S;
     const bool craft = Q.craft != 0;
     const RaftSnapScal sc = rsnap_scal(S.base, Q);
-    const uint32_t nx = M.n(v, Q);
+    const uint32_t nx = M.n(v.G, Q.G);
     const SnapWave w = snap_wave(Q.tiles, nx);
     const size_t G = v.G, NX = nx;
     uint64_t base[2] = {0, 0};
@@ -395,17 +378,17 @@ __device__ __forceinline__ void rsnap_unpack_all(const RaftSnapArgs &A, const Ma
     if (Map::WHOLE) snap_counters_load<(int)SMR_CTR_STRIDE>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
 }
 
-__global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) { rsnap_pack_all(A, RaftSnapAllGroups{}); }
-__global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) { rsnap_unpack_all<RaftSnapAllGroups, false>(A, RaftSnapAllGroups{}, 0); }
+__global__ __launch_bounds__(256) void raft_snap_pack(const RaftSnapArgs A) { rsnap_pack_all(A, SnapAllGroups{}); }
+__global__ __launch_bounds__(256) void raft_snap_unpack(const RaftSnapArgs A) { rsnap_unpack_all<SnapAllGroups, false>(A, SnapAllGroups{}, 0); }
 // group x of the image (A.geo.G = n groups) <-> group list[x] of the replica; fresh: no image, the listed groups as a new
 // replica object holds them (A carries the geometry of n groups and no buffers)
-__global__ __launch_bounds__(256) void raft_snap_pack_groups(const RaftSnapArgs A, const RaftSnapGroups L) { rsnap_pack_all(A, RaftSnapGroupList{L.list}); }
+__global__ __launch_bounds__(256) void raft_snap_pack_groups(const RaftSnapArgs A, const RaftSnapGroups L) { rsnap_pack_all(A, SnapGroupList{L.list}); }
 __global__ __launch_bounds__(256) void raft_snap_unpack_groups(const RaftSnapArgs A, const RaftSnapGroups L, int fresh) {
     uint64_t term = 0;
 #pragma unroll
     for (int k = 0; k < (int)RMAX; k++) if (blockIdx.y == (unsigned)k) term = L.init_term[k];
-    if (fresh) rsnap_unpack_all<RaftSnapGroupList, true>(A, RaftSnapGroupList{L.list}, term);
-    else rsnap_unpack_all<RaftSnapGroupList, false>(A, RaftSnapGroupList{L.list}, term);
+    if (fresh) rsnap_unpack_all<SnapGroupList, true>(A, SnapGroupList{L.list}, term);
+    else rsnap_unpack_all<SnapGroupList, false>(A, SnapGroupList{L.list}, term);
 }
 
 }  // namespace smr

@@ -946,170 +946,97 @@ int smr_rsp_exec_poll(smr_rsp_replica *e, uint32_t *group_host, uint32_t *slot_h
  * calls, by one kernel each, while the other replicas of its cluster go on. */
 }  // extern "C"
 
-struct smr_rsp_snapshot {
+struct smr_rsp_snapshot : SnapObj<RspSnapHdr, 2> {               // cap: instance records, execution-list entries
     uint32_t G = 0;
     uint8_t R = 0, me = 0, ft = 0;
-    SnapBuf buf;
-    uint64_t cap_s = 0, cap_x = 0;                               // records the device buffer's sections have room for
-    RspSnapHdr hdr;                                              // the image's header, once buf.hdr_known
-    SnapGroupListBuf glist;                                      // smr_rsp_save_groups / smr_rsp_load_groups: the list on the device
 };
 
 namespace smr {
-static const char *const RSPSNAP = "rspaxos snapshot: ";
 static RspSnapGeom rspsnap_geom_of(const smr_rsp_snapshot *s) { return rspsnap_geom(s->G, s->R); }
-static RspSnapImg rspsnap_img(const smr_rsp_snapshot *s) { return RspSnapImg{s->buf.dev, s->cap_s, s->cap_x}; }
-static int rspsnap_alloc(smr_rsp_snapshot *s, uint64_t cap_s, uint64_t cap_x) {
-    s->cap_s = cap_s; s->cap_x = cap_x;
-    return snap_buf_alloc(s->buf, rspsnap_dev_bytes(rspsnap_geom_of(s), rspsnap_img(s)), RSPSNAP);
-}
-// room for the worst case of a replica with e's window: every ring row live, a full execution list.  A save can then never find
-// the snapshot too small, so it stays a call that only enqueues.  Grows (host-known sizes: no read-back) when a replica with a
-// larger window is saved into it.
-static int rspsnap_room(smr_rsp_snapshot *s, const smr_rsp_replica *e) {
-    const uint64_t n = (uint64_t)s->G * e->cfg.window;
-    if (s->buf.dev && n <= s->cap_s && n <= s->cap_x) return SMR_OK;
-    s->buf.filled = false; s->buf.hdr_known = false;             // (what it held goes with the old buffer)
-    return rspsnap_alloc(s, n > s->cap_s ? n : s->cap_s, n > s->cap_x ? n : s->cap_x);
-}
-// the image's header on the host (synchronises once after a save)
-static int rspsnap_header(smr_rsp_snapshot *s) {
-    return snap_buf_header(s->buf, s->hdr, RSPSNAP, [s](const RspSnapHdr &h) { return h.n_slots <= s->cap_s && h.n_exec <= s->cap_x; });
-}
-// the image of header h between the device buffer (sections at their capacities) and packed host bytes
-static int rspsnap_copy(const smr_rsp_snapshot *s, uint8_t *host, const RspSnapHdr &h, bool to_host) {
-    const RspSnapGeom q = rspsnap_geom_of(s);
-    return snap_copy_sections(s->buf.dev, host, q.fixed, to_host, {{q.fixed, h.n_slots * sizeof(RspSnapSlot), h.n_slots * sizeof(RspSnapSlot)},
-                                                                  {rspsnap_off_exec(q, rspsnap_img(s)), h.n_exec * 4, snap_a8(h.n_exec * 4)}});
-}
+static RspSnapImg rspsnap_img(const smr_rsp_snapshot *s) { return RspSnapImg{s->buf.dev, s->cap[0], s->cap[1]}; }
 // made for a replica like e, whatever its n_groups (a snapshot of chosen groups has its own)
 static bool rspsnap_like_kind(const smr_rsp_snapshot *s, const smr_rsp_replica *e) {
     return s->R == e->cfg.population && s->me == e->cfg.me && s->ft == e->cfg.fault_tolerance;
 }
-static bool rspsnap_like(const smr_rsp_snapshot *s, const smr_rsp_replica *e) { return s->G == e->cfg.n_groups && rspsnap_like_kind(s, e); }
 static bool rspsnap_hdr_like(const RspSnapHdr &h, const smr_rsp_snapshot *s) {
     return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.fault_tolerance == s->ft;
 }
 static const char *const RSPSNAP_OTHER = "another n_groups / population / replica id / fault_tolerance";
 
-// the arguments of the one launch for n replicas and their snapshots; load: every check before anything is written
-static int rspsnap_setup(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, bool load, RspSnapArgs &A) {
-    if (int rc = snap_pairs_check(n, reps, snaps, RSPSNAP, [&](uint32_t k) {
-            if (reps[k]->v.G != reps[0]->v.G || reps[k]->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, "rspaxos snapshot: the replicas differ in groups / population");
-            if (!rspsnap_like(snaps[k], reps[k])) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: made for ") + RSPSNAP_OTHER);
-            return (int)SMR_OK;
-        })) return rc;
-    memset(&A, 0, sizeof(A));
-    for (uint32_t k = 0; k < n; k++) {
-        smr_rsp_replica *e = reps[k];
-        smr_rsp_snapshot *s = snaps[k];
-        if (load) {
-            if (int rc = rspsnap_header(s)) return rc;
-            const RspSnapHdr &h = s->hdr;
-            if (!rspsnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: the image is of ") + RSPSNAP_OTHER);
-            // a slot is held iff slot + W >= len: in another ring the cells around the saved span would count as held or lost
-            if (h.window != e->cfg.window)
-                return fail(SMR_ERR_ARG, "rspaxos snapshot: an image of window " + std::to_string(h.window) + " does not load into window " + std::to_string(e->cfg.window));
-        } else if (int rc = rspsnap_room(s, e)) return rc;               // (only a failed hipMalloc: the snapshots that grew before it are
-                                                                         //  then empty, SMR_ERR_STATE on use, and none holds a partial image)
+// what is RSPaxos's own of a snapshot object and its calls (snapshot_common.h: SnapObj)
+struct RspSnap {
+    static constexpr const char *WHAT = "rspaxos snapshot: ", *GWHAT = "rspaxos groups: ", *NOUN = "replica", *LIST_OF = "";
+    static constexpr bool LIST_FIRST = false;
+    static uint32_t groups_of(const smr_rsp_replica *e) { return e->cfg.n_groups; }
+    static int init(smr_rsp_snapshot *s, const smr_rsp_replica *like) {
+        s->R = like->cfg.population; s->me = like->cfg.me; s->ft = like->cfg.fault_tolerance;
+        s->buf.device = like->device;
+        return SMR_OK;
     }
-    A.geo = rspsnap_geom(reps[0]->v.G, reps[0]->v.R);
-    for (uint32_t k = 0; k < n; k++) { A.v[k] = reps[k]->v; A.img[k] = snaps[k]->buf.dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
-    return SMR_OK;
-}
+    // every ring row live, a full execution list
+    static void need(const smr_rsp_snapshot *s, const smr_rsp_replica *e, uint64_t (&n)[2]) { n[0] = n[1] = (uint64_t)s->G * e->cfg.window; }
+    static void counts(const RspSnapHdr &h, uint64_t (&n)[2]) { n[0] = h.n_slots; n[1] = h.n_exec; }
+    static uint64_t dev_bytes(const smr_rsp_snapshot *s) { return rspsnap_dev_bytes(rspsnap_geom_of(s), rspsnap_img(s)); }
+    static int copy(const smr_rsp_snapshot *s, uint8_t *host, const RspSnapHdr &h, bool to_host) {
+        const RspSnapGeom q = rspsnap_geom_of(s);
+        return snap_copy_sections(s->buf.dev, host, q.fixed, to_host, {{q.fixed, h.n_slots * sizeof(RspSnapSlot), h.n_slots * sizeof(RspSnapSlot)},
+                                                                      {rspsnap_off_exec(q, rspsnap_img(s)), h.n_exec * 4, snap_a8(h.n_exec * 4)}});
+    }
+    static int load_fits(const smr_rsp_snapshot *s, const smr_rsp_replica *e, const char *what, bool) {
+        if (!rspsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + RSPSNAP_OTHER);
+        // there is no ring_lo beside len: a slot is held iff slot + W >= len, so in another ring the cells around the saved span
+        // would count as held or lost
+        if (s->hdr.window != e->cfg.window)
+            return fail(SMR_ERR_ARG, std::string(what) + "an image of window " + std::to_string(s->hdr.window) + " does not load into window " + std::to_string(e->cfg.window));
+        return SMR_OK;
+    }
+    static int replica_check(smr_rsp_replica *const *reps, uint32_t k, const char *what) {
+        if (reps[k]->v.G != reps[0]->v.G || reps[k]->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, std::string(what) + "the replicas differ in groups / population");
+        return SMR_OK;
+    }
+    static int pair_check(smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, uint32_t k) {
+        if (int rc = replica_check(reps, k, WHAT)) return rc;
+        if (snaps[k]->G != reps[k]->cfg.n_groups || !rspsnap_like_kind(snaps[k], reps[k])) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: made for ") + RSPSNAP_OTHER);
+        return SMR_OK;
+    }
+    static int groups_pair_check(smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, uint32_t k, uint32_t n, SnapGroupsCall call) {
+        if (int rc = replica_check(reps, k, GWHAT)) return rc;
+        if (reps[k]->device != reps[0]->device) return fail(SMR_ERR_ARG, "rspaxos groups: a replica lives on another device");
+        if (call == SNAP_GROUPS_RESET) return SMR_OK;
+        const smr_rsp_snapshot *s = snaps[k];
+        if (s->buf.device != reps[k]->device) return fail(SMR_ERR_ARG, "rspaxos groups: a snapshot lives on another device");
+        if (!rspsnap_like_kind(s, reps[k])) return fail(SMR_ERR_ARG, "rspaxos groups: the snapshot was made for another population / replica id / fault_tolerance");
+        return snap_groups_len_check(n, s->G, GWHAT);
+    }
+};
 
-// ---- chosen groups between replica objects (rsp_snapshot.h: the same image, the same bodies, through a group list) -----------
-static const char *const RSPGROUPS = "rspaxos groups: ";
-enum RspGroupsCall { RSPG_SAVE, RSPG_LOAD, RSPG_RESET };
-// the arguments of the one launch over n_reps replicas for the n listed groups (one list for all of them); every check before
-// anything is written, allocated or launched.  A reset has no snapshots
-static int rspgroups_setup(uint32_t n_reps, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, const uint32_t *groups, uint32_t n,
-                           RspGroupsCall call, RspSnapArgs &A) {
-    if (!groups) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
-    const auto replica = [&](uint32_t k) {
-        const smr_rsp_replica *e = reps[k];
-        if (e->v.G != reps[0]->v.G || e->v.R != reps[0]->v.R) return fail(SMR_ERR_ARG, "rspaxos groups: the replicas differ in groups / population");
-        if (e->device != reps[0]->device) return fail(SMR_ERR_ARG, "rspaxos groups: a replica lives on another device");
-        return (int)SMR_OK;
-    };
-    if (call == RSPG_RESET) {                                    // (no snapshots: the replicas stand in for them in the pairs' check)
-        if (int rc = snap_pairs_check(n_reps, reps, reps, RSPGROUPS, replica)) return rc;
-    } else if (int rc = snap_pairs_check(n_reps, reps, snaps, RSPGROUPS, [&](uint32_t k) {
-                   if (int rc2 = replica(k)) return rc2;
-                   const smr_rsp_snapshot *s = snaps[k];
-                   if (s->buf.device != reps[k]->device) return fail(SMR_ERR_ARG, "rspaxos groups: a snapshot lives on another device");
-                   if (!rspsnap_like_kind(s, reps[k])) return fail(SMR_ERR_ARG, "rspaxos groups: the snapshot was made for another population / replica id / fault_tolerance");
-                   if (s->G != n) return fail(SMR_ERR_ARG, "rspaxos groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
-                   return (int)SMR_OK;
-               })) return rc;
-    if (int rc = snap_glist_check(groups, n, reps[0]->v.G, RSPGROUPS)) return rc;
-    if (call == RSPG_LOAD)
-        for (uint32_t k = 0; k < n_reps; k++) {
-            smr_rsp_snapshot *s = snaps[k];
-            if (int rc = rspsnap_header(s)) return rc;
-            if (!rspsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string("rspaxos groups: the image is of ") + RSPSNAP_OTHER);
-            // there is no ring_lo beside len: a slot is held iff slot + W >= len, so the window must be the image's
-            if (s->hdr.window != reps[k]->cfg.window)
-                return fail(SMR_ERR_ARG, "rspaxos groups: an image of window " + std::to_string(s->hdr.window) + " does not load into window " +
-                                             std::to_string(reps[k]->cfg.window));
-        }
-    if (call == RSPG_SAVE)
-        for (uint32_t k = 0; k < n_reps; k++)
-            if (int rc = rspsnap_room(snaps[k], reps[k])) return rc;
+// the arguments of the one launch over n replicas (snaps = nullptr: a reset); G: the geometry's groups
+static void rspsnap_args(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, uint32_t G, RspSnapArgs &A) {
     memset(&A, 0, sizeof(A));
-    A.geo = rspsnap_geom(n, reps[0]->v.R);                       // the geometry of an n-group replica
-    for (uint32_t k = 0; k < n_reps; k++) {
+    A.geo = rspsnap_geom(G, reps[0]->v.R);
+    for (uint32_t k = 0; k < n; k++) {
         A.v[k] = reps[k]->v;
-        if (call != RSPG_RESET) { A.img[k] = snaps[k]->buf.dev; A.cap_s[k] = snaps[k]->cap_s; A.cap_x[k] = snaps[k]->cap_x; }
+        if (snaps) { A.img[k] = snaps[k]->buf.dev; A.cap_s[k] = snaps[k]->cap[0]; A.cap_x[k] = snaps[k]->cap[1]; }
     }
-    return SMR_OK;
 }
 }  // namespace smr
 
 extern "C" {
 
-// a snapshot object for n groups of a replica like `like` (n = its n_groups: the whole replica)
-static int rspsnap_create(const smr_rsp_replica *like, uint32_t n, smr_rsp_snapshot **out) {
-    smr_rsp_snapshot *s = new smr_rsp_snapshot();
-    s->G = n; s->R = like->cfg.population; s->me = like->cfg.me; s->ft = like->cfg.fault_tolerance;
-    s->buf.device = like->device;
-    memset(&s->hdr, 0, sizeof(s->hdr));
-    if (int rc = rspsnap_room(s, like)) { delete s; return rc; }
-    *out = s;
-    return SMR_OK;
-}
+int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out) { return snap_obj_create<RspSnap>(like, out); }
+int smr_rsp_snapshot_create_groups(const smr_rsp_replica *like, uint32_t n, smr_rsp_snapshot **out) { return snap_obj_create_groups<RspSnap>(like, n, out); }
+void smr_rsp_snapshot_destroy(smr_rsp_snapshot *s) { snap_obj_destroy(s); }
 
-int smr_rsp_snapshot_create(const smr_rsp_replica *like, smr_rsp_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
-    return rspsnap_create(like, like->cfg.n_groups, out);
-}
-
-void smr_rsp_snapshot_destroy(smr_rsp_snapshot *s) {
-    if (!s) return;
-    snap_buf_free(s->buf);
-    snap_glist_free(s->glist);
-    delete s;
-}
-
-int smr_rsp_snapshot_create_groups(const smr_rsp_replica *like, uint32_t n, smr_rsp_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "rspaxos groups: null argument");
-    if (n == 0 || n > like->cfg.n_groups)
-        return fail(SMR_ERR_ARG, "rspaxos groups: a snapshot of " + std::to_string(n) + " groups of a replica of " + std::to_string(like->cfg.n_groups));
-    smr_rsp_snapshot *s = nullptr;
-    if (int rc = rspsnap_create(like, n, &s)) return rc;
-    if (int rc = snap_glist_room(s->glist, n, RSPGROUPS)) { smr_rsp_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
-    *out = s;
-    return SMR_OK;
-}
-
+// ---- chosen groups between replica objects (rsp_snapshot.h: the same image, the same bodies, through a group list) -----------
 int smr_rsp_cluster_save_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const uint32_t *groups_host, uint32_t n, smr_rsp_snapshot *const *snaps,
                                 void *stream) {
     RspSnapArgs A;
-    if (int rc = rspgroups_setup(n_reps, reps, snaps, groups_host, n, RSPG_SAVE, A)) return rc;
-    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RSPGROUPS)) return rc;
+    if (int rc = snap_groups_setup<RspSnap>(n_reps, reps, snaps, groups_host, n, SNAP_GROUPS_SAVE)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RspSnap::GWHAT)) return rc;
+    rspsnap_args(n_reps, reps, snaps, n, A);
     hipLaunchKernelGGL(rsp_snap_pack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)snaps[0]->glist.dev);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n_reps; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    for (uint32_t k = 0; k < n_reps; k++) snap_obj_saved(snaps[k]);
     return SMR_OK;
 }
 
@@ -1117,8 +1044,9 @@ int smr_rsp_cluster_load_groups(uint32_t n_reps, smr_rsp_replica *const *reps, c
                                 void *stream) {
     smr_rsp_snapshot *const *snaps = const_cast<smr_rsp_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
     RspSnapArgs A;
-    if (int rc = rspgroups_setup(n_reps, reps, snaps, groups_host, n, RSPG_LOAD, A)) return rc;
-    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RSPGROUPS)) return rc;
+    if (int rc = snap_groups_setup<RspSnap>(n_reps, reps, snaps, groups_host, n, SNAP_GROUPS_LOAD)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, RspSnap::GWHAT)) return rc;
+    rspsnap_args(n_reps, reps, snaps, n, A);
     hipLaunchKernelGGL(rsp_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)snaps[0]->glist.dev, 0);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1126,8 +1054,9 @@ int smr_rsp_cluster_load_groups(uint32_t n_reps, smr_rsp_replica *const *reps, c
 
 int smr_rsp_cluster_reset_groups(uint32_t n_reps, smr_rsp_replica *const *reps, const uint32_t *groups_host, uint32_t n, void *stream) {
     RspSnapArgs A;
-    if (int rc = rspgroups_setup(n_reps, reps, nullptr, groups_host, n, RSPG_RESET, A)) return rc;
-    if (int rc = snap_glist_upload(reps[0]->glist, groups_host, n, (hipStream_t)stream, RSPGROUPS)) return rc;
+    if (int rc = snap_groups_setup<RspSnap>(n_reps, reps, (smr_rsp_snapshot *const *)nullptr, groups_host, n, SNAP_GROUPS_RESET)) return rc;
+    if (int rc = snap_glist_upload(reps[0]->glist, groups_host, n, (hipStream_t)stream, RspSnap::GWHAT)) return rc;
+    rspsnap_args(n_reps, reps, nullptr, n, A);
     hipLaunchKernelGGL(rsp_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)reps[0]->glist.dev, 1);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1150,16 +1079,19 @@ int smr_rsp_reset_groups(smr_rsp_replica *e, const uint32_t *groups_host, uint32
 
 int smr_rsp_cluster_save_state(uint32_t n, smr_rsp_replica *const *reps, smr_rsp_snapshot *const *snaps, void *stream) {
     RspSnapArgs A;
-    if (int rc = rspsnap_setup(n, reps, snaps, false, A)) return rc;
+    if (int rc = snap_cluster_setup<RspSnap>(n, reps, snaps, false)) return rc;
+    rspsnap_args(n, reps, snaps, reps[0]->v.G, A);
     hipLaunchKernelGGL(rsp_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    for (uint32_t k = 0; k < n; k++) { snaps[k]->buf.filled = true; snaps[k]->buf.hdr_known = false; }
+    for (uint32_t k = 0; k < n; k++) snap_obj_saved(snaps[k]);
     return SMR_OK;
 }
 
-int smr_rsp_cluster_load_state(uint32_t n, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *snaps, void *stream) {
-    RspSnapArgs A;                                               // (a snapshot's header is read back and cached on first use)
-    if (int rc = rspsnap_setup(n, reps, const_cast<smr_rsp_snapshot *const *>(snaps), true, A)) return rc;
+int smr_rsp_cluster_load_state(uint32_t n, smr_rsp_replica *const *reps, const smr_rsp_snapshot *const *csnaps, void *stream) {
+    smr_rsp_snapshot *const *snaps = const_cast<smr_rsp_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
+    RspSnapArgs A;
+    if (int rc = snap_cluster_setup<RspSnap>(n, reps, snaps, true)) return rc;
+    rspsnap_args(n, reps, snaps, reps[0]->v.G, A);
     hipLaunchKernelGGL(rsp_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
@@ -1182,31 +1114,20 @@ int smr_rsp_debug_arena_view(smr_rsp_replica *e, void **base_dev, uint64_t *n_by
 }
 
 int smr_rsp_snapshot_info_get(const smr_rsp_snapshot *cs, smr_rsp_snapshot_info *out) {
-    if (!cs || !out) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
-    smr_rsp_snapshot *s = const_cast<smr_rsp_snapshot *>(cs);
-    if (int rc = rspsnap_header(s)) return rc;
-    const RspSnapHdr &h = s->hdr;
-    memset(out, 0, sizeof(*out));
+    if (int rc = snap_obj_info<RspSnap>(cs, out)) return rc;
+    const RspSnapHdr &h = cs->hdr;
     out->bytes = h.bytes; out->n_slots = h.n_slots; out->n_exec = h.n_exec;
     out->n_groups = h.n_groups; out->window = h.window; out->max_live = h.max_live; out->max_exec = h.max_exec;
     out->population = h.population; out->replica_id = h.me; out->fault_tolerance = h.fault_tolerance;
     return SMR_OK;
 }
 
-int64_t smr_rsp_snapshot_export(const smr_rsp_snapshot *cs, uint8_t *host, uint64_t cap) {
-    if (!cs || !host) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
-    smr_rsp_snapshot *s = const_cast<smr_rsp_snapshot *>(cs);
-    if (int rc = rspsnap_header(s)) return rc;
-    const RspSnapHdr &h = s->hdr;
-    if (cap < h.bytes) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image takes " + std::to_string(h.bytes) + " bytes");
-    if (int rc = rspsnap_copy(s, host, h, true)) return rc;
-    return (int64_t)h.bytes;
-}
+int64_t smr_rsp_snapshot_export(const smr_rsp_snapshot *cs, uint8_t *host, uint64_t cap) { return snap_obj_export<RspSnap>(cs, host, cap); }
 
 int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "rspaxos snapshot: null argument");
     RspSnapHdr h;
-    if (int rc = snap_import_prologue(host, len, RSPSNAP_MAGIC, RSPSNAP_VERSION, RSPSNAP, h)) return rc;
+    if (int rc = snap_import_prologue(host, len, RSPSNAP_MAGIC, RSPSNAP_VERSION, RspSnap::WHAT, h)) return rc;
     if (h.me >= h.population) return fail(SMR_ERR_ARG, "rspaxos snapshot: the image's replica id is not below its population");
     if (!rspsnap_hdr_like(h, s) || h.reserved0 || h.reserved1 || h.reserved2) return fail(SMR_ERR_ARG, std::string("rspaxos snapshot: the image is of ") + RSPSNAP_OTHER);
     const uint32_t W = h.window;
@@ -1255,13 +1176,7 @@ int smr_rsp_snapshot_import(smr_rsp_snapshot *s, const uint8_t *host, uint64_t l
         }
     }
     if (!snap_pad_is_zero(p, 0, h.n_exec * 4)) return bad("padding is not zero");
-    if (h.n_slots > s->cap_s || h.n_exec > s->cap_x)
-        if (int rc = rspsnap_alloc(s, h.n_slots > s->cap_s ? h.n_slots : s->cap_s, h.n_exec > s->cap_x ? h.n_exec : s->cap_x)) return rc;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    s->buf.filled = false;
-    if (int rc = rspsnap_copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
-    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
-    return SMR_OK;
+    return snap_obj_import_bytes<RspSnap>(s, host, h);
 }
 
 }  // extern "C"

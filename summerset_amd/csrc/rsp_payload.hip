@@ -1454,35 +1454,13 @@ int smr_rsp_pstore_debug_delivered(smr_rsp_pstore *s, uint64_t *out_host) {
  * codeword: here the shard bytes themselves, between two calls on the store, two launches each way. */
 }  // extern "C"
 
-struct smr_rsp_pstore_snapshot {
-    uint32_t G = 0, W = 0;
+struct smr_rsp_pstore_snapshot : SnapObj<PsSnapHdr, 1> {         // buf: the image, dense (header .. shard bytes); cap: room of the shard section;
+    uint32_t G = 0, W = 0;                                       // scratch: [planes][W][G] u64, where a cell's stored shards begin
     uint8_t n = 0, d = 0, planes = 0, craft = 0;
-    SnapBuf buf;                                                 // the image, dense: header .. shard bytes
-    uint64_t *d_off = nullptr;                                   // [planes][W][G] where a cell's stored shards begin (scratch of the two launches)
-    uint64_t cap_bytes = 0;                                      // room of the shard section
-    PsSnapHdr hdr;                                               // the image's header, once buf.hdr_known
-    SnapGroupListBuf glist;                                      // smr_rsp_pstore_save_groups / _load_groups: the list on the device
 };
 
 namespace smr {
-static const char *const PSSNAP = "pstore snapshot: ";
 static PsSnapGeom pssnap_geom_of(const smr_rsp_pstore_snapshot *s) { return pssnap_geom(s->G, s->W, s->planes); }
-static int pssnap_alloc(smr_rsp_pstore_snapshot *s, uint64_t cap_bytes) {
-    s->cap_bytes = cap_bytes;
-    return snap_buf_alloc(s->buf, pssnap_geom_of(s).fixed + cap_bytes + 16, PSSNAP);
-}
-// room for the worst case of the snapshot's groups in store `st`: every cell holding every shard at max_data_len -- for a whole
-// store the planes' own size.  A save can then never find the snapshot too small, so it only enqueues.  Grows (host-known sizes)
-// when a store with a larger max_data_len is saved.
-static int pssnap_room(smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
-    const uint64_t need = (uint64_t)st->planes * st->v.W * st->v.n * s->G * st->v.cap_sl;
-    if (s->buf.dev && need <= s->cap_bytes) return SMR_OK;
-    s->buf.filled = false; s->buf.hdr_known = false;
-    return pssnap_alloc(s, need > s->cap_bytes ? need : s->cap_bytes);
-}
-static int pssnap_header(smr_rsp_pstore_snapshot *s) {
-    return snap_buf_header(s->buf, s->hdr, PSSNAP, [s](const PsSnapHdr &h) { return h.shard_bytes <= s->cap_bytes; });
-}
 // made for a store like st, whatever its n_groups (a snapshot of chosen groups has its own)
 static bool pssnap_like_kind(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st) {
     return s->W == st->v.W && s->n == st->v.n && s->d == st->v.d && s->planes == st->planes && (s->craft != 0) == st->craft_store;
@@ -1492,94 +1470,81 @@ static bool pssnap_hdr_like(const PsSnapHdr &h, const smr_rsp_pstore_snapshot *s
     return h.n_groups == s->G && h.window == s->W && h.n_shards == s->n && h.n_data_shards == s->d && h.planes == s->planes && h.craft == s->craft;
 }
 static const char *const PSSNAP_OTHER = "another n_groups / n_shards / n_data_shards / window / kind (RSPaxos or CRaft store)";
-static PsSnapArgs pssnap_args(const smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *s) {
+
+// what is the stores' own of a snapshot object and its calls (snapshot_common.h: SnapObj)
+struct PsSnap {
+    static constexpr const char *WHAT = "pstore snapshot: ", *GWHAT = "pstore groups: ", *NOUN = "store", *LIST_OF = "";
+    static constexpr bool LIST_FIRST = false;
+    static uint32_t groups_of(const smr_rsp_pstore *st) { return st->v.G; }
+    static int init(smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *like) {
+        s->W = like->v.W; s->n = (uint8_t)like->v.n; s->d = (uint8_t)like->v.d; s->planes = (uint8_t)like->planes;
+        s->craft = like->craft_store ? 1 : 0;
+        hipError_t e = hipMalloc(&s->scratch, (size_t)s->planes * s->G * s->W * 8 + 8);
+        if (e != hipSuccess) { s->scratch = nullptr; return fail(SMR_ERR_DEVICE, std::string("pstore snapshot: hipMalloc: ") + hipGetErrorString(e)); }
+        return SMR_OK;
+    }
+    // every cell holding every shard at max_data_len -- for a whole store the planes' own size
+    static void need(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st, uint64_t (&n)[1]) {
+        n[0] = (uint64_t)st->planes * st->v.W * st->v.n * s->G * st->v.cap_sl;
+    }
+    static void counts(const PsSnapHdr &h, uint64_t (&n)[1]) { n[0] = h.shard_bytes; }
+    static uint64_t dev_bytes(const smr_rsp_pstore_snapshot *s) { return pssnap_geom_of(s).fixed + s->cap[0] + 16; }
+    static int copy(const smr_rsp_pstore_snapshot *s, uint8_t *host, const PsSnapHdr &h, bool to_host) {   // (the image is dense)
+        SMR_HIP_TRY(to_host ? hipMemcpy(host, s->buf.dev, h.bytes, hipMemcpyDeviceToHost) : hipMemcpy(s->buf.dev, host, h.bytes, hipMemcpyHostToDevice));
+        return SMR_OK;
+    }
+    static int load_fits(const smr_rsp_pstore_snapshot *s, const smr_rsp_pstore *st, const char *what, bool) {
+        if (!pssnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + PSSNAP_OTHER);
+        if (s->hdr.max_dlen > st->max_data_len)
+            return fail(SMR_ERR_ARG, std::string(what) + "a payload of " + std::to_string(s->hdr.max_dlen) + " bytes does not fit max_data_len " + std::to_string(st->max_data_len));
+        return SMR_OK;
+    }
+    static int groups_pair_check(smr_rsp_pstore *const *sts, smr_rsp_pstore_snapshot *const *snaps, uint32_t, uint32_t n, SnapGroupsCall call) {
+        if (call == SNAP_GROUPS_RESET) return SMR_OK;
+        if (!pssnap_like_kind(snaps[0], sts[0])) return fail(SMR_ERR_ARG, "pstore groups: the snapshot was made for another n_shards / n_data_shards / window / kind (RSPaxos or CRaft store)");
+        return snap_groups_len_check(n, snaps[0]->G, GWHAT);
+    }
+};
+
+// the launches' arguments; s = nullptr (a reset): the geometry of n groups and no buffers
+static PsSnapArgs pssnap_args(const smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *s, uint32_t n = 0) {
     PsSnapArgs A;
     memset(&A, 0, sizeof(A));
-    A.v = st->v; A.img = s->buf.dev; A.cell_off = s->d_off; A.cap_bytes = s->cap_bytes; A.craft = s->craft; A.geo = pssnap_geom_of(s);
+    A.v = st->v;
+    if (s) { A.img = s->buf.dev; A.cell_off = (uint64_t *)s->scratch; A.cap_bytes = s->cap[0]; A.craft = s->craft; A.geo = pssnap_geom_of(s); }
+    else A.geo = pssnap_geom(n, st->v.W, (uint32_t)st->planes);
     return A;
 }
 static uint32_t pssnap_byte_blocks(const PsSnapArgs &A) {
     const uint64_t items = (uint64_t)A.geo.planes * A.geo.cells * A.v.n, want = (items + 3) / 4;   // (the image's items: a short list, a short launch)
     return (uint32_t)(want < PSSNAP_BYTE_BLOCKS ? (want ? want : 1) : PSSNAP_BYTE_BLOCKS);
 }
-
-// ---- chosen groups between stores (ps_snapshot.h: the same image, the same bodies, through a group list) ---------------------
-static const char *const PSGROUPS = "pstore groups: ";
-enum PsGroupsCall { PSG_SAVE, PSG_LOAD, PSG_RESET };
-// every check of a listed-groups call before anything is written, allocated or launched, then the launches' arguments.  A reset
-// has no snapshot: A carries the geometry of n groups and no buffers
-static int psgroups_setup(smr_rsp_pstore *st, smr_rsp_pstore_snapshot *s, const uint32_t *groups, uint32_t n, PsGroupsCall call, PsSnapArgs &A) {
-    if (!st || !groups || (call != PSG_RESET && !s)) return fail(SMR_ERR_ARG, "pstore groups: null argument");
-    if (call != PSG_RESET) {
-        if (!pssnap_like_kind(s, st)) return fail(SMR_ERR_ARG, "pstore groups: the snapshot was made for another n_shards / n_data_shards / window / kind (RSPaxos or CRaft store)");
-        if (s->G != n) return fail(SMR_ERR_ARG, "pstore groups: a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(s->G));
-    }
-    if (int rc = snap_glist_check(groups, n, st->v.G, PSGROUPS)) return rc;
-    if (call == PSG_LOAD) {
-        if (int rc = pssnap_header(s)) return rc;
-        const PsSnapHdr &h = s->hdr;
-        if (!pssnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("pstore groups: the image is of ") + PSSNAP_OTHER);
-        if (h.max_dlen > st->max_data_len)
-            return fail(SMR_ERR_ARG, "pstore groups: a payload of " + std::to_string(h.max_dlen) + " bytes does not fit max_data_len " + std::to_string(st->max_data_len));
-    }
-    if (call == PSG_SAVE)
-        if (int rc = pssnap_room(s, st)) return rc;
-    if (call == PSG_RESET) {
-        memset(&A, 0, sizeof(A));
-        A.v = st->v; A.geo = pssnap_geom(n, st->v.W, (uint32_t)st->planes);
-    } else A = pssnap_args(st, s);
-    return SMR_OK;
-}
 }  // namespace smr
 
 extern "C" {
 
-// a snapshot object for n groups of a store like `like` (n = its n_groups: the whole store)
-static int pssnap_create(const smr_rsp_pstore *like, uint32_t n, smr_rsp_pstore_snapshot **out) {
-    smr_rsp_pstore_snapshot *s = new smr_rsp_pstore_snapshot();
-    s->G = n; s->W = like->v.W; s->n = (uint8_t)like->v.n; s->d = (uint8_t)like->v.d; s->planes = (uint8_t)like->planes;
-    s->craft = like->craft_store ? 1 : 0;
-    memset(&s->hdr, 0, sizeof(s->hdr));
-    hipError_t e = hipMalloc((void **)&s->d_off, (size_t)s->planes * s->G * s->W * 8 + 8);
-    if (e != hipSuccess) { delete s; return fail(SMR_ERR_DEVICE, std::string("pstore snapshot: hipMalloc: ") + hipGetErrorString(e)); }
-    if (int rc = pssnap_room(s, like)) { (void)hipFree(s->d_off); delete s; return rc; }
-    *out = s;
-    return SMR_OK;
-}
+int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_snapshot **out) { return snap_obj_create<PsSnap>(like, out); }
+int smr_rsp_pstore_snapshot_create_groups(const smr_rsp_pstore *like, uint32_t n, smr_rsp_pstore_snapshot **out) { return snap_obj_create_groups<PsSnap>(like, n, out); }
+void smr_rsp_pstore_snapshot_destroy(smr_rsp_pstore_snapshot *s) { snap_obj_destroy(s); }
 
-int smr_rsp_pstore_snapshot_create(const smr_rsp_pstore *like, smr_rsp_pstore_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
-    return pssnap_create(like, like->v.G, out);
-}
-
-int smr_rsp_pstore_snapshot_create_groups(const smr_rsp_pstore *like, uint32_t n, smr_rsp_pstore_snapshot **out) {
-    if (!like || !out) return fail(SMR_ERR_ARG, "pstore groups: null argument");
-    if (n == 0 || n > like->v.G)
-        return fail(SMR_ERR_ARG, "pstore groups: a snapshot of " + std::to_string(n) + " groups of a store of " + std::to_string(like->v.G));
-    smr_rsp_pstore_snapshot *s = nullptr;
-    if (int rc = pssnap_create(like, n, &s)) return rc;
-    if (int rc = snap_glist_room(s->glist, n, PSGROUPS)) { smr_rsp_pstore_snapshot_destroy(s); return rc; }   // no allocation in the calls that use it
-    *out = s;
-    return SMR_OK;
-}
-
+// ---- chosen groups between stores (ps_snapshot.h: the same image, the same bodies, through a group list) ---------------------
 int smr_rsp_pstore_save_groups(smr_rsp_pstore *st, const uint32_t *groups_host, uint32_t n, smr_rsp_pstore_snapshot *s, void *stream) {
-    PsSnapArgs A;
-    if (int rc = psgroups_setup(st, s, groups_host, n, PSG_SAVE, A)) return rc;
-    if (int rc = snap_glist_upload(s->glist, groups_host, n, (hipStream_t)stream, PSGROUPS)) return rc;
+    if (int rc = snap_groups_setup<PsSnap>(1, &st, &s, groups_host, n, SNAP_GROUPS_SAVE)) return rc;
+    if (int rc = snap_glist_upload(s->glist, groups_host, n, (hipStream_t)stream, PsSnap::GWHAT)) return rc;
+    const PsSnapArgs A = pssnap_args(st, s);
     const uint32_t *list = s->glist.dev;
     hipLaunchKernelGGL(ps_snap_head_groups<true>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A, list, 0);
     hipLaunchKernelGGL(ps_snap_bytes_groups<true>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A, list);
     SMR_HIP_TRY(hipGetLastError());
-    s->buf.filled = true; s->buf.hdr_known = false;
+    snap_obj_saved(s);
     return SMR_OK;
 }
 
 int smr_rsp_pstore_load_groups(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *cs, const uint32_t *groups_host, uint32_t n, void *stream) {
     smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);   // (the header is read back and cached on first use)
-    PsSnapArgs A;
-    if (int rc = psgroups_setup(st, s, groups_host, n, PSG_LOAD, A)) return rc;
-    if (int rc = snap_glist_upload(s->glist, groups_host, n, (hipStream_t)stream, PSGROUPS)) return rc;
+    if (int rc = snap_groups_setup<PsSnap>(1, &st, &s, groups_host, n, SNAP_GROUPS_LOAD)) return rc;
+    if (int rc = snap_glist_upload(s->glist, groups_host, n, (hipStream_t)stream, PsSnap::GWHAT)) return rc;
+    const PsSnapArgs A = pssnap_args(st, s);
     const uint32_t *list = s->glist.dev;
     hipLaunchKernelGGL(ps_snap_head_groups<false>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A, list, 0);
     hipLaunchKernelGGL(ps_snap_bytes_groups<false>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A, list);
@@ -1588,33 +1553,24 @@ int smr_rsp_pstore_load_groups(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot
 }
 
 int smr_rsp_pstore_reset_groups(smr_rsp_pstore *st, const uint32_t *groups_host, uint32_t n, void *stream) {
-    PsSnapArgs A;
-    if (int rc = psgroups_setup(st, nullptr, groups_host, n, PSG_RESET, A)) return rc;
-    if (int rc = snap_glist_upload(st->glist, groups_host, n, (hipStream_t)stream, PSGROUPS)) return rc;
+    if (int rc = snap_groups_setup<PsSnap>(1, &st, (smr_rsp_pstore_snapshot *const *)nullptr, groups_host, n, SNAP_GROUPS_RESET)) return rc;
+    if (int rc = snap_glist_upload(st->glist, groups_host, n, (hipStream_t)stream, PsSnap::GWHAT)) return rc;
+    const PsSnapArgs A = pssnap_args(st, nullptr, n);
     const uint32_t *list = st->glist.dev;
     hipLaunchKernelGGL(ps_snap_head_groups<false>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A, list, 1);   // cell headers only: row bytes are not touched
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
 }
 
-void smr_rsp_pstore_snapshot_destroy(smr_rsp_pstore_snapshot *s) {
-    if (!s) return;
-    if (s->buf.dev || s->d_off) (void)hipDeviceSynchronize();
-    if (s->buf.dev) (void)hipFree(s->buf.dev);
-    if (s->d_off) (void)hipFree(s->d_off);
-    snap_glist_free(s->glist);
-    delete s;
-}
-
 int smr_rsp_pstore_save(smr_rsp_pstore *st, smr_rsp_pstore_snapshot *s, void *stream) {
     if (!st || !s) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
     if (!pssnap_like(s, st)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: made for ") + PSSNAP_OTHER);
-    if (int rc = pssnap_room(s, st)) return rc;
+    if (int rc = snap_obj_room_for<PsSnap>(s, st)) return rc;
     const PsSnapArgs A = pssnap_args(st, s);
     hipLaunchKernelGGL(ps_snap_head<true>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A);
     hipLaunchKernelGGL(ps_snap_bytes<true>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
-    s->buf.filled = true; s->buf.hdr_known = false;
+    snap_obj_saved(s);
     return SMR_OK;
 }
 
@@ -1622,11 +1578,7 @@ int smr_rsp_pstore_load(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *cs, v
     if (!st || !cs) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
     smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
     if (!pssnap_like(s, st)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: made for ") + PSSNAP_OTHER);
-    if (int rc = pssnap_header(s)) return rc;
-    const PsSnapHdr &h = s->hdr;
-    if (!pssnap_hdr_like(h, s)) return fail(SMR_ERR_ARG, std::string("pstore snapshot: the image is of ") + PSSNAP_OTHER);
-    if (h.max_dlen > st->max_data_len)
-        return fail(SMR_ERR_ARG, "pstore snapshot: a payload of " + std::to_string(h.max_dlen) + " bytes does not fit max_data_len " + std::to_string(st->max_data_len));
+    if (int rc = snap_obj_load_ready<PsSnap>(s, st, PsSnap::WHAT, false)) return rc;
     const PsSnapArgs A = pssnap_args(st, s);
     hipLaunchKernelGGL(ps_snap_head<false>, dim3(A.geo.tiles.nblock), dim3(256), 0, (hipStream_t)stream, A);
     hipLaunchKernelGGL(ps_snap_bytes<false>, dim3(pssnap_byte_blocks(A)), dim3(256), 0, (hipStream_t)stream, A);
@@ -1635,30 +1587,20 @@ int smr_rsp_pstore_load(smr_rsp_pstore *st, const smr_rsp_pstore_snapshot *cs, v
 }
 
 int smr_rsp_pstore_snapshot_info_get(const smr_rsp_pstore_snapshot *cs, smr_rsp_pstore_snapshot_info *out) {
-    if (!cs || !out) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
-    smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
-    if (int rc = pssnap_header(s)) return rc;
-    const PsSnapHdr &h = s->hdr;
-    memset(out, 0, sizeof(*out));
+    if (int rc = snap_obj_info<PsSnap>(cs, out)) return rc;
+    const PsSnapHdr &h = cs->hdr;
     out->bytes = h.bytes; out->n_cells = h.n_cells; out->n_shards_stored = h.n_shards_stored; out->shard_bytes = h.shard_bytes;
     out->n_groups = h.n_groups; out->window = h.window; out->max_dlen = h.max_dlen;
     out->n_shards = h.n_shards; out->n_data_shards = h.n_data_shards; out->planes = h.planes; out->craft = h.craft;
     return SMR_OK;
 }
 
-int64_t smr_rsp_pstore_snapshot_export(const smr_rsp_pstore_snapshot *cs, uint8_t *host, uint64_t cap) {
-    if (!cs || !host) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
-    smr_rsp_pstore_snapshot *s = const_cast<smr_rsp_pstore_snapshot *>(cs);
-    if (int rc = pssnap_header(s)) return rc;
-    if (cap < s->hdr.bytes) return fail(SMR_ERR_ARG, "pstore snapshot: the image takes " + std::to_string(s->hdr.bytes) + " bytes");
-    SMR_HIP_TRY(hipMemcpy(host, s->buf.dev, s->hdr.bytes, hipMemcpyDeviceToHost));     // (the image is dense)
-    return (int64_t)s->hdr.bytes;
-}
+int64_t smr_rsp_pstore_snapshot_export(const smr_rsp_pstore_snapshot *cs, uint8_t *host, uint64_t cap) { return snap_obj_export<PsSnap>(cs, host, cap); }
 
 int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *host, uint64_t len) {
     if (!s || !host) return fail(SMR_ERR_ARG, "pstore snapshot: null argument");
     PsSnapHdr h;
-    if (int rc = snap_import_prologue(host, len, PSSNAP_MAGIC, PSSNAP_VERSION, PSSNAP, h, "store")) return rc;
+    if (int rc = snap_import_prologue(host, len, PSSNAP_MAGIC, PSSNAP_VERSION, PsSnap::WHAT, h, "store")) return rc;
     if (!pssnap_hdr_like(h, s) || h.reserved) return fail(SMR_ERR_ARG, std::string("pstore snapshot: the image is of ") + PSSNAP_OTHER);
     const PsSnapGeom q = pssnap_geom_of(s);
     if (snap_truncated(len, q.fixed, h.bytes) || h.bytes - q.fixed != h.shard_bytes || (h.shard_bytes & 15))
@@ -1699,13 +1641,7 @@ int smr_rsp_pstore_snapshot_import(smr_rsp_pstore_snapshot *s, const uint8_t *ho
                 }
     if (off != h.shard_bytes || n_cells != h.n_cells || n_stored != h.n_shards_stored || max_dlen != h.max_dlen)
         return bad("the header's counts contradict the cell headers");
-    if (!s->buf.dev || h.shard_bytes > s->cap_bytes)
-        if (int rc = pssnap_alloc(s, h.shard_bytes > s->cap_bytes ? h.shard_bytes : s->cap_bytes)) return rc;
-    SMR_HIP_TRY(hipDeviceSynchronize());
-    s->buf.filled = false;
-    SMR_HIP_TRY(hipMemcpy(s->buf.dev, host, h.bytes, hipMemcpyHostToDevice));
-    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
-    return SMR_OK;
+    return snap_obj_import_bytes<PsSnap>(s, host, h);
 }
 
 /* debug / measurement only: the three device allocations that hold the store (meta, REQS plane, VOTED plane; a CRaft store's

@@ -24,7 +24,7 @@
 // capacities behind the fixed part; export closes the gaps.
 // Chosen groups (smr_rsp_save_groups / smr_rsp_load_groups / smr_rsp_reset_groups and their cluster forms) go through the same
 // image and the same bodies: an image of "these n groups, in this order" is the image of an n-group replica, read and written
-// through a group list (RspSnapGroupList below).  A group image holds zero counters; the unpolled execution list is per-group
+// through a group list (SnapGroupList below).  A group image holds zero counters; the unpolled execution list is per-group
 // rows and travels like every other section.
 #pragma once
 #include "snapshot_common.h"
@@ -112,25 +112,9 @@ constexpr uint8_t RSP_INIT_VAL_BYTE = 0xFF;                  // create fills byt
 constexpr uint32_t RSP_INIT_VAL = 0x01010101u * RSP_INIT_VAL_BYTE;
 static_assert(RSP_INIT_WORD == 0 && RSP_INIT_LEADER == 0xFF, "create fills bytes");
 
-// ---- which group of the replica an image position holds -----------------------------------------------------------------
-// An image has its own group index (position x, stride n = its n_groups, lane = x & 63) and the replica has its own (group g,
-// stride v.G).  For a whole-replica image they are one and the same; an image of "these n groups, in this order" is the image of
-// an n-group replica whose group x is group list[x] of this one: the same format, the same tiles, bases and placement run over
-// list positions, and the replica side a gather or scatter.  The bodies below take the map as a parameter; with
-// RspSnapAllGroups they are what they were.
-// What a group image does not carry (WHOLE = false): the four counters.  Events stay counted where they happened, so the sum over
-// objects is conserved.  The image's counters are zero, and a load through a list leaves the target's alone.
-struct RspSnapAllGroups {
-    static constexpr bool WHOLE = true;
-    __device__ __forceinline__ uint32_t n(const RspView &v, const RspSnapGeom &) const { return v.G; }
-    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
-};
-struct RspSnapGroupList {
-    static constexpr bool WHOLE = false;
-    const uint32_t *__restrict__ list;                           // [n], every entry < v.G, none twice (the host has checked)
-    __device__ __forceinline__ uint32_t n(const RspView &, const RspSnapGeom &Q) const { return Q.G; }
-    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
-};
+// ---- which group of the replica an image position holds: snapshot_common.h's SnapAllGroups / SnapGroupList -----------------
+// What a group image does not carry (WHOLE = false): the four counters.  The image's counters are zero, and a load through a
+// list leaves the target's alone.
 
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1).  An RSPaxos replica keeps no device
@@ -168,7 +152,7 @@ __device__ __forceinline__ void rspsnap_pack_all(const RspSnapArgs &A, const Map
     const RspView &v = A.v[rep];
     const RspSnapImg S{A.img[rep], A.cap_s[rep], A.cap_x[rep]};
     const RspSnapScal sc = rspsnap_scal(S.base, Q);
-    const uint32_t ni = M.n(v, Q);
+    const uint32_t ni = M.n(v.G, Q.G);
     const SnapWave w = snap_wave(Q.tiles, ni);
     const size_t G = v.G, NX = ni;
     uint64_t base[2];                                            // slot records, exec entries in front
@@ -233,7 +217,7 @@ __device__ __forceinline__ void rspsnap_unpack_all(const RspSnapArgs &A, const M
     const RspView &v = A.v[rep];
     const RspSnapImg S{A.img[rep], A.cap_s[rep], A.cap_x[rep]};
     const RspSnapScal sc = rspsnap_scal(S.base, Q);
-    const uint32_t ni = M.n(v, Q);
+    const uint32_t ni = M.n(v.G, Q.G);
     const SnapWave w = snap_wave(Q.tiles, ni);
     const size_t G = v.G, NX = ni;
     uint64_t base[2] = {0, 0};
@@ -285,14 +269,14 @@ __device__ __forceinline__ void rspsnap_unpack_all(const RspSnapArgs &A, const M
     if (Map::WHOLE) snap_counters_load<4>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
 }
 
-__global__ __launch_bounds__(256) void rsp_snap_pack(const RspSnapArgs A) { rspsnap_pack_all(A, RspSnapAllGroups{}); }
-__global__ __launch_bounds__(256) void rsp_snap_unpack(const RspSnapArgs A) { rspsnap_unpack_all<RspSnapAllGroups, false>(A, RspSnapAllGroups{}); }
+__global__ __launch_bounds__(256) void rsp_snap_pack(const RspSnapArgs A) { rspsnap_pack_all(A, SnapAllGroups{}); }
+__global__ __launch_bounds__(256) void rsp_snap_unpack(const RspSnapArgs A) { rspsnap_unpack_all<SnapAllGroups, false>(A, SnapAllGroups{}); }
 // group x of the image (A.geo.G = n groups) <-> group list[x] of the replica, one list for all replicas of the call; fresh: no
 // image, the listed groups as a new replica object holds them (A carries the geometry of n groups and no buffers)
-__global__ __launch_bounds__(256) void rsp_snap_pack_groups(const RspSnapArgs A, const uint32_t *list) { rspsnap_pack_all(A, RspSnapGroupList{list}); }
+__global__ __launch_bounds__(256) void rsp_snap_pack_groups(const RspSnapArgs A, const uint32_t *list) { rspsnap_pack_all(A, SnapGroupList{list}); }
 __global__ __launch_bounds__(256) void rsp_snap_unpack_groups(const RspSnapArgs A, const uint32_t *list, int fresh) {
-    if (fresh) rspsnap_unpack_all<RspSnapGroupList, true>(A, RspSnapGroupList{list});
-    else rspsnap_unpack_all<RspSnapGroupList, false>(A, RspSnapGroupList{list});
+    if (fresh) rspsnap_unpack_all<SnapGroupList, true>(A, SnapGroupList{list});
+    else rspsnap_unpack_all<SnapGroupList, false>(A, SnapGroupList{list});
 }
 
 }  // namespace smr

@@ -153,6 +153,29 @@ __device__ __forceinline__ void snap_zero_pad(uint8_t *base, uint64_t off, uint6
     for (uint64_t p = off + n; p < off + snap_a8(n); p++) base[p] = 0;
 }
 
+// ---- which group of the object an image position holds --------------------------------------------------------------------
+// An image has its own group index (position x, stride n = its n_groups, lane = x & 63) and the engine object has its own
+// (group g, stride = its n_groups).  For a whole-object image they are one and the same; an image of "these n groups, in this
+// order" (the save_groups / load_groups calls) is the image of an n-group object whose group x is group list[x] of this one:
+// the same format, the same tiles, bases and placement run over list positions, and the object's side a gather or scatter
+// (two listed groups share a line of a ring row only where they sit in the same 64-group tile).  The engines' pack and unpack
+// bodies take the map as a parameter, so the field moves are written once; with SnapAllGroups they are the whole-object
+// kernels.  WHOLE = false: the object's reporting (its counters, ...) does not travel -- events stay counted where they
+// happened, so the sum over objects is conserved; each engine's header says what that is for its image.
+// n(G_obj, G_img): the positions of the image, out of the object's and the image geometry's group counts; group(x, in): `in`
+// is false for the lanes behind the last position
+struct SnapAllGroups {
+    static constexpr bool WHOLE = true;
+    __device__ __forceinline__ uint32_t n(uint32_t G_obj, uint32_t) const { return G_obj; }
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool) const { return x; }
+};
+struct SnapGroupList {
+    static constexpr bool WHOLE = false;
+    const uint32_t *__restrict__ list;                           // [n], every entry < G_obj, none twice (the host has checked)
+    __device__ __forceinline__ uint32_t n(uint32_t, uint32_t G_img) const { return G_img; }
+    __device__ __forceinline__ uint32_t group(uint32_t x, bool in) const { return in ? list[x] : 0u; }
+};
+
 // ---- host -----------------------------------------------------------------------------------------------------------------
 // `what` is the engine's message prefix ("raft snapshot: ", ...): every text below is what the engines said before they shared it.
 
@@ -249,9 +272,9 @@ inline int snap_glist_room(SnapGroupListBuf &b, uint32_t n, const char *what) {
 inline void snap_glist_free(SnapGroupListBuf &b) {
     if (b.dev) { (void)hipDeviceSynchronize(); (void)hipFree(b.dev); b.dev = nullptr; b.cap = 0; }
 }
-// n in 1 .. G, every id below G, none twice (a bitmap: O(n))
-inline int snap_glist_check(const uint32_t *groups, uint32_t n, uint32_t G, const char *what) {
-    if (n == 0 || n > G) return fail(SMR_ERR_ARG, std::string(what) + "a list of " + std::to_string(n) + " groups for " + std::to_string(G));
+// n in 1 .. G, every id below G, none twice (a bitmap: O(n)).  of: what the first message calls the G ("a cluster of ", or nothing)
+inline int snap_glist_check(const uint32_t *groups, uint32_t n, uint32_t G, const char *what, const char *of = "") {
+    if (n == 0 || n > G) return fail(SMR_ERR_ARG, std::string(what) + "a list of " + std::to_string(n) + " groups for " + of + std::to_string(G));
     std::vector<uint64_t> seen(((size_t)G + 63) / 64, 0ull);
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t g = groups[i];
@@ -267,6 +290,170 @@ inline int snap_glist_check(const uint32_t *groups, uint32_t n, uint32_t G, cons
 inline int snap_glist_upload(SnapGroupListBuf &b, const uint32_t *groups, uint32_t n, hipStream_t st, const char *what) {
     if (int rc = snap_glist_room(b, n, what)) return rc;
     SMR_HIP_TRY(hipMemcpyAsync(b.dev, groups, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    return SMR_OK;
+}
+
+// ---- host: one snapshot object, one call path ----------------------------------------------------------------
+// An engine's snapshot struct derives from SnapObj and adds what it was made for (G = its n_groups, and the engine's own
+// fields); a struct E of static members says what is the engine's own.  S = the snapshot struct, Like = the engine object:
+//   WHAT, GWHAT, NOUN          message prefixes of the whole-object and the listed-groups calls; what the engine object is called
+//   LIST_FIRST, LIST_OF        listed-groups calls: the list is checked before the pairs (MultiPaxos), and what it calls G
+//   groups_of(like)            the engine object's n_groups
+//   init(s, like)              s's own fields from `like` (s->G is set); may refuse, may allocate s->scratch
+//   need(s, like, n[N])        the sections' worst case for s's groups in an object like `like`
+//   counts(hdr, n[N])          the header's section counts
+//   dev_bytes(s)               the device buffer for s->cap
+//   copy(s, host, hdr, to_host)   the image between the device buffer and packed host bytes
+//   load_fits(s, like, what, groups)   a load's rules on s->hdr: the image is of s's kind, and fits `like` (window, ...)
+//   pair_check(reps, snaps, k)         the whole-object cluster calls' check of pair k
+//   groups_pair_check(reps, snaps, k, n, call)   the listed-groups calls' (snaps = nullptr for a reset)
+template <class Hdr, int N>
+struct SnapObj {
+    static constexpr int NSEC = N;
+    SnapBuf buf;
+    uint64_t cap[N] = {};                                        // records (the stores: bytes) the device buffer's sections have room for
+    Hdr hdr;                                                     // the image's header, once buf.hdr_known
+    SnapGroupListBuf glist;                                      // the save_groups / load_groups calls' list on the device
+    void *scratch = nullptr;                                     // device memory of the launches that is not image (the stores' cell_off)
+};
+
+// room for `need` records per section: grows (host-known sizes: no read-back), and what the buffer held goes with the old one
+template <class E, class S>
+int snap_obj_room(S *s, const uint64_t (&need)[S::NSEC]) {
+    bool fits = s->buf.dev != nullptr;
+    for (int k = 0; k < S::NSEC; k++) fits = fits && need[k] <= s->cap[k];
+    if (fits) return SMR_OK;
+    s->buf.filled = false; s->buf.hdr_known = false;
+    for (int k = 0; k < S::NSEC; k++) s->cap[k] = need[k] > s->cap[k] ? need[k] : s->cap[k];
+    return snap_buf_alloc(s->buf, E::dev_bytes(s), E::WHAT);
+}
+// ... for the worst case of s's groups in an object like `like`: a save can then never find the snapshot too small, so it stays
+// a call that only enqueues
+template <class E, class S, class Like>
+int snap_obj_room_for(S *s, const Like *like) {
+    uint64_t need[S::NSEC];
+    E::need(s, like, need);
+    return snap_obj_room<E>(s, need);
+}
+// the image's header on the host (synchronises once after a save)
+template <class E, class S>
+int snap_obj_header(S *s) {
+    return snap_buf_header(s->buf, s->hdr, E::WHAT, [s](const decltype(s->hdr) &h) {
+        uint64_t n[S::NSEC];
+        E::counts(h, n);
+        for (int k = 0; k < S::NSEC; k++) if (n[k] > s->cap[k]) return false;
+        return true;
+    });
+}
+template <class S>
+void snap_obj_saved(S *s) { s->buf.filled = true; s->buf.hdr_known = false; }
+// before a load writes anything: the header, and the engine's rules on it
+template <class E, class S, class Like>
+int snap_obj_load_ready(S *s, const Like *like, const char *what, bool groups) {
+    if (int rc = snap_obj_header<E>(s)) return rc;
+    return E::load_fits(s, like, what, groups);
+}
+
+// every device buffer of the object synchronises before it is freed: a launch may still use it
+template <class S>
+void snap_obj_destroy(S *s) {
+    if (!s) return;
+    snap_buf_free(s->buf);
+    snap_glist_free(s->glist);
+    if (s->scratch) { (void)hipDeviceSynchronize(); (void)hipFree(s->scratch); }
+    delete s;
+}
+// a snapshot object for n groups of an object like `like` (n = its n_groups: the whole object)
+template <class E, class S, class Like>
+int snap_obj_make(const Like *like, uint32_t n, S **out) {
+    S *s = new S();
+    s->G = n;
+    memset(&s->hdr, 0, sizeof(s->hdr));
+    int rc = E::init(s, like);
+    if (rc == SMR_OK) rc = snap_obj_room_for<E>(s, like);
+    if (rc != SMR_OK) { snap_obj_destroy(s); return rc; }
+    *out = s;
+    return SMR_OK;
+}
+template <class E, class S, class Like>
+int snap_obj_create(const Like *like, S **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, std::string(E::WHAT) + "null argument");
+    return snap_obj_make<E>(like, E::groups_of(like), out);
+}
+template <class E, class S, class Like>
+int snap_obj_create_groups(const Like *like, uint32_t n, S **out) {
+    if (!like || !out) return fail(SMR_ERR_ARG, std::string(E::GWHAT) + "null argument");
+    if (n == 0 || n > E::groups_of(like))
+        return fail(SMR_ERR_ARG, std::string(E::GWHAT) + "a snapshot of " + std::to_string(n) + " groups of a " + E::NOUN + " of " + std::to_string(E::groups_of(like)));
+    S *s = nullptr;
+    if (int rc = snap_obj_make<E>(like, n, &s)) return rc;
+    if (int rc = snap_glist_room(s->glist, n, E::GWHAT)) { snap_obj_destroy(s); return rc; }   // no allocation in the calls that use it
+    *out = s;
+    return SMR_OK;
+}
+
+// info_get's first half: the header on the host, *out zeroed; the engine copies the fields
+template <class E, class S, class Info>
+int snap_obj_info(const S *cs, Info *out) {
+    if (!cs || !out) return fail(SMR_ERR_ARG, std::string(E::WHAT) + "null argument");
+    if (int rc = snap_obj_header<E>(const_cast<S *>(cs))) return rc;
+    memset(out, 0, sizeof(*out));
+    return SMR_OK;
+}
+template <class E, class S>
+int64_t snap_obj_export(const S *cs, uint8_t *host, uint64_t cap) {
+    if (!cs || !host) return fail(SMR_ERR_ARG, std::string(E::WHAT) + "null argument");
+    S *s = const_cast<S *>(cs);
+    if (int rc = snap_obj_header<E>(s)) return rc;
+    if (cap < s->hdr.bytes) return fail(SMR_ERR_ARG, std::string(E::WHAT) + "the image takes " + std::to_string(s->hdr.bytes) + " bytes");
+    if (int rc = E::copy(s, host, s->hdr, true)) return rc;
+    return (int64_t)s->hdr.bytes;
+}
+// an import's last step, once the engine has validated the image of header h: room, then the bytes
+template <class E, class S, class Hdr>
+int snap_obj_import_bytes(S *s, const uint8_t *host, const Hdr &h) {
+    uint64_t n[S::NSEC];
+    E::counts(h, n);
+    if (int rc = snap_obj_room<E>(s, n)) return rc;
+    SMR_HIP_TRY(hipDeviceSynchronize());
+    s->buf.filled = false;
+    if (int rc = E::copy(s, const_cast<uint8_t *>(host), h, false)) return rc;
+    s->hdr = h; s->buf.filled = true; s->buf.hdr_known = true;
+    return SMR_OK;
+}
+
+// the whole-object cluster calls (n replicas and their snapshots): every check before anything is written, then room for a save.
+// The engine fills its launch arguments afterwards
+template <class E, class Rep, class S>
+int snap_cluster_setup(uint32_t n, Rep *const *reps, S *const *snaps, bool load) {
+    if (int rc = snap_pairs_check(n, reps, snaps, E::WHAT, [&](uint32_t k) { return E::pair_check(reps, snaps, k); })) return rc;
+    for (uint32_t k = 0; k < n; k++)                             // (a save: only a failed hipMalloc -- the snapshots that grew before it are
+        if (int rc = load ? snap_obj_load_ready<E>(snaps[k], reps[k], E::WHAT, false) : snap_obj_room_for<E>(snaps[k], reps[k])) return rc;   // then empty, none holds a partial image)
+    return SMR_OK;
+}
+
+// the listed-groups calls over n_reps objects (the one-object engines: 1) for the n listed groups, one list for all of them:
+// every check before anything is written, allocated or launched, in the order the engine's messages have always come; then the
+// headers and fit rules of a load, room for a save.  A reset has no snapshots: the objects stand in for them in the pairs' check
+enum SnapGroupsCall { SNAP_GROUPS_SAVE, SNAP_GROUPS_LOAD, SNAP_GROUPS_RESET };
+inline int snap_groups_len_check(uint32_t n, uint32_t G_snap, const char *what) {
+    if (G_snap != n) return fail(SMR_ERR_ARG, std::string(what) + "a list of " + std::to_string(n) + " groups and a snapshot made for " + std::to_string(G_snap));
+    return SMR_OK;
+}
+template <class E, class Rep, class S>
+int snap_groups_setup(uint32_t n_reps, Rep *const *reps, S *const *snaps, const uint32_t *groups, uint32_t n, SnapGroupsCall call) {
+    if (!groups) return fail(SMR_ERR_ARG, std::string(E::GWHAT) + "null argument");
+    const auto list = [&] { return snap_glist_check(groups, n, E::groups_of(reps[0]), E::GWHAT, E::LIST_OF); };
+    const auto pair = [&](uint32_t k) {
+        if (E::LIST_FIRST && k == 0)
+            if (int rc = list()) return rc;
+        return E::groups_pair_check(reps, snaps, k, n, call);
+    };
+    if (int rc = call == SNAP_GROUPS_RESET ? snap_pairs_check(n_reps, reps, reps, E::GWHAT, pair) : snap_pairs_check(n_reps, reps, snaps, E::GWHAT, pair)) return rc;
+    if (!E::LIST_FIRST)
+        if (int rc = list()) return rc;
+    for (uint32_t k = 0; k < n_reps && call != SNAP_GROUPS_RESET; k++)
+        if (int rc = call == SNAP_GROUPS_LOAD ? snap_obj_load_ready<E>(snaps[k], reps[k], E::GWHAT, true) : snap_obj_room_for<E>(snaps[k], reps[k])) return rc;
     return SMR_OK;
 }
 

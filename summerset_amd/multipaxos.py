@@ -9,7 +9,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .snapshot import DeviceSnapshot, group_list as _group_list
+from . import snapshot as _snapshot
+from .snapshot import DeviceSnapshot
 from ._lib import MpCfg, MpDumpBufs, MpGroupState, MpTickIn, SummersetError, check, stream_ptr
 
 _DUMP_T = {"leader": np.uint8, "bal_prep_sent": np.uint64, "bal_prepared": np.uint64, "bal_max_seen": np.uint64,
@@ -187,21 +188,16 @@ class MultiPaxosCluster:
     def save_groups(self, groups, snap=None, stream=None):
         """the listed groups' state as the image of a len(groups) cluster, group i of it = groups[i] (`smr_mp_save_groups`);
         counters and unpolled commits stay here"""
-        g = _group_list(groups)
-        snap = MpSnapshot(self, len(g)) if snap is None else snap
-        check(self._L.smr_mp_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
-        return snap
+        return _snapshot.save_groups("smr_mp", MpSnapshot, self, groups, snap, stream)
 
     def load_groups(self, snap, groups, stream=None):
         """group i of a len(groups) image overwrites group groups[i]; every other group, the counters and the commit list
         are left alone (`smr_mp_load_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_mp_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.load_groups("smr_mp", self, snap, groups, stream)
 
     def reset_groups(self, groups, stream=None):
         """the listed groups back to what a new cluster holds: no leader, empty log (`smr_mp_reset_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_mp_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.reset_groups("smr_mp", self, groups, stream)
 
     def counters(self, rep):
         arr = (C.c_uint64 * 3)()

@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .snapshot import DeviceSnapshot, group_list as _group_list
+from . import snapshot as _snapshot
+from .snapshot import DeviceSnapshot
 from ._lib import RaftAppendEntries, RaftAppendReply, RaftCfg, RaftDumpBufs, check, stream_ptr
 
 _T = {"role": np.uint8, "leader": np.uint8, "curr_term": np.uint64, "entry_term": np.uint64}
@@ -20,10 +21,6 @@ _T = {"role": np.uint8, "leader": np.uint8, "curr_term": np.uint64, "entry_term"
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
-
-
-def _handles(xs):
-    return (C.c_void_p * len(xs))(*[x._h for x in xs])
 
 
 class RaftSnapshot(DeviceSnapshot):
@@ -40,50 +37,29 @@ class RaftSnapshot(DeviceSnapshot):
 def save_cluster_state(reps, snaps=None, stream=None):
     """`reps[k].save_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch
     (`smr_raft_cluster_save_state`); returns the snapshots (new ones without `snaps`)"""
-    snaps = [RaftSnapshot(r) for r in reps] if snaps is None else list(snaps)
-    n = len(reps)
-    if len(snaps) != n:
-        raise ValueError("save_cluster_state: %d replicas, %d snapshots" % (n, len(snaps)))
-    L = _lib.load()
-    check(L.smr_raft_cluster_save_state(n, (C.c_void_p * n)(*[r._h for r in reps]), (C.c_void_p * len(snaps))(*[s._h for s in snaps]),
-                                        stream_ptr(stream)))
-    return snaps
+    return _snapshot.save_cluster_state("smr_raft", RaftSnapshot, reps, snaps, stream)
 
 
 def load_cluster_state(reps, snaps, stream=None):
     """`reps[k].load_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch (`smr_raft_cluster_load_state`)"""
-    n = len(reps)
-    if len(snaps) != n:
-        raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (n, len(snaps)))
-    L = _lib.load()
-    check(L.smr_raft_cluster_load_state(n, (C.c_void_p * n)(*[r._h for r in reps]), (C.c_void_p * len(snaps))(*[s._h for s in snaps]),
-                                        stream_ptr(stream)))
+    _snapshot.load_cluster_state("smr_raft", reps, snaps, stream)
 
 
 def save_cluster_groups(reps, groups, snaps=None, stream=None):
     """`reps[k].save_groups(groups, snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch, one list for all of
     them (`smr_raft_cluster_save_groups`); returns the snapshots (new ones without `snaps`)"""
-    g = _group_list(groups)
-    snaps = [RaftSnapshot(r, len(g)) for r in reps] if snaps is None else list(snaps)
-    if len(snaps) != len(reps):
-        raise ValueError("save_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
-    check(_lib.load().smr_raft_cluster_save_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), _handles(snaps), stream_ptr(stream)))
-    return snaps
+    return _snapshot.save_cluster_groups("smr_raft", RaftSnapshot, reps, groups, snaps, stream)
 
 
 def load_cluster_groups(reps, snaps, groups, stream=None):
     """`reps[k].load_groups(snaps[k], groups)` for up to 8 replicas of one co-located cluster in ONE launch
     (`smr_raft_cluster_load_groups`)"""
-    g = _group_list(groups)
-    if len(snaps) != len(reps):
-        raise ValueError("load_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
-    check(_lib.load().smr_raft_cluster_load_groups(len(reps), _handles(reps), _handles(snaps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+    _snapshot.load_cluster_groups("smr_raft", reps, snaps, groups, stream)
 
 
 def reset_cluster_groups(reps, groups, stream=None):
     """`reps[k].reset_groups(groups)` for up to 8 replicas of one co-located cluster in ONE launch (`smr_raft_cluster_reset_groups`)"""
-    g = _group_list(groups)
-    check(_lib.load().smr_raft_cluster_reset_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+    _snapshot.reset_cluster_groups("smr_raft", reps, groups, stream)
 
 
 def move_groups(src_reps, src_groups, dst_reps, dst_groups, snaps=None, reset=True):
@@ -91,11 +67,7 @@ def move_groups(src_reps, src_groups, dst_reps, dst_groups, snaps=None, reset=Tr
     between two handler calls of both): one cluster save, one cluster load, and the source's slots back to what a new object
     holds.  The counters stay where the events happened.  Returns the snapshots, for the next move of as many groups.  Which job
     group sits in which slot is the caller's table"""
-    snaps = save_cluster_groups(src_reps, src_groups, snaps)
-    load_cluster_groups(dst_reps, snaps, dst_groups)
-    if reset:
-        reset_cluster_groups(src_reps, src_groups)
-    return snaps
+    return _snapshot.move_cluster_groups("smr_raft", RaftSnapshot, src_reps, src_groups, dst_reps, dst_groups, snaps, reset)
 
 
 class RaftLeaderGroup:
@@ -228,33 +200,26 @@ class RaftLeaderGroup:
     def save_state(self, snap=None, stream=None):
         """my whole logical state into a device-resident snapshot (a new one, or `snap` again), between two handler calls; one
         kernel on `stream`, nothing read back (`smr_raft_save_state`)"""
-        snap = RaftSnapshot(self) if snap is None else snap
-        check(self._L.smr_raft_save_state(self._h, snap._h, stream_ptr(stream)))
-        return snap
+        return _snapshot.save_state("smr_raft", RaftSnapshot, self, snap, stream)
 
     def load_state(self, snap, stream=None):
         """overwrite my whole logical state with a snapshot's (`smr_raft_load_state`): same n_groups, population, replica id,
         commit_extra and variant; window at least the snapshot's max_live"""
-        check(self._L.smr_raft_load_state(self._h, snap._h, stream_ptr(stream)))
+        _snapshot.load_state("smr_raft", self, snap, stream)
 
     def save_groups(self, groups, snap=None, stream=None):
         """the listed groups' state as the image of a len(groups) replica, group i of it = groups[i] (`smr_raft_save_groups`);
         the counters stay here"""
-        g = _group_list(groups)
-        snap = RaftSnapshot(self, len(g)) if snap is None else snap
-        check(self._L.smr_raft_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
-        return snap
+        return _snapshot.save_groups("smr_raft", RaftSnapshot, self, groups, snap, stream)
 
     def load_groups(self, snap, groups, stream=None):
         """group i of a len(groups) image overwrites group groups[i]; every other group and the counters are left alone
         (`smr_raft_load_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_raft_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.load_groups("smr_raft", self, snap, groups, stream)
 
     def reset_groups(self, groups, stream=None):
         """the listed groups back to what a new replica object holds (`smr_raft_reset_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_raft_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.reset_groups("smr_raft", self, groups, stream)
 
     def debug_arena_view(self):
         """debug / measurement only: [(device pointer, bytes)] of the allocations that hold my arrays -- the arena and, for a CRaft

@@ -22,7 +22,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, stream_ptr
-from .snapshot import DeviceSnapshot, group_list as _group_list
+from . import snapshot as _snapshot
+from .snapshot import DeviceSnapshot
 
 REQS, VOTED = 0, 1
 NULL = 0xFFFFFFFF
@@ -201,21 +202,16 @@ class RSPaxosPayloadStore:
     def save_groups(self, groups, snap=None, stream=None):
         """the listed groups' headers, alias bytes and present shards as the image of a len(groups) store, group i of it =
         groups[i] (`smr_rsp_pstore_save_groups`); the counters stay here"""
-        g = _group_list(groups)
-        snap = PayloadStoreSnapshot(self, len(g)) if snap is None else snap
-        check(self._L.smr_rsp_pstore_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
-        return snap
+        return _snapshot.save_groups("smr_rsp_pstore", PayloadStoreSnapshot, self, groups, snap, stream)
 
     def load_groups(self, snap, groups, stream=None):
         """group i of a len(groups) image overwrites the cells of group groups[i]; every other group, the counters and the row
         bytes behind a shard's length are left alone (`smr_rsp_pstore_load_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_rsp_pstore_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.load_groups("smr_rsp_pstore", self, snap, groups, stream)
 
     def reset_groups(self, groups, stream=None):
         """the listed groups' cells back to what a new store holds (`smr_rsp_pstore_reset_groups`); row bytes are not touched"""
-        g = _group_list(groups)
-        check(self._L.smr_rsp_pstore_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.reset_groups("smr_rsp_pstore", self, groups, stream)
 
     def delivered(self):
         """of `counters()["copied"]`: shards a sender's `put_follow_all` wrote here from its put launch (no copy out of its row)"""

@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .snapshot import DeviceSnapshot, group_list as _group_list
+from . import snapshot as _snapshot
+from .snapshot import DeviceSnapshot
 from ._lib import RspAccepts, RspCfg, RspDumpBufs, RspHeartbeat, RspPrepareReply, RspShards, check, stream_ptr
 
 NULL, NO_REP = 0xFFFFFFFF, 0xFF
@@ -44,51 +45,32 @@ class RSPaxosSnapshot(DeviceSnapshot):
         check(self._L.smr_rsp_load_state(rep._h, self._h, stream_ptr(stream)))
 
 
-def _handles(xs):
-    return (C.c_void_p * len(xs))(*[x._h for x in xs])
-
-
 def save_cluster_state(reps, snaps=None, stream=None):
     """`reps[k].save_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch
     (`smr_rsp_cluster_save_state`); returns the snapshots (new ones without `snaps`)"""
-    snaps = [RSPaxosSnapshot(r) for r in reps] if snaps is None else list(snaps)
-    if len(snaps) != len(reps):
-        raise ValueError("save_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
-    check(_lib.load().smr_rsp_cluster_save_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
-    return snaps
+    return _snapshot.save_cluster_state("smr_rsp", RSPaxosSnapshot, reps, snaps, stream)
 
 
 def load_cluster_state(reps, snaps, stream=None):
     """`reps[k].load_state(snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch (`smr_rsp_cluster_load_state`)"""
-    if len(snaps) != len(reps):
-        raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
-    check(_lib.load().smr_rsp_cluster_load_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+    _snapshot.load_cluster_state("smr_rsp", reps, snaps, stream)
 
 
 def save_cluster_groups(reps, groups, snaps=None, stream=None):
     """`reps[k].save_groups(groups, snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch, one list for all of
     them (`smr_rsp_cluster_save_groups`); returns the snapshots (new ones without `snaps`)"""
-    g = _group_list(groups)
-    snaps = [RSPaxosSnapshot(r, len(g)) for r in reps] if snaps is None else list(snaps)
-    if len(snaps) != len(reps):
-        raise ValueError("save_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
-    check(_lib.load().smr_rsp_cluster_save_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), _handles(snaps), stream_ptr(stream)))
-    return snaps
+    return _snapshot.save_cluster_groups("smr_rsp", RSPaxosSnapshot, reps, groups, snaps, stream)
 
 
 def load_cluster_groups(reps, snaps, groups, stream=None):
     """`reps[k].load_groups(snaps[k], groups)` for up to 8 replicas of one co-located cluster in ONE launch
     (`smr_rsp_cluster_load_groups`)"""
-    g = _group_list(groups)
-    if len(snaps) != len(reps):
-        raise ValueError("load_cluster_groups: %d replicas, %d snapshots" % (len(reps), len(snaps)))
-    check(_lib.load().smr_rsp_cluster_load_groups(len(reps), _handles(reps), _handles(snaps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+    _snapshot.load_cluster_groups("smr_rsp", reps, snaps, groups, stream)
 
 
 def reset_cluster_groups(reps, groups, stream=None):
     """`reps[k].reset_groups(groups)` for up to 8 replicas of one co-located cluster in ONE launch (`smr_rsp_cluster_reset_groups`)"""
-    g = _group_list(groups)
-    check(_lib.load().smr_rsp_cluster_reset_groups(len(reps), _handles(reps), g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+    _snapshot.reset_cluster_groups("smr_rsp", reps, groups, stream)
 
 
 class RSPaxosReplicaGroup:
@@ -233,21 +215,16 @@ class RSPaxosReplicaGroup:
     def save_groups(self, groups, snap=None, stream=None):
         """the listed groups' state as the image of a len(groups) replica, group i of it = groups[i] (`smr_rsp_save_groups`),
         the unpolled execution list included; the counters stay here"""
-        g = _group_list(groups)
-        snap = RSPaxosSnapshot(self, len(g)) if snap is None else snap
-        check(self._L.smr_rsp_save_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), snap._h, stream_ptr(stream)))
-        return snap
+        return _snapshot.save_groups("smr_rsp", RSPaxosSnapshot, self, groups, snap, stream)
 
     def load_groups(self, snap, groups, stream=None):
         """group i of a len(groups) image overwrites group groups[i]; every other group and the counters are left alone
         (`smr_rsp_load_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_rsp_load_groups(self._h, snap._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.load_groups("smr_rsp", self, snap, groups, stream)
 
     def reset_groups(self, groups, stream=None):
         """the listed groups back to what a new replica object holds (`smr_rsp_reset_groups`)"""
-        g = _group_list(groups)
-        check(self._L.smr_rsp_reset_groups(self._h, g.ctypes.data_as(C.c_void_p), len(g), stream_ptr(stream)))
+        _snapshot.reset_groups("smr_rsp", self, groups, stream)
 
     def dump(self):
         G, R, W = self.G, self.R, self.W

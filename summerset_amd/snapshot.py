@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import check, stream_ptr
 
 
 def group_list(groups):
@@ -68,3 +68,88 @@ class DeviceSnapshot:
         data = bytes(data)
         check(self._call("import")(self._h, C.cast(C.c_char_p(data), C.c_void_p), len(data)))
         return self
+
+
+# ---- what an engine object and a cluster of them do with snapshots: the same for every engine, given the C symbol stem
+# ("smr_raft": smr_raft_save_groups, smr_raft_cluster_save_groups, ...) and the snapshot class ------------------------------
+def _handles(xs):
+    return (C.c_void_p * len(xs))(*[x._h for x in xs])
+
+
+def _sym(stem, what):
+    return getattr(_lib.load(), "%s_%s" % (stem, what))
+
+
+def _glist(groups):
+    g = group_list(groups)
+    return g, g.ctypes.data_as(C.c_void_p), len(g)
+
+
+def _paired(what, reps, snaps):
+    if len(snaps) != len(reps):
+        raise ValueError("%s: %d replicas, %d snapshots" % (what, len(reps), len(snaps)))
+    return snaps
+
+
+def save_state(stem, Snap, obj, snap=None, stream=None):
+    snap = Snap(obj) if snap is None else snap
+    check(_sym(stem, "save_state")(obj._h, snap._h, stream_ptr(stream)))
+    return snap
+
+
+def load_state(stem, obj, snap, stream=None):
+    check(_sym(stem, "load_state")(obj._h, snap._h, stream_ptr(stream)))
+
+
+def save_groups(stem, Snap, obj, groups, snap=None, stream=None):
+    g, p, n = _glist(groups)
+    snap = Snap(obj, n) if snap is None else snap
+    check(_sym(stem, "save_groups")(obj._h, p, n, snap._h, stream_ptr(stream)))
+    return snap
+
+
+def load_groups(stem, obj, snap, groups, stream=None):
+    g, p, n = _glist(groups)
+    check(_sym(stem, "load_groups")(obj._h, snap._h, p, n, stream_ptr(stream)))
+
+
+def reset_groups(stem, obj, groups, stream=None):
+    g, p, n = _glist(groups)
+    check(_sym(stem, "reset_groups")(obj._h, p, n, stream_ptr(stream)))
+
+
+def save_cluster_state(stem, Snap, reps, snaps=None, stream=None):
+    snaps = _paired("save_cluster_state", reps, [Snap(r) for r in reps] if snaps is None else list(snaps))
+    check(_sym(stem, "cluster_save_state")(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_state(stem, reps, snaps, stream=None):
+    _paired("load_cluster_state", reps, snaps)
+    check(_sym(stem, "cluster_load_state")(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+
+
+def save_cluster_groups(stem, Snap, reps, groups, snaps=None, stream=None):
+    g, p, n = _glist(groups)
+    snaps = _paired("save_cluster_groups", reps, [Snap(r, n) for r in reps] if snaps is None else list(snaps))
+    check(_sym(stem, "cluster_save_groups")(len(reps), _handles(reps), p, n, _handles(snaps), stream_ptr(stream)))
+    return snaps
+
+
+def load_cluster_groups(stem, reps, snaps, groups, stream=None):
+    g, p, n = _glist(groups)
+    _paired("load_cluster_groups", reps, snaps)
+    check(_sym(stem, "cluster_load_groups")(len(reps), _handles(reps), _handles(snaps), p, n, stream_ptr(stream)))
+
+
+def reset_cluster_groups(stem, reps, groups, stream=None):
+    g, p, n = _glist(groups)
+    check(_sym(stem, "cluster_reset_groups")(len(reps), _handles(reps), p, n, stream_ptr(stream)))
+
+
+def move_cluster_groups(stem, Snap, src_reps, src_groups, dst_reps, dst_groups, snaps=None, reset=True):
+    snaps = save_cluster_groups(stem, Snap, src_reps, src_groups, snaps)
+    load_cluster_groups(stem, dst_reps, snaps, dst_groups)
+    if reset:
+        reset_cluster_groups(stem, src_reps, src_groups)
+    return snaps
