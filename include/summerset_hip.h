@@ -1109,6 +1109,58 @@ int64_t smr_ep_snapshot_export(const smr_ep_snapshot *s, uint8_t *host, uint64_t
 int smr_ep_snapshot_import(smr_ep_snapshot *s, const uint8_t *host, uint64_t len);
 int smr_ep_cluster_save_state(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, void *stream);
 int smr_ep_cluster_load_state(uint32_t n, smr_ep_replica *const *reps, const smr_ep_snapshot *const *snaps, void *stream);
+
+/* ---- chosen groups between replica objects, on the device --------------------------------------------------------------------
+ * The contract smr_mp_snapshot_create_groups, smr_raft_snapshot_create_groups and smr_rsp_snapshot_create_groups settled, for an
+ * EPaxos replica object.  No new format: an image of "these n groups, in this order" is the version-1 "SEPS" image of an n-group
+ * replica, group i of the image being group groups_host[i] of the replica: the same magic and version, the same tile-major cell
+ * order (64 list entries a tile), the same reply-record and exec-entry sections, n_groups = n, max_live / max_exec and the
+ * header's totals taken over the listed groups.  It interchanges both ways with smr_ep_save_state / smr_ep_load_state images of
+ * an n-group replica object, byte for byte where the content is equal.
+ *   smr_ep_snapshot_create_groups  a snapshot object for n groups of a replica like `like`: its population, replica id,
+ *                            optimized_quorum, execute, recovery and n_keys, worst-case room for n groups at its window (growing
+ *                            by host-known sizes as above).  info, export and import work on it unchanged; import checks
+ *                            against n_groups = n;
+ *   smr_ep_save_groups       one kernel on `stream`; enqueues only, apart from handing the list to the device (an async copy on
+ *                            `stream` into a buffer the snapshot owns).  Everything smr_ep_save_state writes for the listed
+ *                            groups: len, commit_bars, rewritten; with execute exec_bars, the commit-bar copies, digest and the
+ *                            unpolled submissions as (column, row) entries -- the target hands them to smr_ep_exec_poll under
+ *                            its own group id; the group's highest columns and KV tokens of the per-key table; the live cells'
+ *                            records with exp_prepare_max_bal; the reachable stored PreAcceptReplies and voted entries.  The
+ *                            replica is not modified;
+ *   smr_ep_load_groups       the inverse: group i of an n-group image overwrites the whole logical state of group
+ *                            groups_host[i]; nothing of any other group changes.  The per-key entries are written where the
+ *                            target keeps them: a replica seated in an smr_ep_cluster's shared table is written in its slots of
+ *                            that table.  The image may come from smr_ep_save_groups or be an ordinary smr_ep_save_state image
+ *                            of an n-group replica.  Ring cells outside the live span are left alone, as smr_ep_load_state
+ *                            leaves them.  Synchronises once per save to read the image's header;
+ *   smr_ep_reset_groups      the listed groups back to exactly what smr_ep_replica_create leaves for a group: the scalars zero,
+ *                            every one of the population * window ring cells a null instance, the per-key entries
+ *                            SMR_EP_NONE with KV word 0, no unpolled submission.  (The reply tables and the executor's graph
+ *                            arrays are not written: nothing reaches them without a live cell's bits);
+ *   smr_ep_cluster_save_groups / _load_groups / _reset_groups   a group lives in R replica objects: n_reps <= 8 distinct
+ *                            replicas that share n_groups / population / n_keys / execute / recovery, ONE list for all of them,
+ *                            each replica with its own snapshot, in ONE launch -- exactly what the n_reps single calls give.
+ * What does not travel: the seven engine counters and the eight executor counters.  Events stay counted where they happened, so
+ * the sum over replica objects is conserved: a group image holds zero counters, smr_ep_load_groups ignores an image's counters
+ * and leaves the target's alone (smr_ep_cluster_batch_stats' word too).  Nor, as for the whole object, the wire call's scratch
+ * and anything of an smr_ep_cluster or smr_ep_spread object: within-tick scratch.  Which job group sits in which slot is the
+ * host's table.  The calls are defined between two handler calls / ticks, as smr_ep_save_state is.
+ * The list is a host array (a move is a rare host decision), checked before anything is launched: n in 1 .. n_groups, every id
+ * below n_groups, none twice; for save and load n is the snapshot's n_groups.  SMR_ERR_ARG for these, for a null argument,
+ * another population / replica id / optimized_quorum / execute / recovery / n_keys, another window (a cell is held iff column +
+ * window >= len, as for smr_ep_load_state), a replica or snapshot listed twice or replicas that differ in a cluster form;
+ * SMR_ERR_STATE for an empty snapshot.  A refused call leaves replica and snapshot untouched.
+ * The list's device buffer belongs to the snapshot object (a cluster form uses snaps[0]'s for all replicas; a reset the
+ * replica's, reps[0]'s), and smr_ep_load_groups writes it although its snapshot argument is const: calls that use one snapshot
+ * (one replica, for resets) with different lists must be on one stream or ordered by the caller. */
+int smr_ep_snapshot_create_groups(const smr_ep_replica *like, uint32_t n, smr_ep_snapshot **out);
+int smr_ep_save_groups(smr_ep_replica *e, const uint32_t *groups_host, uint32_t n, smr_ep_snapshot *s, void *stream);
+int smr_ep_load_groups(smr_ep_replica *e, const smr_ep_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_ep_reset_groups(smr_ep_replica *e, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_ep_cluster_save_groups(uint32_t n_reps, smr_ep_replica *const *reps, const uint32_t *groups_host, uint32_t n, smr_ep_snapshot *const *snaps, void *stream);
+int smr_ep_cluster_load_groups(uint32_t n_reps, smr_ep_replica *const *reps, const smr_ep_snapshot *const *snaps, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_ep_cluster_reset_groups(uint32_t n_reps, smr_ep_replica *const *reps, const uint32_t *groups_host, uint32_t n, void *stream);
 /* debug / measurement only: the device allocation that holds the replica's arrays (ring cells dead or alive, the reply tables,
  * the executor's graph arrays, counter shards), i.e. what a wholesale copy of the replica's state would move --
  * tools/time_ep_snapshot.py times that copy beside smr_ep_cluster_save_state.  The layout inside is the library's own. */

@@ -15,6 +15,7 @@ from .raft import CRaftLeaderGroup, RaftLeaderGroup, RaftSnapshot, load_cluster_
 from .raft import load_cluster_groups, reset_cluster_groups, save_cluster_groups  # noqa: F401
 from .raft import move_groups as move_raft_groups  # noqa: F401
 from .epaxos import EPaxosReplicaGroup, EPaxosSnapshot  # noqa: F401
+from .epaxos import move_groups as move_ep_groups  # noqa: F401
 from .rspaxos import RSPaxosReplicaGroup, RSPaxosSnapshot  # noqa: F401
 from .rsp_payload import CRaftPayloadStore, PayloadStoreSnapshot, RSPaxosPayloadStore, RSPaxosReplicaWithPayload  # noqa: F401
 from .rsp_payload import move_craft_groups, move_rsp_groups, move_store_groups  # noqa: F401

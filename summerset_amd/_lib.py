@@ -394,6 +394,13 @@ SYMBOLS = [
     ("smr_ep_snapshot_import", _i, [_vp, _vp, _u64]),
     ("smr_ep_cluster_save_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("smr_ep_cluster_load_state", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("smr_ep_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_ep_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_ep_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_ep_reset_groups", _i, [_vp, _vp, _u32, _vp]),
+    ("smr_ep_cluster_save_groups", _i, [_u32, C.POINTER(_vp), _vp, _u32, C.POINTER(_vp), _vp]),
+    ("smr_ep_cluster_load_groups", _i, [_u32, C.POINTER(_vp), C.POINTER(_vp), _vp, _u32, _vp]),
+    ("smr_ep_cluster_reset_groups", _i, [_u32, C.POINTER(_vp), _vp, _u32, _vp]),
     ("smr_ep_debug_arena_view", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_rsp_replica_create", _i, [C.POINTER(RspCfg), C.POINTER(_vp)]),
     ("smr_rsp_replica_destroy", None, [_vp]),

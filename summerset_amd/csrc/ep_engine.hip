@@ -1811,6 +1811,7 @@ struct smr_ep_replica {
     bool skip_exec = false;      // smr_ep_cluster_tick around the handlers that cannot move a commit bar (see there)
     smr_ep_replica **seat = nullptr;   // my seat in the cluster whose per-key table I use (smr_ep_cluster_create): cleared when I go first
     unsigned long long *wire_acc = nullptr;   // smr_ep_leader_handle_wire_pre_accept_replies: its counters and arrival tickets, cumulative over the calls
+    SnapGroupListBuf glist;      // smr_ep_reset_groups' list on the device
 };
 
 namespace smr {
@@ -1865,9 +1866,9 @@ __global__ __launch_bounds__(256) void ep_hc_migrate_kernel(uint32_t *__restrict
 __global__ __launch_bounds__(256) void ep_init_records_kernel(u32x4 *__restrict__ p1, u32x4 *__restrict__ p2, u32x4 *__restrict__ p3, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    p1[i] = (u32x4){EP_NONE, EP_NONE, EP_NONE, EP_NONE};
-    p2[i] = (u32x4){EP_NONE, (uint32_t)EP_NO_KEY << 8, 0u, EP_NONE};
-    if (p3) p3[i] = (u32x4){EP_NONE, EP_NONE, 0u, 0u};
+    p1[i] = ep_init_p1();                                        // (ep_snapshot.h: what a new replica object holds; p0 is zero bytes)
+    p2[i] = ep_init_p2();
+    if (p3) p3[i] = ep_init_p3();
 }
 // out[g] = in[g] unless drop[g] (a lost message)
 __global__ __launch_bounds__(256) void ep_flags_drop_kernel(uint32_t G, const uint8_t *__restrict__ in, const uint8_t *__restrict__ drop,
@@ -2904,6 +2905,7 @@ void smr_ep_replica_destroy(smr_ep_replica *e) {
     if (e->seat) *e->seat = nullptr;                             // (the cluster then has nothing of mine to hand back)
     if (e->arena.base) (void)hipFree(e->arena.base);
     if (e->wire_acc) (void)hipFree(e->wire_acc);
+    snap_glist_free(e->glist);
     delete e;
 }
 
@@ -3532,19 +3534,23 @@ struct smr_ep_snapshot : SnapObj<EpSnapHdr, 3> {                 // cap: cells, 
 namespace smr {
 static EpSnapGeom epsnap_geom_of(const smr_ep_snapshot *s) { return epsnap_geom(s->G, s->R, s->K, s->execute, s->recovery); }
 static EpSnapImg epsnap_img(const smr_ep_snapshot *s) { return EpSnapImg{s->buf.dev, s->cap[0], s->cap[1], s->cap[2]}; }
-static bool epsnap_like(const smr_ep_snapshot *s, const smr_ep_cfg &c) {
-    return s->G == c.n_groups && s->R == c.population && s->me == c.me && s->oq == (c.optimized_quorum ? 1 : 0) && s->execute == c.execute &&
-           s->recovery == c.recovery && s->K == c.n_keys;
+// made for a replica of c's kind, whatever its n_groups (a snapshot of chosen groups has its own)
+static bool epsnap_like_kind(const smr_ep_snapshot *s, const smr_ep_cfg &c) {
+    return s->R == c.population && s->me == c.me && s->oq == (c.optimized_quorum ? 1 : 0) && s->execute == c.execute && s->recovery == c.recovery &&
+           s->K == c.n_keys;
 }
-static bool epsnap_hdr_like(const EpSnapHdr &h, const smr_ep_snapshot *s) {
-    return h.n_groups == s->G && h.population == s->R && h.me == s->me && h.optimized_quorum == s->oq && h.execute == s->execute &&
-           h.recovery == s->recovery && h.n_keys == s->K;
+static bool epsnap_like(const smr_ep_snapshot *s, const smr_ep_cfg &c) { return s->G == c.n_groups && epsnap_like_kind(s, c); }
+static bool epsnap_hdr_like_kind(const EpSnapHdr &h, const smr_ep_snapshot *s) {
+    return h.population == s->R && h.me == s->me && h.optimized_quorum == s->oq && h.execute == s->execute && h.recovery == s->recovery && h.n_keys == s->K;
 }
+static bool epsnap_hdr_like(const EpSnapHdr &h, const smr_ep_snapshot *s) { return h.n_groups == s->G && epsnap_hdr_like_kind(h, s); }
 static const char *const EPSNAP_OTHER = "another n_groups / population / replica id / optimized_quorum / execute / recovery / n_keys";
+static const char *const EPSNAP_OTHER_KIND = "another population / replica id / optimized_quorum / execute / recovery / n_keys";   // (the listed-groups calls)
 
-// what is EPaxos's own of a snapshot object and its calls (snapshot_common.h: SnapObj); it has no listed-groups calls
+// what is EPaxos's own of a snapshot object and its calls (snapshot_common.h: SnapObj)
 struct EpSnap {
-    static constexpr const char *WHAT = "epaxos snapshot: ";
+    static constexpr const char *WHAT = "epaxos snapshot: ", *GWHAT = "epaxos groups: ", *NOUN = "replica", *LIST_OF = "";
+    static constexpr bool LIST_FIRST = false;
     static uint32_t groups_of(const smr_ep_replica *e) { return e->cfg.n_groups; }
     static int init(smr_ep_snapshot *s, const smr_ep_replica *like) {
         const smr_ep_cfg &c = like->cfg;
@@ -3564,29 +3570,46 @@ struct EpSnap {
         return snap_copy_sections(s->buf.dev, host, q.fixed, to_host,
                                   {{q.fixed, bc, bc}, {epsnap_off_rep(q, epsnap_img(s)), br, br}, {epsnap_off_exec(q, epsnap_img(s)), bx, bx}});
     }
-    static int load_fits(const smr_ep_snapshot *s, const smr_ep_replica *e, const char *what, bool) {
-        if (!epsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + EPSNAP_OTHER);
+    // groups: the image's n_groups is the snapshot's and the list's length (groups_pair_check), the replica's own is free
+    static int load_fits(const smr_ep_snapshot *s, const smr_ep_replica *e, const char *what, bool groups) {
+        if (groups) {
+            if (!epsnap_hdr_like_kind(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + EPSNAP_OTHER_KIND);
+            if (int rc = snap_groups_len_check(s->hdr.n_groups, s->G, what)) return rc;
+        } else if (!epsnap_hdr_like(s->hdr, s)) return fail(SMR_ERR_ARG, std::string(what) + "the image is of " + EPSNAP_OTHER);
         // a cell is held iff column + W >= len: in another ring the cells around the saved span would count as held or lost
         if (s->hdr.window != e->cfg.window)
             return fail(SMR_ERR_ARG, std::string(what) + "an image of window " + std::to_string(s->hdr.window) + " does not load into window " + std::to_string(e->cfg.window));
         return SMR_OK;
     }
-    static int pair_check(smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, uint32_t k) {
+    static int replica_check(smr_ep_replica *const *reps, uint32_t k, const char *what) {
         const smr_ep_cfg &c = reps[k]->cfg, &c0 = reps[0]->cfg;
         if (c.n_groups != c0.n_groups || c.population != c0.population || c.n_keys != c0.n_keys || c.execute != c0.execute || c.recovery != c0.recovery)
-            return fail(SMR_ERR_ARG, "epaxos snapshot: the replicas differ in groups / population / n_keys / execute / recovery");
-        if (!epsnap_like(snaps[k], c)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: made for ") + EPSNAP_OTHER);
+            return fail(SMR_ERR_ARG, std::string(what) + "the replicas differ in groups / population / n_keys / execute / recovery");
         return SMR_OK;
+    }
+    static int pair_check(smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, uint32_t k) {
+        if (int rc = replica_check(reps, k, WHAT)) return rc;
+        if (!epsnap_like(snaps[k], reps[k]->cfg)) return fail(SMR_ERR_ARG, std::string("epaxos snapshot: made for ") + EPSNAP_OTHER);
+        return SMR_OK;
+    }
+    static int groups_pair_check(smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, uint32_t k, uint32_t n, SnapGroupsCall call) {
+        if (int rc = replica_check(reps, k, GWHAT)) return rc;
+        if (call == SNAP_GROUPS_RESET) return SMR_OK;
+        if (!epsnap_like_kind(snaps[k], reps[k]->cfg)) return fail(SMR_ERR_ARG, std::string("epaxos groups: the snapshot was made for ") + EPSNAP_OTHER_KIND);
+        return snap_groups_len_check(n, snaps[k]->G, GWHAT);
     }
 };
 
-// the arguments of the one launch for n replicas and their snapshots
-static void epsnap_args(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, EpSnapArgs &A) {
+// the arguments of the one launch for n replicas and their snapshots (snaps = nullptr: a reset); G: the image's groups -- the
+// snapshots' (the whole replica's, or the list's length), not the replicas'
+static void epsnap_args(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, uint32_t G, EpSnapArgs &A) {
     memset(&A, 0, sizeof(A));
     const smr_ep_cfg &c0 = reps[0]->cfg;
-    A.geo = epsnap_geom(c0.n_groups, c0.population, c0.n_keys, c0.execute, c0.recovery);
+    A.geo = epsnap_geom(G, c0.population, c0.n_keys, c0.execute, c0.recovery);
     for (uint32_t k = 0; k < n; k++) {
-        A.v[k] = reps[k]->v; A.x[k] = reps[k]->x; A.img[k] = snaps[k]->buf.dev;
+        A.v[k] = reps[k]->v; A.x[k] = reps[k]->x;
+        if (!snaps) continue;
+        A.img[k] = snaps[k]->buf.dev;
         A.cap_c[k] = snaps[k]->cap[0]; A.cap_r[k] = snaps[k]->cap[1]; A.cap_x[k] = snaps[k]->cap[2]; A.oq[k] = snaps[k]->oq;
     }
 }
@@ -3600,7 +3623,7 @@ void smr_ep_snapshot_destroy(smr_ep_snapshot *s) { snap_obj_destroy(s); }
 int smr_ep_cluster_save_state(uint32_t n, smr_ep_replica *const *reps, smr_ep_snapshot *const *snaps, void *stream) {
     EpSnapArgs A;
     if (int rc = snap_cluster_setup<EpSnap>(n, reps, snaps, false)) return rc;
-    epsnap_args(n, reps, snaps, A);
+    epsnap_args(n, reps, snaps, snaps[0]->G, A);
     hipLaunchKernelGGL(ep_snap_pack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     for (uint32_t k = 0; k < n; k++) snap_obj_saved(snaps[k]);
@@ -3611,10 +3634,62 @@ int smr_ep_cluster_load_state(uint32_t n, smr_ep_replica *const *reps, const smr
     smr_ep_snapshot *const *snaps = const_cast<smr_ep_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
     EpSnapArgs A;
     if (int rc = snap_cluster_setup<EpSnap>(n, reps, snaps, true)) return rc;
-    epsnap_args(n, reps, snaps, A);
+    epsnap_args(n, reps, snaps, snaps[0]->G, A);
     hipLaunchKernelGGL(ep_snap_unpack, dim3(A.geo.tiles.nblock, n), dim3(256), 0, (hipStream_t)stream, A);
     SMR_HIP_TRY(hipGetLastError());
     return SMR_OK;
+}
+
+// ---- chosen groups between replica objects (ep_snapshot.h: the same image, the same bodies, through a group list) -------------
+int smr_ep_snapshot_create_groups(const smr_ep_replica *like, uint32_t n, smr_ep_snapshot **out) { return snap_obj_create_groups<EpSnap>(like, n, out); }
+
+int smr_ep_cluster_save_groups(uint32_t n_reps, smr_ep_replica *const *reps, const uint32_t *groups_host, uint32_t n, smr_ep_snapshot *const *snaps,
+                               void *stream) {
+    EpSnapArgs A;
+    if (int rc = snap_groups_setup<EpSnap>(n_reps, reps, snaps, groups_host, n, SNAP_GROUPS_SAVE)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, EpSnap::GWHAT)) return rc;
+    epsnap_args(n_reps, reps, snaps, n, A);
+    hipLaunchKernelGGL(ep_snap_pack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)snaps[0]->glist.dev);
+    SMR_HIP_TRY(hipGetLastError());
+    for (uint32_t k = 0; k < n_reps; k++) snap_obj_saved(snaps[k]);
+    return SMR_OK;
+}
+
+int smr_ep_cluster_load_groups(uint32_t n_reps, smr_ep_replica *const *reps, const smr_ep_snapshot *const *csnaps, const uint32_t *groups_host, uint32_t n,
+                               void *stream) {
+    smr_ep_snapshot *const *snaps = const_cast<smr_ep_snapshot *const *>(csnaps);   // (a header is read back and cached on first use)
+    EpSnapArgs A;
+    if (int rc = snap_groups_setup<EpSnap>(n_reps, reps, snaps, groups_host, n, SNAP_GROUPS_LOAD)) return rc;
+    if (int rc = snap_glist_upload(snaps[0]->glist, groups_host, n, (hipStream_t)stream, EpSnap::GWHAT)) return rc;
+    epsnap_args(n_reps, reps, snaps, n, A);
+    hipLaunchKernelGGL(ep_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)snaps[0]->glist.dev, 0);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_ep_cluster_reset_groups(uint32_t n_reps, smr_ep_replica *const *reps, const uint32_t *groups_host, uint32_t n, void *stream) {
+    EpSnapArgs A;
+    if (int rc = snap_groups_setup<EpSnap>(n_reps, reps, (smr_ep_snapshot *const *)nullptr, groups_host, n, SNAP_GROUPS_RESET)) return rc;
+    if (int rc = snap_glist_upload(reps[0]->glist, groups_host, n, (hipStream_t)stream, EpSnap::GWHAT)) return rc;
+    epsnap_args(n_reps, reps, nullptr, n, A);
+    hipLaunchKernelGGL(ep_snap_unpack_groups, dim3(A.geo.tiles.nblock, n_reps), dim3(256), 0, (hipStream_t)stream, A, (const uint32_t *)reps[0]->glist.dev, 1);
+    SMR_HIP_TRY(hipGetLastError());
+    return SMR_OK;
+}
+
+int smr_ep_save_groups(smr_ep_replica *e, const uint32_t *groups_host, uint32_t n, smr_ep_snapshot *s, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "epaxos groups: null argument");
+    return smr_ep_cluster_save_groups(1, &e, groups_host, n, &s, stream);
+}
+
+int smr_ep_load_groups(smr_ep_replica *e, const smr_ep_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!e || !s) return fail(SMR_ERR_ARG, "epaxos groups: null argument");
+    return smr_ep_cluster_load_groups(1, &e, &s, groups_host, n, stream);
+}
+
+int smr_ep_reset_groups(smr_ep_replica *e, const uint32_t *groups_host, uint32_t n, void *stream) {
+    if (!e) return fail(SMR_ERR_ARG, "epaxos groups: null argument");
+    return smr_ep_cluster_reset_groups(1, &e, groups_host, n, stream);
 }
 
 int smr_ep_save_state(smr_ep_replica *e, smr_ep_snapshot *s, void *stream) {

@@ -144,6 +144,34 @@ SMR_HD EpSnapScal epsnap_scal(uint8_t *b, const EpSnapGeom &q) {
     return s;
 }
 
+// ---- what a new replica object holds for a group ------------------------------------------------------------------------
+// The one place that says it: smr_ep_replica_create's ep_init_records_kernel fills the record planes from here, and
+// smr_ep_reset_groups (the unpack of nothing, below) returns a listed group to the same values.  Every word of a group is
+// EP_INIT_WORD (its scalars, p0, sq32, xp_max, my_nulls, n_sub, the KV word of its per-key entries) except: the dependencies of
+// every ring cell are none and its key is none -- all R * W ring cells are null instances (EpInst::make_null) -- and the
+// highest columns of its per-key entries are none.
+constexpr uint32_t EP_INIT_WORD = 0;
+__device__ __forceinline__ u32x4 ep_init_p0() { return (u32x4){EP_INIT_WORD, EP_INIT_WORD, EP_INIT_WORD, EP_INIT_WORD}; }
+__device__ __forceinline__ u32x4 ep_init_p1() { return (u32x4){EP_NONE, EP_NONE, EP_NONE, EP_NONE}; }
+__device__ __forceinline__ u32x4 ep_init_p2() { return (u32x4){EP_NONE, (uint32_t)EP_NO_KEY << 8, EP_INIT_WORD, EP_NONE}; }
+__device__ __forceinline__ u32x4 ep_init_p3() { return (u32x4){EP_NONE, EP_NONE, EP_INIT_WORD, EP_INIT_WORD}; }
+static_assert(EP_INIT_WORD == 0, "create fills the arena with zero bytes");
+
+// ---- which group of the replica an image position holds: snapshot_common.h's SnapAllGroups / SnapGroupList -----------------
+// Chosen groups (smr_ep_save_groups / smr_ep_load_groups / smr_ep_reset_groups and their cluster forms) go through the same
+// image and the same bodies: an image of "these n groups, in this order" is the version-1 image of an n-group replica whose
+// group x is group list[x] of this one.  The image's side of every index is the position x with stride n (the scalar arrays,
+// the tiles, the bases, the placement); the object's side is the group g = list[x] with stride G (the view's and the executor's
+// arrays, the per-key entry (g * K + k) * hc_es at the view's own hc_es / hc_kv, order[j * G + g]).
+// What travels with a group is everything the image rules above cover.  What does not (WHOLE = false): the seven engine and eight
+// executor counters -- a group image holds zero counters and a load through a list leaves the target's alone, word 7 of the
+// shards (batch_stats) included, so sums over objects are conserved -- and, as for the whole object, ring cells outside the
+// live span, wire_acc and anything of smr_ep_cluster / smr_ep_spread.
+// Reset (FRESH, the unpack of nothing) writes what the list above says, for all R * W ring cells.  It does not write the reply
+// tables (pa_seq, pa_deps, xv_*) nor the executor's graph arrays and `order`: nothing reaches a reply-table entry without a
+// live cell's leader bookkeeping and ack / has-entry bits (the canonical rule above), the graph arrays are zero or dead
+// between two attempts, and `order` is read only below n_sub.
+
 // ---- the kernels --------------------------------------------------------------------------------------------------------
 // blockIdx.y = which replica of the call (the single calls are the cluster form with n = 1).  The views travel by value and are
 // indexed only by the block-uniform blockIdx.y, so they stay in the kernarg segment.  Tiles, bases and placement
@@ -154,21 +182,24 @@ struct EpSnapArgs {
     uint8_t *img[SMR_MAX_REPLICAS];
     uint64_t cap_c[SMR_MAX_REPLICAS], cap_r[SMR_MAX_REPLICAS], cap_x[SMR_MAX_REPLICAS];
     uint8_t oq[SMR_MAX_REPLICAS];                                // smr_ep_cfg.optimized_quorum (the view holds only the quorum sizes)
-    EpSnapGeom geo;
+    EpSnapGeom geo;                                              // the image's: of the snapshot's groups
 };
 
-// live cells and unpolled submissions in front of a wavefront: the replica's own (PACK) or the image's (of the same window: the
-// host has refused any other).  base[0] holds two counts, the live cells of every row in its low half and those of my row in its
-// high half -- each stays below 2^28 (smr_ep_replica_create: a record plane under 4 GB), and the prefix keeps its 96 bytes of LDS
-template <bool PACK>
-__device__ __forceinline__ void epsnap_bases(const EpView &v, const EpExec &x, const EpSnapGeom &Q, const EpSnapScal &sc, const SnapWave &w,
-                                             uint64_t (&base)[2], uint32_t (&mx)[2]) {
+// live cells and unpolled submissions in front of a wavefront, over image positions: the replica's own (PACK: of the group the
+// map puts there) or the image's (of the same window: the host has refused any other).  base[0] holds two counts, the live
+// cells of every row in its low half and those of my row in its high half -- each stays below 2^28 (smr_ep_replica_create: a
+// record plane under 4 GB), and the prefix keeps its 96 bytes of LDS.  NX: the image's groups
+template <bool PACK, class Map>
+__device__ __forceinline__ void epsnap_bases(const EpView &v, const EpExec &x, const EpSnapGeom &Q, const EpSnapScal &sc, const Map &M, size_t NX,
+                                             const SnapWave &w, uint64_t (&base)[2], uint32_t (&mx)[2]) {
     const uint32_t *const len = PACK ? v.len : sc.len, *const nsub = PACK ? x.n_sub : sc.nsub;
+    const size_t stride = PACK ? (size_t)v.G : NX;
     snap_bases(
-        [&](uint32_t g, uint64_t (&add)[2], uint32_t (&m)[2]) {
+        [&](uint32_t xi, uint64_t (&add)[2], uint32_t (&m)[2]) {
+            const uint32_t g = PACK ? M.group(xi, true) : xi;
             uint32_t all = 0, mine = 0;
             for (uint32_t r = 0; r < v.R; r++) {
-                const uint32_t n = ep_live_n(len[(size_t)r * v.G + g], v.W);
+                const uint32_t n = ep_live_n(len[(size_t)r * stride + g], v.W);
                 all += n; mine = r == v.me ? n : mine; m[0] = n > m[0] ? n : m[0];
             }
             uint32_t nx = Q.execute ? nsub[g] : 0u;
@@ -178,44 +209,50 @@ __device__ __forceinline__ void epsnap_bases(const EpView &v, const EpExec &x, c
         w.gb0, w.gw0, base, mx);
 }
 
-__global__ __launch_bounds__(256) void ep_snap_pack(const EpSnapArgs A) {
+// save: the whole replica (ep_snap_pack) or the listed groups (ep_snap_pack_groups).  xi: the lane's position in the image
+// (stride NX), g: its group in the replica (stride G).  The lanes behind the last position stay in every wave-wide step and
+// contribute nothing: their group reads as 0, their loads are safe and their stores guarded by `on`
+template <class Map>
+__device__ __forceinline__ void epsnap_pack_all(const EpSnapArgs &A, const Map &M) {
     const EpSnapGeom &Q = A.geo;
     const uint32_t rep = blockIdx.y < SMR_MAX_REPLICAS ? blockIdx.y : 0u;
     const EpView &v = A.v[rep];
     const EpExec &x = A.x[rep];
     const EpSnapImg S{A.img[rep], A.cap_c[rep], A.cap_r[rep], A.cap_x[rep]};
     const EpSnapScal sc = epsnap_scal(S.base, Q);
-    const SnapWave w = snap_wave(Q.tiles, v.G);
-    const size_t G = v.G;
+    const uint32_t ni = M.n(v.G, Q.G);
+    const SnapWave w = snap_wave(Q.tiles, ni);
+    const size_t G = v.G, NX = ni;
     const uint32_t R = v.R, W = v.W, K = v.n_keys, rec = v.recovery, wshift = 31u - (uint32_t)__clz((int)W);
     uint64_t base[2];
     uint32_t mx[2];
-    epsnap_bases<true>(v, x, Q, sc, w, base, mx);
+    epsnap_bases<true>(v, x, Q, sc, M, NX, w, base, mx);
     uint64_t rbase = rec ? (base[0] & 0xFFFFFFFFull) : (base[0] >> 32);   // reply records in front
     base[0] &= 0xFFFFFFFFull;                                             // cell records in front
     u32x4 *const cells = (u32x4 *)(S.base + Q.fixed);
     uint8_t *const reps = S.base + epsnap_off_rep(Q, S);
     EpSnapExec *const execs = (EpSnapExec *)(S.base + epsnap_off_exec(Q, S));
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
-        const bool on = g < v.G;
+        const uint32_t xi = t * 64 + w.lane;
+        const bool on = xi < ni;
+        const uint32_t g = M.group(xi, on);
         uint32_t nx = 0;
         if (on) {
             for (uint32_t r = 0; r < R; r++) {
-                const size_t o = (size_t)r * G + g;
-                sc.len[o] = v.len[o]; sc.cb[o] = v.commit_bars[o];
-                if (Q.execute) { sc.eb[o] = x.exec_bars[o]; sc.pcb[o] = x.prev_cb[o]; }
+                const size_t o = (size_t)r * G + g, oi = (size_t)r * NX + xi;
+                sc.len[oi] = v.len[o]; sc.cb[oi] = v.commit_bars[o];
+                if (Q.execute) { sc.eb[oi] = x.exec_bars[o]; sc.pcb[oi] = x.prev_cb[o]; }
             }
-            sc.rew[g] = v.rewritten[g] ? 1 : 0;
+            sc.rew[xi] = v.rewritten[g] ? 1 : 0;
             if (Q.execute) {
                 nx = x.n_sub[g];
                 if (nx > 2u * R * W) nx = 2u * R * W;
-                sc.digest[g] = x.digest[g]; sc.nsub[g] = nx;
+                sc.digest[xi] = x.digest[g]; sc.nsub[xi] = nx;
             }
             for (uint32_t k = 0; k < K; k++) {                   // my entries of the per-key table, wherever the view keeps them
                 const uint32_t *const e = v.hc + ((size_t)g * K + k) * v.hc_es;
-                for (uint32_t r = 0; r < R; r++) sc.hc[((size_t)k * R + r) * G + g] = e[r];
-                if (Q.execute) sc.kv[(size_t)k * G + g] = ep_kv_unpack(e[v.hc_kv]);
+                for (uint32_t r = 0; r < R; r++) sc.hc[((size_t)k * R + r) * NX + xi] = e[r];
+                if (Q.execute) sc.kv[(size_t)k * NX + xi] = ep_kv_unpack(e[v.hc_kv]);
             }
         }
         for (uint32_t r = 0; r < R; r++) {
@@ -264,23 +301,27 @@ __global__ __launch_bounds__(256) void ep_snap_pack(const EpSnapArgs A) {
         });
         mx[1] = maxx > mx[1] ? maxx : mx[1];
     }
-    snap_counters_save<7>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
-    if (Q.execute) snap_counters_save<8>(x.counters, (uint64_t *)(S.base + Q.off_ctr) + 7);
+    if (Map::WHOLE) {
+        snap_counters_save<7>(v.counters, (uint64_t *)(S.base + Q.off_ctr));
+        if (Q.execute) snap_counters_save<8>(x.counters, (uint64_t *)(S.base + Q.off_ctr) + 7);
+    } else if (blockIdx.x == 0 && threadIdx.x < 7u + (Q.execute ? 8u : 0u)) {
+        ((uint64_t *)(S.base + Q.off_ctr))[threadIdx.x] = 0;     // a group image carries no counters
+    }
     if (w.last && w.lane == 0) {                                 // the wavefront of the last tile knows the totals
         if (rec) rbase = base[0];
         EpSnapHdr h;
         h.magic = EPSNAP_MAGIC; h.version = EPSNAP_VERSION;
         h.bytes = epsnap_bytes(Q, base[0], rbase, base[1]);
-        h.n_groups = v.G; h.population = (uint8_t)R; h.me = (uint8_t)v.me;
+        h.n_groups = ni; h.population = (uint8_t)R; h.me = (uint8_t)v.me;
         h.optimized_quorum = A.oq[rep];
         h.execute = (uint8_t)Q.execute; h.recovery = (uint8_t)rec;
         h.reserved0[0] = h.reserved0[1] = h.reserved0[2] = 0;
         h.window = W; h.n_keys = K; h.max_live = mx[0];
         h.n_cells = base[0]; h.n_exec = base[1]; h.max_exec = mx[1]; h.n_replies = (uint32_t)rbase;
         *(EpSnapHdr *)S.base = h;
-        snap_zero_pad(S.base, Q.o_len, 4 * G * R); snap_zero_pad(S.base, Q.o_cb, 4 * G * R); snap_zero_pad(S.base, Q.o_rew, G);
-        if (Q.execute) { snap_zero_pad(S.base, Q.o_eb, 4 * G * R); snap_zero_pad(S.base, Q.o_pcb, 4 * G * R); snap_zero_pad(S.base, Q.o_nsub, 4 * G); }
-        snap_zero_pad(S.base, Q.o_hc, 4 * G * R * K);
+        snap_zero_pad(S.base, Q.o_len, 4 * NX * R); snap_zero_pad(S.base, Q.o_cb, 4 * NX * R); snap_zero_pad(S.base, Q.o_rew, NX);
+        if (Q.execute) { snap_zero_pad(S.base, Q.o_eb, 4 * NX * R); snap_zero_pad(S.base, Q.o_pcb, 4 * NX * R); snap_zero_pad(S.base, Q.o_nsub, 4 * NX); }
+        snap_zero_pad(S.base, Q.o_hc, 4 * NX * R * K);
         for (uint64_t p = Q.o_end; p < Q.fixed; p++) S.base[p] = 0;
     }
 }
@@ -288,49 +329,76 @@ __global__ __launch_bounds__(256) void ep_snap_pack(const EpSnapArgs A) {
 // Load re-establishes, every one from the image's values: every scalar; the live cells' records at column & Wmask, with sq32 =
 // min(seq, 2^32 - 1) beside p0 and m0 / m1 repacked; xp_max; the reply tables' entries of those cells; the per-key entries at the
 // view's own hc_es / hc_kv (a replica seated in a cluster's shared table loads into its slots of that table) with the KV word
-// through ep_kv_pack; my_nulls recounted; order / n_sub as ring cells of this replica; the counters as one shard.
-__global__ __launch_bounds__(256) void ep_snap_unpack(const EpSnapArgs A) {
+// through ep_kv_pack; my_nulls recounted; order / n_sub as ring cells of this replica; the counters as one shard (the whole
+// replica only).
+// FRESH: the unpack of nothing -- no image is read, the listed groups become what smr_ep_replica_create leaves (EP_INIT_* above),
+// all R * W ring cells included, which is how smr_ep_reset_groups empties a slot
+template <class Map, bool FRESH>
+__device__ __forceinline__ void epsnap_unpack_all(const EpSnapArgs &A, const Map &M) {
     const EpSnapGeom &Q = A.geo;
     const uint32_t rep = blockIdx.y < SMR_MAX_REPLICAS ? blockIdx.y : 0u;
     const EpView &v = A.v[rep];
     const EpExec &x = A.x[rep];
     const EpSnapImg S{A.img[rep], A.cap_c[rep], A.cap_r[rep], A.cap_x[rep]};
     const EpSnapScal sc = epsnap_scal(S.base, Q);
-    const SnapWave w = snap_wave(Q.tiles, v.G);
-    const size_t G = v.G;
+    const uint32_t ni = M.n(v.G, Q.G);
+    const SnapWave w = snap_wave(Q.tiles, ni);
+    const size_t G = v.G, NX = ni;
     const uint32_t R = v.R, W = v.W, K = v.n_keys, rec = v.recovery, wshift = 31u - (uint32_t)__clz((int)W);
-    uint64_t base[2];
+    uint64_t base[2] = {0, 0};
     uint32_t mx[2];
-    epsnap_bases<false>(v, x, Q, sc, w, base, mx);
+    if (!FRESH) epsnap_bases<false>(v, x, Q, sc, M, NX, w, base, mx);
     uint64_t rbase = rec ? (base[0] & 0xFFFFFFFFull) : (base[0] >> 32);
     base[0] &= 0xFFFFFFFFull;
     const u32x4 *const cells = (const u32x4 *)(S.base + Q.fixed);
     const uint8_t *const reps = S.base + epsnap_off_rep(Q, S);
     const EpSnapExec *const execs = (const EpSnapExec *)(S.base + epsnap_off_exec(Q, S));
     for (uint32_t t = w.t0; t < w.t1; t++) {
-        const uint32_t g = t * 64 + w.lane;
-        const bool on = g < v.G;
+        const uint32_t xi = t * 64 + w.lane;
+        const bool on = xi < ni;
+        const uint32_t g = M.group(xi, on);
         uint32_t nx = 0, nulls = 0;
-        if (on) {
+        if (on && FRESH) {
             for (uint32_t r = 0; r < R; r++) {
                 const size_t o = (size_t)r * G + g;
-                v.len[o] = sc.len[o]; v.commit_bars[o] = sc.cb[o];
-                if (Q.execute) { x.exec_bars[o] = sc.eb[o]; x.prev_cb[o] = sc.pcb[o]; }
+                v.len[o] = EP_INIT_WORD; v.commit_bars[o] = EP_INIT_WORD;
+                if (Q.execute) { x.exec_bars[o] = EP_INIT_WORD; x.prev_cb[o] = EP_INIT_WORD; }
             }
-            v.rewritten[g] = sc.rew[g];
+            v.rewritten[g] = (uint8_t)EP_INIT_WORD; v.my_nulls[g] = EP_INIT_WORD;
+            if (Q.execute) { x.digest[g] = EP_INIT_WORD; x.n_sub[g] = EP_INIT_WORD; }
+            for (uint32_t k = 0; k < K; k++) {
+                uint32_t *const e = v.hc + ((size_t)g * K + k) * v.hc_es;
+                for (uint32_t r = 0; r < R; r++) e[r] = EP_NONE;
+                e[v.hc_kv] = EP_INIT_WORD;
+            }
+            for (uint32_t c = 0; c < R * W; c++) {               // every ring cell a null instance
+                const size_t i = (size_t)c * G + g;
+                v.p0[i] = ep_init_p0(); v.sq32[i] = EP_INIT_WORD; v.p1[i] = ep_init_p1(); v.p2[i] = ep_init_p2();
+                if (R > 6) v.p3[i] = ep_init_p3();
+                if (rec) v.xp_max[i] = EP_INIT_WORD;
+            }
+        }
+        if (FRESH) continue;
+        if (on) {
+            for (uint32_t r = 0; r < R; r++) {
+                const size_t o = (size_t)r * G + g, oi = (size_t)r * NX + xi;
+                v.len[o] = sc.len[oi]; v.commit_bars[o] = sc.cb[oi];
+                if (Q.execute) { x.exec_bars[o] = sc.eb[oi]; x.prev_cb[o] = sc.pcb[oi]; }
+            }
+            v.rewritten[g] = sc.rew[xi];
             if (Q.execute) {
-                nx = sc.nsub[g];
+                nx = sc.nsub[xi];
                 if (nx > 2u * R * W) nx = 2u * R * W;            // (refused by the host)
-                x.digest[g] = sc.digest[g]; x.n_sub[g] = nx;
+                x.digest[g] = sc.digest[xi]; x.n_sub[g] = nx;
             }
             for (uint32_t k = 0; k < K; k++) {
                 uint32_t *const e = v.hc + ((size_t)g * K + k) * v.hc_es;
-                for (uint32_t r = 0; r < R; r++) e[r] = sc.hc[((size_t)k * R + r) * G + g];
-                if (Q.execute) e[v.hc_kv] = ep_kv_pack(sc.kv[(size_t)k * G + g]);
+                for (uint32_t r = 0; r < R; r++) e[r] = sc.hc[((size_t)k * R + r) * NX + xi];
+                if (Q.execute) e[v.hc_kv] = ep_kv_pack(sc.kv[(size_t)k * NX + xi]);
             }
         }
         for (uint32_t r = 0; r < R; r++) {
-            const uint32_t len = on ? sc.len[(size_t)r * G + g] : 0u, lo = ep_live_lo(len, W);
+            const uint32_t len = on ? sc.len[(size_t)r * NX + xi] : 0u, lo = ep_live_lo(len, W);
             const bool tab = rec || r == v.me;
             const uint64_t b0 = base[0];
             snap_place(len - lo, base[0], S.cap_c, w.lane, [&](uint32_t k, uint64_t pos) {
@@ -367,8 +435,20 @@ __global__ __launch_bounds__(256) void ep_snap_unpack(const EpSnapArgs A) {
             x.order[(size_t)j * G + g] = (uint16_t)((row << wshift) | (e.col & v.Wmask));
         });
     }
-    snap_counters_load<7>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
-    if (Q.execute) snap_counters_load<8>((const uint64_t *)(S.base + Q.off_ctr) + 7, x.counters);
+    if (Map::WHOLE) {
+        snap_counters_load<7>((const uint64_t *)(S.base + Q.off_ctr), v.counters);
+        if (Q.execute) snap_counters_load<8>((const uint64_t *)(S.base + Q.off_ctr) + 7, x.counters);
+    }
+}
+
+__global__ __launch_bounds__(256) void ep_snap_pack(const EpSnapArgs A) { epsnap_pack_all(A, SnapAllGroups{}); }
+__global__ __launch_bounds__(256) void ep_snap_unpack(const EpSnapArgs A) { epsnap_unpack_all<SnapAllGroups, false>(A, SnapAllGroups{}); }
+// group x of the image (A.geo.G = n groups) <-> group list[x] of the replica, one list for all replicas of the call; fresh: no
+// image, the listed groups as a new replica object holds them (A carries the geometry of n groups and no buffers)
+__global__ __launch_bounds__(256) void ep_snap_pack_groups(const EpSnapArgs A, const uint32_t *list) { epsnap_pack_all(A, SnapGroupList{list}); }
+__global__ __launch_bounds__(256) void ep_snap_unpack_groups(const EpSnapArgs A, const uint32_t *list, int fresh) {
+    if (fresh) epsnap_unpack_all<SnapGroupList, true>(A, SnapGroupList{list});
+    else epsnap_unpack_all<SnapGroupList, false>(A, SnapGroupList{list});
 }
 
 }  // namespace smr

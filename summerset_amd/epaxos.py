@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import snapshot as _snapshot
 from .snapshot import DeviceSnapshot
 from ._lib import EpCfg, EpDumpBufs, EpExpPrepare, EpExpPrepareReply, EpMsg, check, stream_ptr
 
@@ -33,7 +34,9 @@ class EPaxosSnapshot(DeviceSnapshot):
     `EPaxosReplicaGroup.save_state` fills and `load_state` takes.  `export()` gives the canonical image as bytes -- equal for any
     two replicas whose dumps agree -- and `import_` takes one back (of a replica like the one this snapshot was made for; any
     window).  `create_like`: room for every ring cell live and a full submission list.  `info()`: bytes, n_cells, n_exec,
-    n_groups, window, n_keys, max_live, max_exec, population, me, optimized_quorum, execute, recovery"""
+    n_groups, window, n_keys, max_live, max_exec, population, me, optimized_quorum, execute, recovery.
+    `EPaxosSnapshot(like, n_groups)`: for that many of its groups only (`smr_ep_snapshot_create_groups`) -- what `save_groups`
+    fills and `load_groups` takes, the image of an n_groups replica"""
     _STEM, _INFO = "smr_ep_snapshot", _lib.EpSnapshotInfo
 
     def save(self, replica, stream=None):
@@ -65,6 +68,32 @@ def load_cluster_state(reps, snaps, stream=None):
     if len(snaps) != len(reps):
         raise ValueError("load_cluster_state: %d replicas, %d snapshots" % (len(reps), len(snaps)))
     check(_lib.load().smr_ep_cluster_load_state(len(reps), _handles(reps), _handles(snaps), stream_ptr(stream)))
+
+
+def save_cluster_groups(reps, groups, snaps=None, stream=None):
+    """`reps[k].save_groups(groups, snaps[k])` for up to 8 replicas of one co-located cluster in ONE launch, one list for all of
+    them (`smr_ep_cluster_save_groups`); returns the snapshots (new ones without `snaps`)"""
+    return _snapshot.save_cluster_groups("smr_ep", EPaxosSnapshot, reps, groups, snaps, stream)
+
+
+def load_cluster_groups(reps, snaps, groups, stream=None):
+    """`reps[k].load_groups(snaps[k], groups)` for up to 8 replicas of one co-located cluster in ONE launch
+    (`smr_ep_cluster_load_groups`)"""
+    _snapshot.load_cluster_groups("smr_ep", reps, snaps, groups, stream)
+
+
+def reset_cluster_groups(reps, groups, stream=None):
+    """`reps[k].reset_groups(groups)` for up to 8 replicas of one co-located cluster in ONE launch (`smr_ep_cluster_reset_groups`)"""
+    _snapshot.reset_cluster_groups("smr_ep", reps, groups, stream)
+
+
+def move_groups(src_reps, src_groups, dst_reps, dst_groups, snaps=None, reset=True):
+    """groups src_groups[i] of the replica objects `src_reps` become groups dst_groups[i] of `dst_reps` (replica k to replica k,
+    between two handler calls / ticks of both): one cluster save, one cluster load, and the source's slots back to what a new
+    object holds.  The unpolled submissions go along and are handed over by the destination under its group ids; the counters
+    stay where the events happened.  Returns the snapshots, for the next move of as many groups.  Which job group sits in which
+    slot is the caller's table"""
+    return _snapshot.move_cluster_groups("smr_ep", EPaxosSnapshot, src_reps, src_groups, dst_reps, dst_groups, snaps, reset)
 
 
 class EPaxosReplicaGroup:
@@ -146,6 +175,20 @@ class EPaxosReplicaGroup:
         """overwrite my whole logical state with a snapshot's (`smr_ep_load_state`): same n_groups, population, replica id,
         optimized_quorum, execute, recovery, n_keys and window"""
         snap.load(self, stream)
+
+    def save_groups(self, groups, snap=None, stream=None):
+        """the listed groups' state as the image of a len(groups) replica, group i of it = groups[i] (`smr_ep_save_groups`),
+        into `snap` (made with `EPaxosSnapshot(self, len(groups))`) or a new one"""
+        return _snapshot.save_groups("smr_ep", EPaxosSnapshot, self, groups, snap, stream)
+
+    def load_groups(self, snap, groups, stream=None):
+        """group i of a len(groups) image overwrites my group groups[i]; nothing of any other group changes
+        (`smr_ep_load_groups`)"""
+        _snapshot.load_groups("smr_ep", self, snap, groups, stream)
+
+    def reset_groups(self, groups, stream=None):
+        """the listed groups back to what a new replica object holds (`smr_ep_reset_groups`)"""
+        _snapshot.reset_groups("smr_ep", self, groups, stream)
 
     # ---- explicit prepare (recovery=True) ----
     def heartbeat_timeout(self, src, exploded=None, stream=None):

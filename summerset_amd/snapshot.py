@@ -22,7 +22,7 @@ class DeviceSnapshot:
     _INFO = None       # the ctypes struct <stem>_info_get fills
 
     def __init__(self, like, n_groups=None):
-        """room for the worst case of `like`; n_groups (MultiPaxos, Raft, RSPaxos, the payload stores: <stem>_create_groups): for
+        """room for the worst case of `like`; n_groups (every engine and the payload stores: <stem>_create_groups): for
         that many of its groups only -- what `save_groups` fills and `load_groups` takes, the image of an n_groups object"""
         self._L = _lib.load()
         h = C.c_void_p()
