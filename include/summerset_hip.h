@@ -2026,6 +2026,97 @@ int smr_skv_heap(smr_skv *h, uint8_t **heap_dev, uint64_t *heap_bytes_per_group)
 int smr_skv_read(smr_skv *h, uint32_t group, uint32_t off, uint32_t len, uint8_t *host_buf);
 int smr_skv_stats(smr_skv *h, uint32_t *n_keys_host, uint32_t *heap_used_host, uint8_t *full_host);
 
+/* ---- the two state machines' state: save, load, chosen groups, compaction -- on the device -----------------------------------
+ * What the reference's snapshot is first of all: a dump of the KV pairs (multipaxos/snapshot.rs:14-51 snapshot_dump_kv_pairs,
+ * :189-260 recover_from_snapshot).  The engines' images carry logs and ballots; these carry the state the engines replicate, so a
+ * job that moves groups between objects (smr_mp_save_groups, smr_raft_*, smr_rsp_*) moves their key-value state with the same
+ * calls, the same list and the same rules.  X = skv (the string store) or kv (the token table):
+ *   smr_X_snapshot_create    a snapshot object with worst-case room for an object like `like` (the string store: every entry
+ *                            live, the heap all live bytes), and the launches' scratch: a save into it only enqueues.  Room
+ *                            grows only by sizes the host knows (a save out of a store of a larger geometry);
+ *   smr_X_snapshot_create_groups   the same for n of its groups: what smr_X_save_groups fills and smr_X_load_groups takes;
+ *   smr_X_save_state / smr_X_load_state   the whole object, on `stream`.  A load synchronises once per save to read the header;
+ *   smr_X_save_groups        group i of the image = group groups_host[i] of the object; enqueues only, apart from handing the
+ *                            list to the device (an async copy on `stream` into a buffer the snapshot owns).  The object is not
+ *                            modified;
+ *   smr_X_load_groups        the inverse: group i of an n-group image overwrites the whole state of group groups_host[i];
+ *                            nothing of any other group changes.  An image of "these n groups, in this order" is the ordinary
+ *                            image of an n-group object: a group image and a whole image of an n-group object are interchangeable;
+ *   smr_X_reset_groups       the listed groups back to exactly what smr_X_create leaves for a group;
+ *   smr_X_snapshot_info_get / _export / _import   sizes (synchronises), the packed image as bytes, and back.  Import validates
+ *                            everything and never reads past len.
+ * The list is a host array (a move is a rare host decision), checked before anything is launched, allocated or written: n in
+ * 1 .. n_groups, every id below n_groups, none twice; for save and load n is the snapshot's n_groups.  SMR_ERR_ARG for these, for
+ * a null argument, a malformed image, and an image that does not fit the target; SMR_ERR_STATE for an empty snapshot.  A refused
+ * call leaves object and snapshot untouched.
+ * A snapshot object serves ONE call at a time: a save fills it, and a load -- though it takes the snapshot as const and leaves
+ * the image alone -- reads the header back on first use and uses launch scratch the snapshot owns (record offsets), so two loads
+ * of one snapshot must not overlap on two streams; stream order on one stream is enough.
+ *
+ * The string store's image (version 1) is CANONICAL: it holds the live pairs and nothing else, so two stores that hold the same
+ * maps export the same bytes whatever their slots, heap_bytes, probe history or number of overwrites.  Little-endian; sections on
+ * multiples of 8, the byte section on a multiple of 16; padding is zero:
+ *   header 64 B      u32 magic "SSKV", version, n_groups, max_keys, max_group_bytes (max over groups of sum(klen + vlen)), 0;
+ *                    u64 bytes, n_records, byte-section size, 0, 0
+ *   n_keys u32[n], full u8[n]      each padded to 8
+ *   records          {hash u64, klen u32, vlen u32}, then zero bytes up to a multiple of 16
+ *   bytes            per record, in record order: key bytes, value bytes, the run zero-padded to a multiple of 16
+ * Record order: tile-major over 64 image positions, then rank, then position; rank within a group is ascending (hash, klen, key
+ * bytes), hash the FNV-1a word of the key.  The sticky full flag travels: a frozen group stays frozen.
+ * A load fits where max_keys <= slots and max_group_bytes <= heap_bytes of the target (checked on the host from the header).  It
+ * is deterministic in (image, slots): the table cleared, the records inserted in rank order by linear probing from hash & mask,
+ * keys and values written contiguously in record order from heap offset 0, heap_used = sum(klen + vlen) -- so a save and a load
+ * of the same groups into the same store is a COMPACTION: the bytes overwritten Puts left behind are reclaimed.  Do it before
+ * the heap fills; a group that is full already stays full.
+ * A load or a reset REWRITES the listed groups' heap strips: (off, len) results smr_skv_execute returned earlier for those groups
+ * are no longer valid (read them first); other groups' strips and results are untouched.  Heap bytes at and behind heap_used
+ * are not state and are not touched.
+ * What does not travel: nothing is left out of a group's state.  (The stores keep no counters and no unpolled lists.)
+ *
+ * The token table's image: header 64 B (u32 magic "SKKV", version, n_groups, n_keys; u64 bytes; zeros), then u32 kv[n_keys][n]
+ * padded to 8.  A load needs the same n_keys. */
+typedef struct smr_skv_snapshot smr_skv_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint64_t n_records, byte_bytes; /* live pairs over all groups; size of the byte section */
+    uint32_t n_groups, max_keys, max_group_bytes, reserved;
+} smr_skv_snapshot_info;
+int smr_skv_snapshot_create(const smr_skv *like, smr_skv_snapshot **out);
+int smr_skv_snapshot_create_groups(const smr_skv *like, uint32_t n, smr_skv_snapshot **out);
+void smr_skv_snapshot_destroy(smr_skv_snapshot *s);
+int smr_skv_snapshot_info_get(const smr_skv_snapshot *s, smr_skv_snapshot_info *out);
+int64_t smr_skv_snapshot_export(const smr_skv_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_skv_snapshot_import(smr_skv_snapshot *s, const uint8_t *host, uint64_t len);
+int smr_skv_save_state(smr_skv *h, smr_skv_snapshot *s, void *stream);
+int smr_skv_load_state(smr_skv *h, const smr_skv_snapshot *s, void *stream);
+int smr_skv_save_groups(smr_skv *h, const uint32_t *groups_host, uint32_t n, smr_skv_snapshot *s, void *stream);
+int smr_skv_load_groups(smr_skv *h, const smr_skv_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_skv_reset_groups(smr_skv *h, const uint32_t *groups_host, uint32_t n, void *stream);
+/* UNSTABLE -- tests and measurement only, not part of the supported interface; they expose the internal layout and may change
+ * or go with any release: the one device allocation that holds the store (what a wholesale copy would move) and where its
+ * nine arrays begin in it -- hash u64, koff, klen, voff, vlen u32 [slots][G]; heap [G][heap_bytes]; heap_used u32, full u8,
+ * n_keys u32 [G] --; a host copy of bytes of it (synchronises); the snapshot's device buffer */
+int smr_skv_debug_arena(smr_skv *h, void **base_dev, uint64_t *n_bytes, uint64_t offsets[9]);
+int smr_skv_debug_read(smr_skv *h, uint64_t off, uint64_t len, uint8_t *host_buf);
+int smr_skv_snapshot_debug_buffer(const smr_skv_snapshot *s, void **dev, uint64_t *n_bytes);
+
+typedef struct smr_kv_snapshot smr_kv_snapshot;
+typedef struct {
+    uint64_t bytes;                 /* size of the exported image */
+    uint32_t n_groups, n_keys;
+} smr_kv_snapshot_info;
+int smr_kv_snapshot_create(const smr_kv *like, smr_kv_snapshot **out);
+int smr_kv_snapshot_create_groups(const smr_kv *like, uint32_t n, smr_kv_snapshot **out);
+void smr_kv_snapshot_destroy(smr_kv_snapshot *s);
+int smr_kv_snapshot_info_get(const smr_kv_snapshot *s, smr_kv_snapshot_info *out);
+int64_t smr_kv_snapshot_export(const smr_kv_snapshot *s, uint8_t *host, uint64_t cap);
+int smr_kv_snapshot_import(smr_kv_snapshot *s, const uint8_t *host, uint64_t len);
+int smr_kv_save_state(smr_kv *h, smr_kv_snapshot *s, void *stream);
+int smr_kv_load_state(smr_kv *h, const smr_kv_snapshot *s, void *stream);
+int smr_kv_save_groups(smr_kv *h, const uint32_t *groups_host, uint32_t n, smr_kv_snapshot *s, void *stream);
+int smr_kv_load_groups(smr_kv *h, const smr_kv_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
+int smr_kv_reset_groups(smr_kv *h, const uint32_t *groups_host, uint32_t n, void *stream);
+
 /* ---- batched Heartbeater (src/server/heartbeat.rs:26-296) --------------------------------
  * One object = replica `replica_id` of n_groups groups: hear timers, send ticker, reply counters / peer_alive.  Clocks and
  * randomness are explicit: calls take now_ms; a kickoff takes draw[R][G], the u32 each timer's random_range would have

@@ -11,6 +11,7 @@ from ._lib import SummersetError, SMR_CTL_IDENTITY, SMR_NO_REPLICA  # noqa: F401
 from .rscoding import RSCodewordBatch, rs_matrix, rs_shard_len  # noqa: F401
 from .multipaxos import MpSnapshot, MultiPaxosCluster, move_groups  # noqa: F401
 from .quorumread import KvStateMachine, QuorumReadGroup, StringKvStateMachine  # noqa: F401
+from .quorumread import KvSnapshot, StringKvSnapshot, move_kv_groups, move_skv_groups  # noqa: F401
 from .raft import CRaftLeaderGroup, RaftLeaderGroup, RaftSnapshot, load_cluster_state, save_cluster_state  # noqa: F401
 from .raft import load_cluster_groups, reset_cluster_groups, save_cluster_groups  # noqa: F401
 from .raft import move_groups as move_raft_groups  # noqa: F401

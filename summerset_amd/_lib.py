@@ -85,6 +85,15 @@ class PstoreSnapshotInfo(C.Structure):
                 ("n_data_shards", C.c_uint8), ("planes", C.c_uint8), ("craft", C.c_uint8)]
 
 
+class SkvSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_records", C.c_uint64), ("byte_bytes", C.c_uint64), ("n_groups", C.c_uint32),
+                ("max_keys", C.c_uint32), ("max_group_bytes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KvSnapshotInfo(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("n_groups", C.c_uint32), ("n_keys", C.c_uint32)]
+
+
 class MpSnapshotInfo(C.Structure):
     _fields_ = [("bytes", C.c_uint64), ("n_slots", C.c_uint64), ("n_outbox", C.c_uint64), ("n_groups", C.c_uint32),
                 ("max_live", C.c_uint32), ("max_outbox", C.c_uint32), ("population", C.c_uint8), ("commit_extra", C.c_uint8),
@@ -524,6 +533,17 @@ SYMBOLS = [
     ("smr_kv_execute", _i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("smr_kv_table", _i, [_vp, C.POINTER(_vp)]),
     ("smr_kv_dump", _i, [_vp, _vp]),
+    ("smr_kv_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_kv_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_kv_snapshot_destroy", None, [_vp]),
+    ("smr_kv_snapshot_info_get", _i, [_vp, C.POINTER(KvSnapshotInfo)]),
+    ("smr_kv_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_kv_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_kv_save_state", _i, [_vp, _vp, _vp]),
+    ("smr_kv_load_state", _i, [_vp, _vp, _vp]),
+    ("smr_kv_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_kv_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_kv_reset_groups", _i, [_vp, _vp, _u32, _vp]),
     ("smr_qread_create", _i, [C.POINTER(QreadCfg), C.POINTER(_vp)]),
     ("smr_qread_destroy", None, [_vp]),
     ("smr_qread_refresh_highest_slot", _i, [_vp, _vp, _vp, _vp]),
@@ -537,6 +557,20 @@ SYMBOLS = [
     ("smr_skv_heap", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_skv_read", _i, [_vp, _u32, _u32, _u32, _vp]),
     ("smr_skv_stats", _i, [_vp, _vp, _vp, _vp]),
+    ("smr_skv_snapshot_create", _i, [_vp, C.POINTER(_vp)]),
+    ("smr_skv_snapshot_create_groups", _i, [_vp, _u32, C.POINTER(_vp)]),
+    ("smr_skv_snapshot_destroy", None, [_vp]),
+    ("smr_skv_snapshot_info_get", _i, [_vp, C.POINTER(SkvSnapshotInfo)]),
+    ("smr_skv_snapshot_export", C.c_int64, [_vp, _vp, _u64]),
+    ("smr_skv_snapshot_import", _i, [_vp, _vp, _u64]),
+    ("smr_skv_save_state", _i, [_vp, _vp, _vp]),
+    ("smr_skv_load_state", _i, [_vp, _vp, _vp]),
+    ("smr_skv_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("smr_skv_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
+    ("smr_skv_reset_groups", _i, [_vp, _vp, _u32, _vp]),
+    ("smr_skv_debug_arena", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64 * 9)]),
+    ("smr_skv_debug_read", _i, [_vp, _u64, _u64, _vp]),
+    ("smr_skv_snapshot_debug_buffer", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("smr_hb_create", _i, [C.POINTER(HbCfg), _u64, C.POINTER(_vp)]),
     ("smr_hb_destroy", None, [_vp]),
     ("smr_hb_set_sending", _i, [_vp, _vp, _vp]),

@@ -9,6 +9,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import snapshot as _snapshot
+from .snapshot import DeviceSnapshot
 from ._lib import QreadCfg, QreadLog, QreadReplies, check, stream_ptr
 
 NONE, SLOT, VALUE = 0, 1, 2                       # Option<(slot, Option<value>)>
@@ -96,9 +98,81 @@ class QuorumReadGroup:
 GET, PUT = 0, 1
 
 
-class KvStateMachine:
+class _GroupStateCalls:
+    """what both state machines do with snapshots: thin calls of snapshot.py's helpers, given the C symbol stem and the class"""
+    _STEM = _SNAP = None
+
+    def save_state(self, snap=None, stream=None):
+        """the whole object's state into a snapshot on the device (a new one if none is given); returns it"""
+        return _snapshot.save_state(self._STEM, self._SNAP, self, snap, stream)
+
+    def load_state(self, snap, stream=None):
+        _snapshot.load_state(self._STEM, self, snap, stream)
+
+    def save_groups(self, groups, snap=None, stream=None):
+        """groups[i] becomes group i of an image of len(groups) groups; returns the snapshot"""
+        return _snapshot.save_groups(self._STEM, self._SNAP, self, groups, snap, stream)
+
+    def load_groups(self, snap, groups, stream=None):
+        """group i of the image overwrites group groups[i]; no other group changes"""
+        _snapshot.load_groups(self._STEM, self, snap, groups, stream)
+
+    def reset_groups(self, groups, stream=None):
+        """the listed groups back to what a new object holds"""
+        _snapshot.reset_groups(self._STEM, self, groups, stream)
+
+
+class KvSnapshot(DeviceSnapshot):
+    """A token table's state held on the device (`smr_kv_snapshot`): header + kv[n_keys][n_groups].  `KvSnapshot(like, n)`: for
+    n of its groups (`save_groups` / `load_groups`).  `info()`: bytes, n_groups, n_keys"""
+    _STEM, _INFO = "smr_kv_snapshot", _lib.KvSnapshotInfo
+
+    def table(self):
+        """the exported image's table as uint32 [n_keys, n_groups]"""
+        i = self.info()
+        return np.frombuffer(self.export(), "<u4", i["n_keys"] * i["n_groups"], 64).reshape(i["n_keys"], i["n_groups"]).copy()
+
+
+class StringKvSnapshot(DeviceSnapshot):
+    """A string store's live pairs held on the device (`smr_skv_snapshot`).  `export()` gives the canonical image -- equal for any
+    two stores that hold the same maps, whatever their slots, heap_bytes or history.  `StringKvSnapshot(like, n)`: for n of its
+    groups.  `info()`: bytes, n_records, byte_bytes, n_groups, max_keys, max_group_bytes"""
+    _STEM, _INFO = "smr_skv_snapshot", _lib.SkvSnapshotInfo
+
+    def items(self):
+        """the exported image as one dict[bytes, bytes] per image position: what the reference's `snapshot_dump_kv_pairs`
+        (multipaxos/snapshot.rs:14-51) writes"""
+        img = self.export()
+        n, n_rec = (int(x) for x in (np.frombuffer(img, "<u4", 1, 8)[0], np.frombuffer(img, "<u8", 1, 32)[0]))
+        a8 = lambda x: (x + 7) & ~7          # noqa: E731
+        o_full = 64 + a8(4 * n)
+        o_rec = o_full + a8(n)
+        nk = np.frombuffer(img, "<u4", n, 64)
+        rec = np.frombuffer(img, np.dtype([("hash", "<u8"), ("klen", "<u4"), ("vlen", "<u4")]), n_rec, o_rec)
+        off, pos = (o_rec + 16 * n_rec + 15) & ~15, 0
+        out = [dict() for _ in range(n)]
+        for t0 in range(0, n, 64):                               # tile-major, then rank, then position
+            c = nk[t0:t0 + 64]
+            for k in range(int(c.max()) if len(c) else 0):
+                for x in np.nonzero(c > k)[0]:
+                    kl, vl = int(rec["klen"][pos]), int(rec["vlen"][pos])
+                    out[t0 + int(x)][img[off:off + kl]] = img[off + kl:off + kl + vl]
+                    off += (kl + vl + 15) & ~15
+                    pos += 1
+        return out
+
+    def full_flags(self):
+        """the exported image's sticky full flag per image position, uint8 [n_groups]"""
+        img = self.export()
+        n = int(np.frombuffer(img, "<u4", 1, 8)[0])
+        return np.frombuffer(img, np.uint8, n, 64 + ((4 * n + 7) & ~7)).copy()
+
+
+class KvStateMachine(_GroupStateCalls):
     """`StateMachineExecutorTask::execute` (src/server/statemach.rs:193-202) for G groups, state resident on the device:
     commands [rows, G] are applied row after row; a Get returns the value, a Put the old value (0 = None)."""
+
+    _STEM, _SNAP = "smr_kv", KvSnapshot
 
     def __init__(self, n_groups, n_keys=16):
         self.G, self.K = int(n_groups), int(n_keys)
@@ -132,9 +206,11 @@ class KvStateMachine:
         return out
 
 
-class StringKvStateMachine:
+class StringKvStateMachine(_GroupStateCalls):
     """`StateMachineExecutorTask::execute` on `HashMap<String, String>` (src/server/statemach.rs:21-63,193-202) for G groups, keys
     and values as bytes, state resident on the device (`smr_skv_*`): a hash table + an append-only heap per group"""
+
+    _STEM, _SNAP = "smr_skv", StringKvSnapshot
 
     def __init__(self, n_groups, slots=256, heap_bytes=1 << 16):
         self.G, self.slots, self.heap_bytes = int(n_groups), int(slots), int(heap_bytes)
@@ -178,3 +254,40 @@ class StringKvStateMachine:
         nk, hu, fl = np.zeros(self.G, np.uint32), np.zeros(self.G, np.uint32), np.zeros(self.G, np.uint8)
         check(self._L.smr_skv_stats(self._h, nk.ctypes.data_as(C.c_void_p), hu.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p)))
         return dict(n_keys=nk, heap_used=hu, full=fl)
+
+    def compact(self, groups, snap=None, stream=None):
+        """the listed groups' heaps down to their live bytes: a `save_groups` and a `load_groups` of the same list into this
+        store (the table is rebuilt in rank order; (off, len) results returned earlier for these groups are no longer valid).
+        Do it before a heap fills: a group that is full already stays full.  Returns the snapshot, for the next call"""
+        snap = self.save_groups(groups, snap, stream)
+        self.load_groups(snap, groups, stream)
+        return snap
+
+    def debug_arena(self):
+        """(device address, bytes, offsets of hash, koff, klen, voff, vlen, heap, heap_used, full, n_keys) of the store's one
+        allocation (unstable: tests and measurement only)"""
+        p, n, offs = C.c_void_p(), C.c_uint64(), (C.c_uint64 * 9)()
+        check(self._L.smr_skv_debug_arena(self._h, C.byref(p), C.byref(n), C.byref(offs)))
+        return p.value, n.value, [int(x) for x in offs]
+
+    def debug_read(self, off, length):
+        """host copy of bytes [off, off + length) of that allocation (tests)"""
+        out = np.zeros(max(int(length), 1), np.uint8)
+        check(self._L.smr_skv_debug_read(self._h, int(off), int(length), out.ctypes.data_as(C.c_void_p)))
+        return out[:int(length)]
+
+
+def move_kv_groups(src, src_groups, dst, dst_groups, snap=None, reset=True):
+    """groups src_groups[i] of the token table `src` become groups dst_groups[i] of `dst`: save, load, and the source's groups
+    back to empty.  Returns the snapshot, for the next move of as many groups.  Call it beside the engine's own move of the same
+    groups; which job group sits where is the caller's table"""
+    snap = src.save_groups(src_groups, snap)
+    dst.load_groups(snap, dst_groups)
+    if reset:
+        src.reset_groups(src_groups)
+    return snap
+
+
+def move_skv_groups(src, src_groups, dst, dst_groups, snap=None, reset=True):
+    """the same for two string stores, of any two geometries the groups fit (read (off, len) results of the moved groups first)"""
+    return move_kv_groups(src, src_groups, dst, dst_groups, snap, reset)
