@@ -251,6 +251,9 @@ int smr_mp_run_ticks(smr_mp_cluster *c, const smr_mp_tick_in *ticks, uint32_t n,
  * image header (uint32 [2]) and the entries are lost: size ovf_cap for the leader changes a tick can hold. */
 enum { SMR_IMG_OUTBOX = 0, SMR_IMG_ACKS = 1, SMR_IMG_PREPARE_REPLIES = 2, SMR_IMG_HEARTBEAT = 3 };
 int smr_mp_set_live(smr_mp_cluster *c, uint32_t live_mask);
+/* the mask as it stands (every replica until smr_mp_set_live says otherwise): a snapshot made like `c` covers its set bits, and
+ * smr_mp_snapshot_from_wal takes one log per (set bit, group) */
+int smr_mp_get_live(const smr_mp_cluster *c, uint32_t *live_mask);
 /* Role rotation (round 3; needs straggler_ticks > 0 and every replica on this device).  The bulk round launches are a grid of
  * (64-group tiles) x (R rows); row y normally runs replica y of every group, so once leaders have moved a wavefront holds
  * leaders and followers side by side and runs both roles' code.  With rotation on, row y runs replica (y + leader[g]) mod R of
@@ -485,6 +488,44 @@ int smr_mp_snapshot_create_groups(const smr_mp_cluster *like, uint32_t n, smr_mp
 int smr_mp_save_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, smr_mp_snapshot *s, void *stream);
 int smr_mp_load_groups(smr_mp_cluster *c, const smr_mp_snapshot *s, const uint32_t *groups_host, uint32_t n, void *stream);
 int smr_mp_reset_groups(smr_mp_cluster *c, const uint32_t *groups_host, uint32_t n, void *stream);
+
+/* ---- a cluster's state from its WAL bytes, on the device --------------------------------------------------------------------
+ * replaces: MultiPaxosReplica::recover_from_wal / recover_apply_entry (multipaxos/recovery.rs:10-178) over read_entry
+ *           (server/storage.rs:240-278), which the crash-restart loop runs on every start (summerset_server/src/main.rs:124-167,
+ *           multipaxos/mod.rs:817-) -- for every (live replica, group) at once.
+ * What is left when the process or the device is gone is what the host's StorageHub wrote: one WAL per (replica, group), frames
+ * as smr_wal_prepare_bal / _accept_data / _commit_slot write them.  This call turns those bytes into the canonical image of a
+ * cluster in the recovered state, exactly as smr_mp_save_state would have written it; smr_mp_snapshot_info_get, _export,
+ * smr_mp_load_state and smr_mp_load_groups work on the result unchanged.
+ *   s              from smr_mp_snapshot_create or _create_groups: fixes n_groups, population, live mask (L live replicas),
+ *                  commit_extra.  n_logs = L x n_groups; log i * n_groups + j is the i-th live replica's log of image group j.
+ *   buf_dev        the logs' bytes (no alignment); log l is buf_dev[log_off_dev[l], log_off_dev[l + 1]) -- empty is fine.
+ *   tok_dev        the token journal: the engine never sees request bytes, a batch is an opaque 32-bit token and 0 the empty
+ *                  batch.  The k-th AcceptData frame of log l (applied or below start_slot) takes tok_dev[tok_off_dev[l] + k].
+ *                  Of `reqs` the device reads the first varint only (the Vec's length); the rest is located by the frame's
+ *                  length and not validated.
+ *   start_slot_dev per log, what recover_from_snapshot left (snapshot.rs:212-216: every bar = start_slot); NULL: 0.
+ *   max_span       the longest live span (log_len - start_slot) a log may reach: 1 .. the snapshot's room per log (the window
+ *                  of the cluster it was made like).
+ *   consumed_dev   [n_logs] the wal_offset, from the log's start, where the reference's final Truncate goes (recovery.rs:153-
+ *                  166): behind the last whole frame -- or in front of the frame the log stopped at;
+ *   status_dev     [n_logs] SMR_WAL_ST_*.  A log with a non-zero status stops in front of the offending frame and keeps the
+ *                  state of the entries before it; the image stays loadable.
+ *   counts_dev     [4] entries applied, entries ignored (below start_slot), logs with a non-zero status, logs with a cut tail
+ *                  (bytes behind the last whole frame: fewer than 8, or a length that passes the log's end -- not an error).
+ * Entries apply as recover_apply_entry's release build applies them; what recovery leaves of the rest: no leader, no
+ * bookkeeping, external = false, peer_exec_bar 0, empty outbox, no commits on the list, counters 0, overflow 0.
+ * SMR_ERR_ARG, everything untouched: a null argument, descending offsets, an offset past buf_len, max_span of 0 or above the
+ * snapshot's room.  The two offset arrays are read back to be checked (the call waits for `stream` once, before anything is
+ * written); the walks themselves -- two kernels -- are only enqueued. */
+#define SMR_WAL_ST_OK 0
+#define SMR_WAL_ST_MALFORMED 1 /* a length above 10^12, an unknown variant, fields that do not parse inside the frame */
+#define SMR_WAL_ST_ORDER 2     /* a CommitSlot at or beyond start_slot + len: the reference indexes out of range (recovery.rs:84) */
+#define SMR_WAL_ST_TOKEN 3     /* journal too short, a zero token for a non-empty batch or a non-zero one for an empty batch */
+#define SMR_WAL_ST_RANGE 4     /* a slot or a live span the image cannot hold: slot + 1 >= 2^32, or slot - start_slot >= max_span */
+int smr_mp_snapshot_from_wal(smr_mp_snapshot *s, const uint8_t *buf_dev, uint64_t buf_len, const uint64_t *log_off_dev /* [n_logs + 1] */,
+                             const uint32_t *tok_dev, const uint64_t *tok_off_dev, const uint32_t *start_slot_dev /* NULL: 0 */,
+                             uint32_t max_span, uint64_t *consumed_dev, int32_t *status_dev, uint64_t *counts_dev /* [4] */, void *stream);
 
 /* counters of replica `rep`: [0] leader-side commits (Accepting->Committed,
  * messages.rs:412-433), [1] redirected batches (request.rs:128-154),
@@ -1678,6 +1719,14 @@ int64_t smr_wal_prepare_bal(uint64_t slot, uint64_t ballot, uint8_t *out, uint64
 int64_t smr_wal_accept_data(uint64_t slot, uint64_t ballot, const uint8_t *reqs, uint64_t reqs_len, uint8_t *out,
                             uint64_t cap);
 int64_t smr_wal_commit_slot(uint64_t slot, uint8_t *out, uint64_t cap);
+/* read_entry's decode of one log frame (server/storage.rs:240-278 + bincode::decode_from_slice of WalEntry, mod.rs:261-274):
+ * the sequential decoder the device walk of smr_mp_snapshot_from_wal is checked against.  kind 0 PrepareBal, 1 AcceptData,
+ * 2 CommitSlot; AcceptData: reqs = buf[reqs_off, reqs_off + reqs_len), walked to its end as a ReqBatch.  Returns the bytes
+ * taken (8 + length), 0 where the frame is not complete in len (fewer than 8 bytes, or a length that passes len: the log's
+ * end), < 0 (SMR_ERR_ARG) for a length above 10^12, an unknown variant or fields that do not parse inside the frame.  Bytes
+ * after the fields inside the frame are tolerated, as decode_from_slice tolerates them. */
+typedef struct { uint8_t kind; uint64_t slot, ballot, reqs_off, reqs_len; } smr_wal_entry;
+int64_t smr_wal_decode(const uint8_t *buf, uint64_t len, smr_wal_entry *out);
 
 typedef struct {
     uint8_t kind;                  /* SMR_WIRE_* */
@@ -2146,9 +2195,11 @@ int smr_hb_dump(smr_hb *h, uint64_t *deadline, uint8_t *exploded, uint8_t *is_se
 
 /* ---- the WAL backer file as a byte image (server/storage.rs:240-432), host only ------------------------------------------
  * StorageHubLoggerTask's file operations -- write_entry (:282), append_entry (:326), read_entry (:240), truncate_log (:351),
- * discard_log (:375) -- on a growable host buffer that stands for the backer file.  Entries are the bincode bytes the
- * smr_wal_* encoders produce WITHOUT their frame header; the log writes `[u64 BE length][bytes]` itself.  `file_size` is the
- * logger's own idea of the log's end and is an argument, as in the reference's functions. */
+ * discard_log (:375) -- on a growable host buffer that stands for the backer file.  An entry handed to write / append is the
+ * bincode bytes of the WalEntry alone: the log writes `[u64 BE length][bytes]` itself.  The smr_wal_* encoders return a whole
+ * FRAME, its 8-byte length header included (as every smr_wire_* encoder does), so the entry of an encoder's n bytes in `out` is
+ * (out + 8, n - 8); the image then holds exactly the encoders' frames back to back, which is what smr_mp_snapshot_from_wal
+ * reads.  `file_size` is the logger's own idea of the log's end and is an argument, as in the reference's functions. */
 typedef struct smr_wallog smr_wallog;
 int smr_wallog_create(smr_wallog **out);
 void smr_wallog_destroy(smr_wallog *l);

@@ -211,6 +211,10 @@ class WireMsg(C.Structure):
                 ("replies_off", C.c_uint64), ("replies_len", C.c_uint64), ("from_leader", C.c_uint8)]
 
 
+class WalEntry(C.Structure):
+    _fields_ = [("kind", C.c_uint8), ("slot", C.c_uint64), ("ballot", C.c_uint64), ("reqs_off", C.c_uint64), ("reqs_len", C.c_uint64)]
+
+
 class WireCodeword(C.Structure):
     _fields_ = [("num_data_shards", C.c_uint8), ("num_parity_shards", C.c_uint8), ("avail_mask", C.c_uint32),
                 ("data_len", C.c_uint64), ("shard_len", C.c_uint64), ("shard_off", C.c_uint64 * 16)]
@@ -255,6 +259,7 @@ SYMBOLS = [
     ("smr_mp_tick", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _i, _vp]),
     ("smr_mp_run_ticks", _i, [_vp, C.POINTER(MpTickIn), _u32, _vp]),
     ("smr_mp_set_live", _i, [_vp, _u32]),
+    ("smr_mp_get_live", _i, [_vp, C.POINTER(_u32)]),
     ("smr_mp_set_role_rotation", _i, [_vp, _i]),
     ("smr_mp_image_bytes", C.c_int64, [_vp, _i, _u32, _u32]),
     ("smr_mp_image_pack", _i, [_vp, _i, _u8, _u8, _vp, _u64, _u32, _u32, _vp]),
@@ -307,6 +312,7 @@ SYMBOLS = [
     ("smr_mp_save_groups", _i, [_vp, _vp, _u32, _vp, _vp]),
     ("smr_mp_load_groups", _i, [_vp, _vp, _vp, _u32, _vp]),
     ("smr_mp_reset_groups", _i, [_vp, _vp, _u32, _vp]),
+    ("smr_mp_snapshot_from_wal", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("smr_mp_profile_enable", _i, [_vp, _i]),
     ("smr_mp_profile_read", _i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("smr_raft_leader_create", _i, [C.POINTER(RaftCfg), C.POINTER(_vp)]),
@@ -487,6 +493,7 @@ SYMBOLS = [
     ("smr_wal_prepare_bal", C.c_int64, [_u64, _u64, _vp, _u64]),
     ("smr_wal_accept_data", C.c_int64, [_u64, _u64, _vp, _u64, _vp, _u64]),
     ("smr_wal_commit_slot", C.c_int64, [_u64, _vp, _u64]),
+    ("smr_wal_decode", C.c_int64, [_vp, _u64, C.POINTER(WalEntry)]),
     ("smr_wire_decode", C.c_int64, [_vp, _u64, C.POINTER(WireMsg)]),
     ("smr_wire_read_query", C.c_int64, [_vp, _u64, _vp, _u64]),
     ("smr_wire_read_query_reply", C.c_int64, [_u64, _u64, _u32, _vp, _vp, _vp, _vp, _i, _vp, _u64]),

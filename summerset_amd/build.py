@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsummerset_hip.so")
 SOURCES = ["core.hip", "rs_kernels.hip", "mp_engine.hip", "raft_engine.hip", "ep_engine.hip", "ep_spread.hip", "rsp_engine.hip", "rsp_spread.hip", "rsp_payload.hip", "rep_nothing.hip", "wire.hip", "wire_ingest.hip", "wire_ingest_replies.hip", "wire_emit.hip", "qread.hip", "kv_exec.hip", "heartbeater.hip", "skv_exec.hip", "leaseman.hip", "comm.hip"]
-HEADERS = ["smr_common.h", "mp_types.h", "mp_device.h", "snapshot_common.h", "spread_common.h", "mp_snapshot.h", "rsp_peek.h", "raft_peek.h", "raft_snapshot.h", "rsp_snapshot.h", "ps_snapshot.h", "ep_snapshot.h", "skv_snapshot.h", "kv_snapshot.h", "wire_rd.h", os.path.join("..", "..", "include", "summerset_hip.h")]
+HEADERS = ["smr_common.h", "mp_types.h", "mp_device.h", "snapshot_common.h", "spread_common.h", "mp_snapshot.h", "mp_wal_replay.h", "rsp_peek.h", "raft_peek.h", "raft_snapshot.h", "rsp_snapshot.h", "ps_snapshot.h", "ep_snapshot.h", "skv_snapshot.h", "kv_snapshot.h", "wire_rd.h", os.path.join("..", "..", "include", "summerset_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 FLAGS += os.environ.get("SMR_EXTRA_HIPCC_FLAGS", "").split()       # e.g. -DSMR_JOB_STAMPS for tools/dbg_stamps.py

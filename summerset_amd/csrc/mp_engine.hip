@@ -16,6 +16,7 @@
 #include "mp_device.h"
 #include "smr_common.h"
 #include "mp_snapshot.h"
+#include "mp_wal_replay.h"
 
 // experiment (profiles/r9h): the bulk round kernels' wavefronts at a raised issue priority, so that on a SIMD they share with the
 // side launch's wavefronts they go first.  Off unless built with -DSMR_BULK_PRIO=1..3
@@ -2661,6 +2662,12 @@ int smr_mp_set_live(smr_mp_cluster *c, uint32_t live_mask) {
     return SMR_OK;
 }
 
+int smr_mp_get_live(const smr_mp_cluster *c, uint32_t *live_mask) {
+    if (!c || !live_mask) return fail(SMR_ERR_ARG, "mp: null argument");
+    *live_mask = c->hp.live;
+    return SMR_OK;
+}
+
 int64_t smr_mp_image_bytes(smr_mp_cluster *c, int kind, uint32_t rows, uint32_t ovf_cap) {
     if (!c || kind < SMR_IMG_OUTBOX || kind > SMR_IMG_HEARTBEAT) return fail(SMR_ERR_ARG, "mp: bad image kind");
     return (int64_t)img_layout((uint32_t)kind, c->cfg.n_groups, rows, ovf_cap).total;
@@ -3507,6 +3514,46 @@ int smr_mp_snapshot_import(smr_mp_snapshot *s, const uint8_t *host, uint64_t len
     }
     s->lead_hint = 0;
     return snap_obj_import_bytes<MpSnap>(s, host, h);
+}
+
+/* ---- a cluster's state from its WAL bytes (mp_wal_replay.h: the two walks) ------------------------------------------------------
+ * The offsets are read back once and checked before anything is launched (one copy in front, in stream order): a refused call
+ * leaves the snapshot and every output untouched.  The kernels clamp every log to the buffer all the same. */
+int smr_mp_snapshot_from_wal(smr_mp_snapshot *s, const uint8_t *buf_dev, uint64_t buf_len, const uint64_t *log_off_dev, const uint32_t *tok_dev,
+                             const uint64_t *tok_off_dev, const uint32_t *start_slot_dev, uint32_t max_span, uint64_t *consumed_dev,
+                             int32_t *status_dev, uint64_t *counts_dev, void *stream) {
+    if (!s || !log_off_dev || !tok_off_dev || !consumed_dev || !status_dev || !counts_dev || (!buf_dev && buf_len))
+        return fail(SMR_ERR_ARG, "mp wal replay: null argument");
+    const SnapGeom q = snap_geom(s->G, s->R, s->live);
+    const uint64_t n_logs = (uint64_t)q.L * s->G;
+    if (!s->buf.dev || max_span == 0 || max_span > s->cap[0] / n_logs)
+        return fail(SMR_ERR_ARG, "mp wal replay: max_span " + std::to_string(max_span) + " outside 1 .. the snapshot's room of " +
+                                     std::to_string(s->buf.dev ? s->cap[0] / n_logs : 0) + " slots per log");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<uint64_t> off(n_logs + 1), toff(n_logs + 1);
+    SMR_HIP_TRY(hipMemcpyAsync(off.data(), log_off_dev, (n_logs + 1) * 8, hipMemcpyDeviceToHost, st));
+    SMR_HIP_TRY(hipMemcpyAsync(toff.data(), tok_off_dev, (n_logs + 1) * 8, hipMemcpyDeviceToHost, st));
+    SMR_HIP_TRY(hipStreamSynchronize(st));
+    for (uint64_t l = 0; l < n_logs; l++) {
+        if (off[l] > off[l + 1]) return fail(SMR_ERR_ARG, "mp wal replay: the offsets of log " + std::to_string(l) + " descend");
+        if (toff[l] > toff[l + 1]) return fail(SMR_ERR_ARG, "mp wal replay: the journal offsets of log " + std::to_string(l) + " descend");
+    }
+    if (off[n_logs] > buf_len) return fail(SMR_ERR_ARG, "mp wal replay: a log offset past buf_len");
+    if (!tok_dev && toff[n_logs] != toff[0]) return fail(SMR_ERR_ARG, "mp wal replay: null argument");
+    WalArgs A;
+    A.buf = buf_dev; A.buf_len = buf_len; A.log_off = log_off_dev; A.tok = tok_dev; A.tok_off = tok_off_dev; A.start = start_slot_dev;
+    A.max_span = max_span; A.n_logs = (uint32_t)n_logs;
+    A.consumed = consumed_dev; A.status = status_dev; A.counts = (unsigned long long *)counts_dev;
+    const SnapImg S = snap_img(s);
+    s->buf.filled = false; s->buf.hdr_known = false;
+    SMR_HIP_TRY(hipMemsetAsync(counts_dev, 0, 4 * 8, st));
+    hipLaunchKernelGGL(mp_wal_span, dim3((uint32_t)((n_logs + 255) / 256)), dim3(256), 0, st, A, S);
+    SMR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mp_wal_apply, dim3(S.geo.tiles.nblock), dim3(256), 0, st, A, S);
+    SMR_HIP_TRY(hipGetLastError());
+    snap_obj_saved(s);
+    s->lead_hint = 0;
+    return SMR_OK;
 }
 
 }  // extern "C"

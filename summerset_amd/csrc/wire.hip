@@ -237,6 +237,29 @@ int64_t smr_wal_commit_slot(uint64_t slot, uint8_t *out, uint64_t cap) {
     return frame_done(w, out);
 }
 
+// read_entry (storage.rs:240-278) + decode_from_slice of a WalEntry: one frame of a log, sequentially
+int64_t smr_wal_decode(const uint8_t *buf, uint64_t len, smr_wal_entry *out) {
+    if (!buf || !out) return fail(SMR_ERR_ARG, "wal: null argument");
+    memset(out, 0, sizeof(*out));
+    if (len < 8) return 0;                                                       // :245-256
+    uint64_t plen = 0;
+    for (int i = 0; i < 8; i++) plen = (plen << 8) | buf[i];
+    if (plen > 1000000000000ull) return fail(SMR_ERR_ARG, "wal: invalidly large frame");
+    if (len - 8 < plen) return 0;                                                // :262-267
+    Rd r{buf + 8, plen};
+    const uint64_t v = r.varint();
+    if (!r.ok || v > 2) return fail(SMR_ERR_ARG, "wal: unknown WalEntry variant");
+    out->kind = (uint8_t)v;
+    out->slot = r.varint();
+    if (v != 2) out->ballot = r.varint();
+    if (v == 1) {
+        out->reqs_off = 8 + r.n;
+        if (skip_reqbatch(r)) out->reqs_len = 8 + r.n - out->reqs_off;
+    }
+    if (!r.ok) return fail(SMR_ERR_ARG, "wal: malformed frame");                 // (bytes behind the fields: decode_from_slice leaves them)
+    return (int64_t)(8 + plen);
+}
+
 int64_t smr_wire_decode(const uint8_t *buf, uint64_t len, smr_wire_msg *m) {
     if (!buf || !m) return fail(SMR_ERR_ARG, "wire: null argument");
     memset(m, 0, sizeof(*m));

@@ -42,6 +42,55 @@ class MpSnapshot(DeviceSnapshot):
         population, commit_extra and live mask (its window and capacities do not matter)"""
         return cls(like, n_groups).import_(data)
 
+    @classmethod
+    def from_wal(cls, like, logs, tokens, start_slot=None, n_groups=None, max_span=None, device=None, stream=None, snap=None):
+        """the snapshot of the state `recover_from_wal` (multipaxos/recovery.rs:10-178) leaves, out of the logs' bytes, on the
+        device (`smr_mp_snapshot_from_wal`).  `like`: a cluster of the image's population, commit_extra and live mask, and of its
+        n_groups unless given.  logs: one bytes object per (live replica, group) -- log i * n_groups + j is the i-th live
+        replica's log of group j -- or `(buf, off)`, a uint8 and an int64 [n_logs + 1] tensor already on the device; tokens:
+        per log the batch tokens of its AcceptData frames in order (0 = the empty batch), or `(tok, off)` as int32 / int64
+        tensors.  start_slot: per log, None = 0; max_span: the longest live span a log may reach, None = `like`'s window.
+        Returns (snapshot, consumed int64[n_logs], status int32[n_logs], counts int64[4]) -- the last three device tensors:
+        the offset the reference's final Truncate goes to, SMR_WAL_ST_*, and entries applied / entries ignored / logs with a
+        non-zero status / logs with a cut tail"""
+        import torch
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        snap = cls(like, n_groups) if snap is None else snap          # (snap: one made for `like` / n_groups before, filled again)
+        if isinstance(logs, tuple):
+            buf, off = logs
+        else:
+            off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(b) for b in logs], dtype=np.int64)]).astype(np.int64)).to(device)
+            buf = torch.from_numpy(np.frombuffer(b"".join(bytes(b) for b in logs) or b"\0", np.uint8).copy()).to(device)
+        if isinstance(tokens, tuple):
+            tok, toff = tokens
+        else:
+            toff = torch.from_numpy(np.concatenate([[0], np.cumsum([len(t) for t in tokens], dtype=np.int64)]).astype(np.int64)).to(device)
+            flat = np.asarray([x for t in tokens for x in t] or [0], dtype=np.int64).astype(np.uint32)
+            tok = torch.from_numpy(flat.view(np.int32)).to(device)
+        n_logs = int(off.numel()) - 1
+        if int(toff.numel()) != n_logs + 1:
+            raise ValueError("from_wal: %d logs, %d token lists" % (n_logs, int(toff.numel()) - 1))
+        G = like.G if n_groups is None else int(n_groups)          # (the library reads live replicas x n_groups + 1 offsets)
+        L = bin(like.live_mask()).count("1")
+        if n_logs != L * G:
+            raise ValueError("from_wal: %d logs, not one per (live replica, group) of %d live replicas x %d groups" % (n_logs, L, G))
+        s0 = None
+        if start_slot is not None:
+            s0 = start_slot if hasattr(start_slot, "data_ptr") else torch.from_numpy(
+                np.asarray(start_slot, dtype=np.int64).astype(np.uint32).view(np.int32)).to(device)
+            if int(s0.numel()) != n_logs:
+                raise ValueError("from_wal: %d logs, %d start slots" % (n_logs, int(s0.numel())))
+        consumed = torch.zeros(n_logs, dtype=torch.int64, device=device)
+        status = torch.zeros(n_logs, dtype=torch.int32, device=device)
+        counts = torch.zeros(4, dtype=torch.int64, device=device)
+        n_bytes = int(buf.numel()) if isinstance(logs, tuple) else sum(len(b) for b in logs)
+        check(snap._L.smr_mp_snapshot_from_wal(snap._h, _ptr(buf), n_bytes, _ptr(off), _ptr(tok), _ptr(toff), _ptr(s0),
+                                               int(like.W if max_span is None else max_span), _ptr(consumed), _ptr(status), _ptr(counts),
+                                               stream_ptr(stream)))
+        snap._wal_inputs = (buf, off, tok, toff, s0)              # the enqueued walks read them
+        return snap, consumed, status, counts
+
 
 class MultiPaxosCluster:
     def __init__(self, n_groups, population=5, window=64, win_reserve=None, outbox_cap=None, commit_extra=0,
@@ -68,6 +117,16 @@ class MultiPaxosCluster:
 
     def preset_leader(self, rep=0):
         check(self._L.smr_mp_preset_leader(self._h, rep))
+
+    def set_live(self, live_mask):
+        """bit r: replica r of this cluster object runs on this device, the others are images (`smr_mp_set_live`, layout L2)"""
+        check(self._L.smr_mp_set_live(self._h, int(live_mask)))
+
+    def live_mask(self):
+        """the live mask as it stands: every replica unless `set_live` said otherwise (`smr_mp_get_live`)"""
+        m = C.c_uint32()
+        check(self._L.smr_mp_get_live(self._h, C.byref(m)))
+        return int(m.value)
 
     def set_role_rotation(self, on=True):
         """row y of the bulk round launches runs replica (y + leader[g]) mod R of group g instead of replica y: wavefronts of
@@ -194,6 +253,17 @@ class MultiPaxosCluster:
         """group i of a len(groups) image overwrites group groups[i]; every other group, the counters and the commit list
         are left alone (`smr_mp_load_groups`)"""
         _snapshot.load_groups("smr_mp", self, snap, groups, stream)
+
+    def recover_from_wal(self, logs, tokens, start_slot=None, max_span=None, groups=None, device=None, stream=None):
+        """`MultiPaxosReplica::recover_from_wal` (recovery.rs:119-178) for every live replica of every group at once:
+        `MpSnapshot.from_wal` followed by `load_state`, or -- with `groups` -- by `load_groups` of a len(groups) image into
+        those groups, everything else left alone.  Returns what `from_wal` returns"""
+        out = MpSnapshot.from_wal(self, logs, tokens, start_slot, None if groups is None else len(groups), max_span, device, stream)
+        if groups is None:
+            self.load_state(out[0], stream)
+        else:
+            self.load_groups(out[0], groups, stream)
+        return out
 
     def reset_groups(self, groups, stream=None):
         """the listed groups back to what a new cluster holds: no leader, empty log (`smr_mp_reset_groups`)"""

@@ -96,6 +96,22 @@ def wal_commit_slot(slot):
     return _call("smr_wal_commit_slot", slot)
 
 
+WAL_PREPARE_BAL, WAL_ACCEPT_DATA, WAL_COMMIT_SLOT = range(3)
+
+
+def wal_decode(buf):
+    """first WalEntry frame of a log's bytes -> (bytes consumed, dict of kind / slot / ballot / reqs); (0, None) where the log ends
+    (fewer than 8 bytes, or a length that passes the end: storage.rs:240-267); raises for a malformed frame (`smr_wal_decode`)"""
+    e = _lib.WalEntry()
+    buf = bytes(buf)
+    n = _lib.load().smr_wal_decode(buf, len(buf), C.byref(e))
+    if n < 0:
+        check(int(n))
+    if n == 0:
+        return 0, None
+    return int(n), {"kind": int(e.kind), "slot": int(e.slot), "ballot": int(e.ballot), "reqs": buf[e.reqs_off:e.reqs_off + e.reqs_len]}
+
+
 def decode(buf):
     """first frame of buf -> (bytes consumed, dict) ; (0, None) if the frame is not complete yet"""
     m = WireMsg()
